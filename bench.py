@@ -82,6 +82,8 @@ def parse():
                         "(ah_comm_init_transport) carried by a gloo group, every rank on device LOCAL_RANK mod the visible devices — lets the "
                         "bench's own N > 1 code (communicator vote, watchdog, C4 / C5 with the owner merge) run on a 1-GPU box; not a measurement")
     p.add_argument("--dump", default=None, help="rank 0 writes the last C4 result and the merged C5 groups to this .npz (tests compare them with the oracle)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="rank 0 writes what the timed step computed in its last step to DIR/<name>.npy (float64; see dump_outputs)")
     p.add_argument("--no-kernels", action="store_true", help="skip the per-kernel table")
     p.add_argument("--traffic", type=float, default=None, help="HBM bytes/launch of the Add kernel from a rocprofv3 --pmc pass")
     return p.parse_args()
@@ -104,6 +106,32 @@ def fill_random(ctx, buf, rows, dtype, seed):
         buf.upload(chunk[:m], off * w)
         total += 1
     return chunk
+
+
+DUMP_SAMPLE_ROWS = 1 << 21   # --dump-outputs: Add rows written at most (three float64 files of this length: 48 MiB)
+
+
+def dump_outputs(out_dir, c, rows, step_sum):
+    """--dump-outputs: what a caller of the timed step holds after its last step — the Int64 Add's output column and the Float64
+    Sum — as float64 .npy files, so that two builds can be compared output for output.  The column is a fixed, seeded sample of
+    DUMP_SAMPLE_ROWS distinct rows (every row of a shorter column), read back in 2^22-row chunks; an Int64 does not fit a float64,
+    so each sampled value is written as its high (signed) and low (unsigned) 32-bit halves, both exact."""
+    os.makedirs(out_dir, exist_ok=True)
+    if rows <= DUMP_SAMPLE_ROWS:
+        idx = np.arange(rows, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(2024).choice(rows, DUMP_SAMPLE_ROWS, replace=False))
+    vals = np.empty(idx.size, np.int64)
+    chunk = 1 << 22
+    for off in range(0, rows, chunk):
+        lo, hi = np.searchsorted(idx, [off, off + chunk])
+        if hi > lo:
+            m = min(chunk, rows - off)
+            vals[lo:hi] = c.download(np.int64, m, off * 8)[idx[lo:hi] - off]
+    np.save(os.path.join(out_dir, "add_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "add_hi32.npy"), (vals >> 32).astype(np.float64))
+    np.save(os.path.join(out_dir, "add_lo32.npy"), (vals & 0xFFFFFFFF).astype(np.float64))
+    np.save(os.path.join(out_dir, "sum.npy"), np.array([step_sum], np.float64))
 
 
 def cpu_baseline(sample_rows, reps):
@@ -721,6 +749,9 @@ def main():
     ms_per_step = dt * 1e3 / max(args.steps, 1)
     add_ms = [ctx.event_elapsed_ms(2 * i, 2 * i + 1) for i in range(args.steps)]
     add_avg_ms = float(np.mean(add_ms)) if add_ms else float("nan")
+    if args.dump_outputs and rank == 0:   # before the sections below: C5 reuses the Add's output buffer for its keys
+        step_sum = float(part.item()) if use_dist and not gloo else float(part_buf.download(np.float64, 1)[0])
+        dump_outputs(args.dump_outputs, c, rows, step_sum)
 
     result = None
     if rank == 0:

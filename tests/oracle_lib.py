@@ -1,12 +1,16 @@
 """ctypes access to the CPU oracle (oracle/liboracle.so) and, when built, to the
-reference's own AVX2 machine code (oracle/_ref/libref_avx2.so, libref_c.so).
+reference's own AVX2 machine code (oracle/_ref/libref_avx2.so, libref_c.so).  Where
+oracle/_ref was not built, reference() answers from the outputs those libraries gave
+for the same calls, stored in tests/golden/reference_outputs.npz.
 
 TEST INFRASTRUCTURE: imported only by tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg.  All arguments are numpy arrays (host memory).
 """
 from __future__ import annotations
 
+import atexit
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -479,3 +483,187 @@ def load_reference():
     if not (os.path.exists(a) and os.path.exists(c)):
         return None
     return Reference(C.CDLL(a), C.CDLL(c))
+
+
+# ---- the reference's outputs, stored ------------------------------------------------------------------------------------------
+REFERENCE_GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_outputs.npz")
+RECORD_ENV = "AH_RECORD_REFERENCE"   # set by scripts/gen_reference_golden.py: record every call into the named file
+
+
+def _call_key(name, args) -> bytes:
+    """16-byte digest of one call: the method, every scalar argument, and each array argument's dtype, shape and bytes"""
+    h = hashlib.sha256(name.encode())
+    for a in args:
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a)
+            h.update(b"A" + a.dtype.str.encode() + repr(a.shape).encode() + a.tobytes())
+        elif isinstance(a, (type, np.dtype)):
+            h.update(b"T" + np.dtype(a).str.encode())
+        else:
+            h.update(b"S" + repr(a).encode())
+    return h.digest()[:16]
+
+
+def _to_parts(out):
+    """(kind, arrays): 0 = one array, 1 = one numpy scalar, 2 = a tuple of numpy scalars"""
+    if isinstance(out, np.ndarray):
+        return 0, [np.ascontiguousarray(out)]
+    if isinstance(out, tuple):
+        return 2, [np.asarray(v) for v in out]
+    return 1, [np.asarray(out)]
+
+
+def _from_parts(kind, parts):
+    if kind == 0:
+        return parts[0].copy()
+    if kind == 1:
+        return parts[0][()]
+    return tuple(p[()] for p in parts)
+
+
+def _same_parts(a, b) -> bool:
+    return len(a) == len(b) and all(x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+
+DIGEST_BYTES = 6   # 48 bits: a wrong answer passes with odds of (calls on record) / 2^48, ≈ 5e-11 per call
+
+
+def _answer_digest(key, kind, parts) -> bytes:
+    """48 bits of SHA-256 over a call's key and its complete answer (kind, and each part's dtype, shape and bytes)"""
+    h = hashlib.sha256(key + bytes([kind]))
+    for p in parts:
+        h.update(p.dtype.str.encode() + repr(p.shape).encode() + p.tobytes())
+    return h.digest()[:DIGEST_BYTES]
+
+
+def _oracle_counterpart(o: Oracle, name, args):
+    """the oracle's restatement of a Reference call, or None where it has none / refuses the input"""
+    try:
+        if name == "sum":
+            which, a = args
+            if a.dtype == np.float64:
+                return o.sum_float64_avx2order(a) if which == "avx2" else o.sum_float64_seq(a)
+            return o.sum_int64(a) if a.dtype == np.int64 else o.sum_uint64(a) if a.dtype == np.uint64 else None
+        if name == "arithmetic":
+            return o.arithmetic(*args)
+        if name == "arithmetic_unary":
+            return o.arithmetic_unary(*args)
+        if name == "comparison":
+            cmpop, shape, l, r, out_bits, off = args
+            return o.comparison(cmpop, shape, l, r, out_bits.copy(), off)
+        if name == "bitmap_aligned":
+            op, l, r = args
+            return o.bitmap_op(op, l, 0, r, 0, np.zeros(l.size, np.uint8), 0, l.size * 8)
+        if name == "cast_numeric":
+            st, out, _ = o.cast_numeric(args[0], args[1], None, 0, True, True)
+            return out if st == 0 else None
+        if name == "min_max":
+            return o.min_max(*args)
+    except AssertionError:
+        return None
+    return None
+
+
+class GoldenReference:
+    """Reference's methods, answered by the live libraries when oracle/_ref is built (each answer must agree with the stored record)
+    and from tests/golden/reference_outputs.npz when it is not.
+
+    The record holds, for a call whose answer the oracle's own restatement reproduces bit for bit, only a 64-bit digest of the call
+    and that answer: replaying it recomputes the oracle's answer and returns it if, and only if, its digest is on record — i.e. it
+    is the reference's answer (up to a 48-bit digest).  The few calls the oracle answers differently (or not at all) are stored whole.  A call the record
+    does not cover fails in both modes: scripts/gen_reference_golden.py rewrites the record where oracle/_ref is built."""
+
+    METHODS = ("sum", "arithmetic", "cast_numeric", "min_max", "arithmetic_unary", "comparison", "bitmap_aligned")
+
+    def __init__(self, live: Reference | None, record_to: str | None = None):
+        self.live, self.record_to = live, record_to
+        self.digests, self.stored = (set(), {}) if record_to else self._load(REFERENCE_GOLDEN)
+
+    @staticmethod
+    def _load(path):
+        if not os.path.exists(path):
+            return set(), {}
+        z = np.load(path)
+        keys, kinds, first, dtypes, shapes, off, blob = (z[k] for k in ("keys", "kinds", "first_part", "part_dtype", "part_shape",
+                                                                         "part_offset", "blob"))
+        parts = []
+        for i in range(len(dtypes)):
+            a = np.frombuffer(blob[off[i]:off[i + 1]].tobytes(), dtype=np.dtype(dtypes[i].decode()))
+            parts.append(a.reshape(()) if shapes[i] < 0 else a)
+        stored = {keys[i].tobytes(): (int(kinds[i]), parts[first[i]:first[i + 1]]) for i in range(len(keys))}
+        return set(d.tobytes() for d in z["digests"]), stored
+
+    def save(self, path):
+        keys, kinds, first, dtypes, shapes, off, chunks = [], [], [0], [], [], [0], []
+        for k, (kind, parts) in self.stored.items():
+            keys.append(np.frombuffer(k, np.uint8))
+            kinds.append(kind)
+            for p in parts:
+                dtypes.append(p.dtype.str)
+                shapes.append(-1 if p.ndim == 0 else p.size)
+                chunks.append(np.frombuffer(p.tobytes(), np.uint8))
+                off.append(off[-1] + p.nbytes)
+            first.append(len(dtypes))
+        np.savez_compressed(path, digests=np.frombuffer(b"".join(sorted(self.digests)), np.uint8).reshape(-1, DIGEST_BYTES),
+                            keys=np.array(keys, np.uint8).reshape(-1, 16), kinds=np.array(kinds, np.int8),
+                            first_part=np.array(first, np.int64), part_dtype=np.array(dtypes, "S8"),
+                            part_shape=np.array(shapes, np.int64), part_offset=np.array(off, np.int64),
+                            blob=np.concatenate(chunks) if chunks else np.zeros(0, np.uint8))
+
+    def _on_record(self, key, kind, parts) -> bool:
+        if key in self.stored:
+            s_kind, s_parts = self.stored[key]
+            return s_kind == kind and _same_parts(s_parts, parts)
+        return _answer_digest(key, kind, parts) in self.digests
+
+    def _call(self, name, args):
+        key = _call_key(name, args)
+        where = os.path.relpath(REFERENCE_GOLDEN, ROOT)
+        if self.live is not None:
+            out = getattr(self.live, name)(*args)
+            kind, parts = _to_parts(out)
+            if self.record_to:
+                mine = _oracle_counterpart(load_oracle(), name, args)
+                m_kind, m_parts = _to_parts(mine) if mine is not None else (None, [])
+                if m_kind == kind and _same_parts(m_parts, parts):
+                    self.digests.add(_answer_digest(key, kind, parts))
+                else:
+                    self.stored[key] = (kind, parts)
+            else:
+                assert self._on_record(key, kind, parts), \
+                    f"reference {name}: the live library's answer is not the one {where} holds for these inputs (rewrite it with " \
+                    "scripts/gen_reference_golden.py)"
+            return out
+        if key in self.stored:
+            res = _from_parts(*self.stored[key])
+        else:
+            res = _oracle_counterpart(load_oracle(), name, args)
+            if res is None or _answer_digest(key, *_to_parts(res)) not in self.digests:
+                raise AssertionError(f"reference {name}: {where} holds no answer for these inputs that the oracle reproduces — the oracle "
+                                     "departs from the reference here, or the record is out of date (scripts/gen_reference_golden.py)")
+        if name == "comparison":     # the live call writes into the caller's bitmap
+            args[4][...] = res
+            return args[4]
+        return res
+
+    def __getattr__(self, name):
+        if name not in GoldenReference.METHODS:
+            raise AttributeError(name)
+        return lambda *args: self._call(name, args)
+
+
+_golden = None
+
+
+def reference() -> GoldenReference:
+    """The reference's kernels for the CPU tests: live where oracle/_ref is built, else the stored record (never None)."""
+    global _golden
+    if _golden is None:
+        record_to = os.environ.get(RECORD_ENV)
+        live = load_reference()
+        if record_to and live is None:
+            raise RuntimeError(f"{RECORD_ENV}: recording needs oracle/_ref (make -C oracle ref)")
+        _golden = GoldenReference(live, record_to)
+        if record_to:
+            atexit.register(_golden.save, record_to)
+    return _golden

@@ -77,9 +77,7 @@ REF_INEXACT = {"big rows cancel exactly, small rows remain", "big rows cancel to
 
 @pytest.mark.parametrize("name", [k for k in CASES if k not in REF_INEXACT])
 def test_oracle_agrees_with_both_reference_orders(orc, name):
-    ref = OL.load_reference()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
+    ref = OL.reference()
     a = np.array(CASES[name], dtype=np.float64)
     want = float(orc.sum_float64_xreal(a))
     assert same(want, float(ref.sum("seq", a))), name
@@ -95,9 +93,7 @@ def test_oracle_agrees_with_both_reference_orders(orc, name):
 
 
 def test_reference_orders_disagree_on_intermediate_overflow(orc):
-    ref = OL.load_reference()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
+    ref = OL.reference()
     for name, want in (("intermediate overflow, exact sum 0", 0.0), ("intermediate overflow, exact sum finite", 1e308 + 4.0)):
         a = np.array(ORDER_DEPENDENT[name], dtype=np.float64)
         seq, avx = float(ref.sum("seq", a)), float(ref.sum("avx2", a))

@@ -62,9 +62,7 @@ def check(got, want, label):
 def test_seq_sum_is_the_reference_below_32_rows():
     """CPU: the Python model of the loop == oracle/_ref's two orders for every column the GPU test uses (and the two orders really
     part ways from 32 rows on, which is why the hand-over sits there)"""
-    ref = OL.load_reference()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
+    ref = OL.reference()
     rng = np.random.default_rng(5)
     for n in range(0, 32):
         for _, col in columns(n, rng):
