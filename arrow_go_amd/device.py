@@ -25,6 +25,12 @@ def _ptr(x) -> Optional[int]:
     return int(x)
 
 
+class SortKey(C.Structure):
+    """ah_sort_key (include/arrowhip.h)"""
+    _fields_ = [("type", C.c_int), ("values", C.c_void_p), ("offsets", C.c_void_p), ("byte_width", C.c_int), ("valid", C.c_void_p),
+                ("off", C.c_int64), ("descending", C.c_int), ("nulls_at_start", C.c_int)]
+
+
 class DeviceBuffer:
     """A device allocation owned by a Context (ah_buf_alloc / ah_buf_free)."""
 
@@ -527,6 +533,15 @@ class Context:
         desc = (C.c_int * k)(*[int(x[4]) for x in keys])
         nfirst = (C.c_int * k)(*[int(x[5]) for x in keys])
         check(self.handle, lib.ah_sort_indices_multi(self.handle, k, types, vals, valids, offs, n, desc, nfirst, _ptr(out_indices)))
+
+    def sort_indices_keys(self, keys, n: int, out_indices) -> None:
+        """keys: [(type_id, values, offsets, byte_width, valid, off, descending, nulls_at_start), …] — most significant first; row i
+        is element off + i of every buffer (ah_sort_key, include/arrowhip.h)"""
+        arr = (SortKey * len(keys))()
+        for s, (t, v, o, w, m, off, d, nf) in zip(arr, keys):
+            s.type, s.values, s.offsets, s.byte_width, s.valid, s.off = t, _ptr(v), _ptr(o), w, _ptr(m), off
+            s.descending, s.nulls_at_start = int(d), int(nf)
+        check(self.handle, lib.ah_sort_indices_keys(self.handle, len(keys), arr, n, _ptr(out_indices)))
 
     def take_boolean(self, data, vvalid, voff: int, nvalues: int, idx_byte_width: int, idx_signed: bool, idx, ivalid, ioff: int, nidx: int,
                      out_data, out_valid) -> int:

@@ -1259,24 +1259,34 @@ static Status SortIndicesImpl(ExecCtx* ctx, const FunctionOptions* o, const std:
     if (length < 0) length = a.array->length;
     else if (length != a.array->length) return Status::Make(StatusCode::Invalid, "all columns must have the same length");  // kernels :403-407
   }
-  std::vector<int> types, desc, nfirst;
-  std::vector<const void*> values;
-  std::vector<const uint8_t*> valids;
-  std::vector<int64_t> offs;
+  std::vector<ah_sort_key> skeys;
   for (size_t i = 0; i < keys.size(); i++) {
     const SortKey& key = keys[i];
     if (key.ColumnIndex < 0 || key.ColumnIndex >= (int)args.size())
       return Status::Make(StatusCode::Invalid, "sort key " + std::to_string(i) + " has invalid column index " + std::to_string(key.ColumnIndex));  // :158-160
     const ArrayData& a = *args[key.ColumnIndex].array;
-    if (!IsInteger(a.type->id) && !IsFloating(a.type->id))
+    const Type id = a.type->id;
+    auto dptr = [&](int b) -> const void* { return a.buffers[b] ? a.buffers[b]->dptr : nullptr; };
+    ah_sort_key k{};
+    if (IsInteger(id) || IsFloating(id)) {
+      k.type = (int)id;
+      k.values = a.length ? dptr(1) : nullptr;
+    } else if (id == Type::STRING || id == Type::BINARY || id == Type::LARGE_STRING || id == Type::LARGE_BINARY) {  // :225-232
+      k.type = (id == Type::STRING || id == Type::BINARY) ? AH_BINARY : AH_LARGE_BINARY;
+      k.offsets = dptr(1);
+      k.values = dptr(2);
+    } else if (IsFixedWidthBinary(id)) {  // FixedSizeBinary :233-234, Decimal128 / 256 :213-216
+      k.type = (int)id;
+      k.values = dptr(1);
+      k.byte_width = a.type->bit_width / 8;
+    } else {
       return Status::Make(StatusCode::NotImplemented, std::string("sorting not supported for type ") + a.type->name);  // :266-268
-    int w = a.type->bit_width / 8;
-    types.push_back((int)a.type->id);
-    values.push_back(a.length ? (const uint8_t*)a.buffers[1]->dptr + a.offset * w : nullptr);
-    valids.push_back((a.buffers[0] && a.null_count != 0) ? (const uint8_t*)a.buffers[0]->dptr : nullptr);
-    offs.push_back(a.offset);
-    desc.push_back(key.Order == SortOrderDescending);
-    nfirst.push_back(key.Placement == SortNullsAtStart);
+    }
+    k.valid = (a.buffers[0] && a.null_count != 0) ? (const uint8_t*)a.buffers[0]->dptr : nullptr;
+    k.off = a.offset;
+    k.descending = key.Order == SortOrderDescending;
+    k.nulls_at_start = key.Placement == SortNullsAtStart;
+    skeys.push_back(k);
   }
   auto res = std::make_shared<ArrayData>();
   res->type = GetDataType(Type::UINT64);
@@ -1284,8 +1294,7 @@ static Status SortIndicesImpl(ExecCtx* ctx, const FunctionOptions* o, const std:
   res->null_count = 0;
   AHC_RETURN_NOT_OK(s->Allocate(length * 8, &res->buffers[1], /*zero_all=*/false));
   if (length > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_sort_indices_multi(s->ctx(), (int)keys.size(), types.data(), values.data(), valids.data(), offs.data(), length,
-                                                          desc.data(), nfirst.data(), (uint64_t*)res->buffers[1]->dptr)));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_sort_indices_keys(s->ctx(), (int)skeys.size(), skeys.data(), length, (uint64_t*)res->buffers[1]->dptr)));
   *out = Datum::Of(res);
   return Status::OK();
 }

@@ -226,6 +226,46 @@ func (x *Context) SortIndicesMulti(keys []SortKey, n int64, outIndices unsafe.Po
 	return x.err(C.ah_sort_indices_multi(x.c, C.int(k), &types[0], (*unsafe.Pointer)(vals), (**C.uint8_t)(valids), &offs[0], C.int64_t(n), &desc[0], &nulls[0], (*C.uint64_t)(outIndices)))
 }
 
+// SortColumn is one key of SortIndicesKeys: a numeric column (Values), a String / Binary / LargeString / LargeBinary column
+// (Values = the data buffer, Offsets = the offsets buffer) or a FixedSizeBinary / Decimal128 / Decimal256 column (Values = the
+// slots, ByteWidth = their width).  Row i of the call is element Off + i of every buffer and bit Off + i of Valid.
+type SortColumn struct {
+	Type         arrow.Type
+	Values       unsafe.Pointer
+	Offsets      unsafe.Pointer
+	ByteWidth    int
+	Valid        unsafe.Pointer
+	Off          int64
+	Descending   bool
+	NullsAtStart bool
+}
+
+// SortIndicesKeys mirrors sort_indices over keys of every sortable kind (kernels/vector_sort.go:195-245): stable, lexicographic
+// by key 0, 1, …; binary values bytewise, decimals by value.  The key table is built in C memory, as in SortIndicesMulti.
+func (x *Context) SortIndicesKeys(keys []SortColumn, n int64, outIndices unsafe.Pointer) error {
+	k := len(keys)
+	if k == 0 {
+		return fmt.Errorf("%w: arrowhip: SortIndicesKeys wants at least one key", arrow.ErrInvalid)
+	}
+	var one C.ah_sort_key
+	tbl := C.malloc(C.size_t(k) * C.size_t(unsafe.Sizeof(one)))
+	defer C.free(tbl)
+	ks := unsafe.Slice((*C.ah_sort_key)(tbl), k)
+	for i, key := range keys {
+		typ := C.int(key.Type)
+		switch key.Type {
+		case arrow.STRING:
+			typ = C.AH_BINARY
+		case arrow.LARGE_STRING:
+			typ = C.AH_LARGE_BINARY
+		}
+		ks[i]._type, ks[i].values, ks[i].offsets, ks[i].byte_width = typ, key.Values, key.Offsets, C.int(key.ByteWidth)
+		ks[i].valid, ks[i].off = (*C.uint8_t)(key.Valid), C.int64_t(key.Off)
+		ks[i].descending, ks[i].nulls_at_start = boolInt(key.Descending), boolInt(key.NullsAtStart)
+	}
+	return x.err(C.ah_sort_indices_keys(x.c, C.int(k), (*C.ah_sort_key)(tbl), C.int64_t(n), (*C.uint64_t)(outIndices)))
+}
+
 // ---- ingest slots: the building blocks of Ingest for callers that run their own kernels on the chunks ------------------------
 
 func (i *Ingest) Depth() int      { return int(C.ah_ingest_depth(i.g)) }

@@ -58,6 +58,11 @@ extern "C" {
 #define AH_INT64 9
 #define AH_FLOAT32 11
 #define AH_FLOAT64 12
+#define AH_BINARY 14             /* also String: same bytes, same order */
+#define AH_FIXED_SIZE_BINARY 15
+#define AH_DECIMAL128 23
+#define AH_DECIMAL256 24
+#define AH_LARGE_BINARY 35       /* also LargeString */
 
 /* ArithmeticOp — kernels/base_arithmetic.go:37-82 == kernels/_lib/base_arithmetic.cc:31-74 */
 #define AH_OP_ADD 0
@@ -608,6 +613,27 @@ int ah_sort_indices(ah_ctx* ctx, int type, const void* values, const uint8_t* va
  * by key 0, then key 1, …, each with its own order and null placement; stable.  Arrays of nkeys entries. */
 int ah_sort_indices_multi(ah_ctx* ctx, int nkeys, const int* types, const void* const* values, const uint8_t* const* valids,
                           const int64_t* offs, int64_t n, const int* descending, const int* nulls_at_start, uint64_t* out_indices);
+/* one sort key of ah_sort_indices_keys; row i of the call is element off + i of every buffer and bit off + i of `valid`
+ * (nullable).  type: a numeric id (values = the values), AH_BINARY / AH_LARGE_BINARY (values = the DATA buffer, offsets = the
+ * 4- / 8-byte offsets buffer; values may be null when every value is empty), AH_FIXED_SIZE_BINARY (values = the slots,
+ * byte_width = the width) or AH_DECIMAL128 / AH_DECIMAL256 (values = the slots, byte_width = 16 / 32). */
+typedef struct ah_sort_key {
+  int type;
+  const void* values;
+  const void* offsets;
+  int byte_width;
+  const uint8_t* valid;
+  int64_t off;
+  int descending;
+  int nulls_at_start;
+} ah_sort_key;
+/* sort_indices over keys of any sortable kind (kernels.SortIndices, kernels/vector_sort.go:388-481, with the binary, fixed-size
+ * binary and decimal comparators of vector_sort.go:195-245; record batches as ah_sort_indices_multi): lexicographic by key 0,
+ * 1, …; stable.  Binary and fixed-size binary values order bytewise, unsigned, a proper prefix first ("ab" < "ab\0" < "abc");
+ * decimals by signed value.  Nulls of every key go to its end or start in input order; no NaN category outside the floats.
+ * Binary keys are sorted in rounds of 7 bytes: a round re-sorts only the rows still tied.  Data buffers of
+ * the 64-bit-offset types may exceed 4 GiB.  Synchronises. */
+int ah_sort_indices_keys(ah_ctx* ctx, int nkeys, const ah_sort_key* keys, int64_t n, uint64_t* out_indices);
 
 /* Boolean VALUES (booleanTakeImpl, kernels/vector_selection.go:990-1074): data and validity are bitmaps
  * indexed at voff + idx; a null output keeps data bit 0.  Output bitmaps start at bit 0.  Filter of a
