@@ -143,6 +143,9 @@ _SIGS = {
     "ah_shift_time": [_vp, _int, _int, _int, _i64, _int, _vp, _vp, _i64, _i64, _vp, _vp],
     "ah_cast_bool_to_numeric": [_vp, _int, _vp, _i64, _i64, _vp],
     "ah_is_in": [_vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _int, _vp, _vp, _i64],
+    "ah_is_in_binary": [_vp, _int, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _vp, _vp, _i64],
+    "ah_is_in_fixed": [_vp, _int, _vp, _vp, _i64, _i64, _int, _vp, _int, _vp, _vp, _i64],
+    "ah_is_in_dict_gather": [_vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64],
     "ah_sort_indices": [_vp, _int, _vp, _vp, _i64, _i64, _int, _int, _vp],
     "ah_wait_event": [_vp, _vp],
     "ah_device_id": [_vp],

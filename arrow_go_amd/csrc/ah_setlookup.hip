@@ -17,6 +17,7 @@
 // as whole 64-bit words (read-modify-write only where the output range is not word-aligned).
 // Algorithmic bytes: w + 2/8 per row (+ 1/8 with an input validity bitmap).
 #include "ah_common.h"
+#include "ah_setlookup.h"
 
 namespace {
 
@@ -24,8 +25,6 @@ constexpr int kBlock = 256;
 constexpr int kLdsSlots = 4096;  // 32 KiB of 8-byte slots: sets of up to 1024 keys probe in LDS
 constexpr unsigned long long kEmpty = ~0ull;
 constexpr int kChunks = 8;  // 64-row chunks per wave step
-
-enum { kFlagSetHasNull = 1u, kFlagAllOnesKey = 2u };
 
 // slot index: membership only needs SOME well-mixed hash; two 32-bit multiplies are ≈ 3× cheaper
 // on CDNA4 than the reference's 64-bit hashInt (bswap64(PRIME·v): three v_mul_lo + one v_mul_hi)
@@ -74,31 +73,6 @@ __global__ __launch_bounds__(kBlock) void build_hash_kernel(const void* __restri
   }
 }
 
-// ---- output: bits [pos, pos + cnt) := low cnt bits of `word`, every other bit preserved -----
-__device__ __forceinline__ void put_bits(uint8_t* __restrict__ bm, int64_t pos, unsigned long long word, int cnt) {
-  const uintptr_t addr = (uintptr_t)bm + (uintptr_t)(pos >> 3);
-  const int sub = (int)(pos & 7);
-  if (cnt == 64 && sub == 0 && (addr & 7) == 0) {
-    *(unsigned long long*)addr = word;
-    return;
-  }
-  // general position: up to three aligned 32-bit words, atomics because a neighbouring chunk may
-  // own the other bits of the same word
-  const uintptr_t base = addr & ~(uintptr_t)3;
-  int shift = (int)((addr - base) * 8) + sub;  // 0..31
-  const unsigned long long m = cnt >= 64 ? ~0ull : ((1ull << cnt) - 1);
-  word &= m;
-  unsigned* w = (unsigned*)base;
-  // 96-bit window
-  const unsigned long long mlo = m << shift, vlo = word << shift;
-  const unsigned long long mhi = shift ? (m >> (64 - shift)) : 0ull, vhi = shift ? (word >> (64 - shift)) : 0ull;
-  const unsigned m0 = (unsigned)mlo, m1 = (unsigned)(mlo >> 32), m2 = (unsigned)mhi;
-  const unsigned v0 = (unsigned)vlo, v1 = (unsigned)(vlo >> 32), v2 = (unsigned)vhi;
-  if (m0) { atomicAnd(&w[0], ~m0); if (v0) atomicOr(&w[0], v0); }
-  if (m1) { atomicAnd(&w[1], ~m1); if (v1) atomicOr(&w[1], v1); }
-  if (m2) { atomicAnd(&w[2], ~m2); if (v2) atomicOr(&w[2], v2); }
-}
-
 // ---- probe -----------------------------------------------------------------------------------
 // MODE 0: bitmap in LDS (W ≤ 2) · 1: hash table in LDS (≤ 4096 slots, 32 KiB) · 2: hash table in HBM · 3: hash table in
 // LDS, 16 384 slots = 128 KiB of gfx950's 160 KiB, one 1024-thread workgroup per CU (sets of up to 4096 keys: 2–4× faster
@@ -127,11 +101,8 @@ __global__ __launch_bounds__(BLOCK) void is_in_kernel(const void* __restrict__ v
     __syncthreads();
   }
   const unsigned fl = flags[0];
-  const bool set_has_null = (fl & kFlagSetHasNull) && null_behavior != AH_NULL_SKIP;
-  // valid row: (found, found ∨ vmiss) · null row: (dnull, vnull)
-  const bool vmiss = !(null_behavior == AH_NULL_INCONCLUSIVE && set_has_null);
-  const bool dnull = null_behavior == AH_NULL_MATCH && set_has_null;
-  const bool vnull = dnull || null_behavior == AH_NULL_SKIP || (!set_has_null && null_behavior == AH_NULL_MATCH);
+  const NullRule rule = null_rule(fl, null_behavior);
+  const bool vmiss = rule.vmiss, dnull = rule.dnull, vnull = rule.vnull;
   const bool all_ones_in_set = fl & kFlagAllOnesKey;
   const int lane = threadIdx.x & 63;
   const int64_t nchunks = (n + 63) >> 6;
@@ -213,8 +184,10 @@ void launch_probe(ah_ctx* c, unsigned grid, const void* values, const uint8_t* v
 }
 
 template <int W>
-int run_is_in(ah_ctx* c, const void* values, const uint8_t* valid, int64_t off, int64_t n, const void* set_values, const uint8_t* set_valid,
-              int64_t set_off, int64_t set_n, int null_behavior, uint8_t* out_data, uint8_t* out_valid, int64_t out_off) {
+int run_is_in(ah_ctx* c, const void* values, const uint8_t* valid, int64_t off, int64_t n, int nparts, const SetPart* parts, int null_behavior,
+              uint8_t* out_data, uint8_t* out_valid, int64_t out_off) {
+  int64_t set_n = 0;
+  for (int p = 0; p < nparts; p++) set_n += parts[p].n;
   const bool bitmap = W <= 2;
   unsigned long long cap = 64;  // load ≤ ¼: short probe chains matter more than table bytes
   int log2cap = 6;
@@ -229,10 +202,12 @@ int run_is_in(ah_ctx* c, const void* values, const uint8_t* valid, int64_t off, 
   void* tab = (uint8_t*)scratch + 128;
   AH_HIP(c, hipMemsetAsync(flags, 0, 128, c->stream));
   AH_HIP(c, hipMemsetAsync(tab, bitmap ? 0 : 0xFF, table_bytes, c->stream));
-  if (set_n > 0) {
-    const unsigned g = ah_stream_grid(c, ah_ceil_div(set_n, kBlock), 8);
-    if constexpr (W <= 2) build_bitmap_kernel<W><<<g, kBlock, 0, c->stream>>>(set_values, set_valid, set_off, set_n, (unsigned*)tab, flags);
-    else build_hash_kernel<W><<<g, kBlock, 0, c->stream>>>(set_values, set_valid, set_off, set_n, (unsigned long long*)tab, (unsigned)(cap - 1), shift, flags);
+  for (int p = 0; p < nparts; p++) {  // every piece of a chunked value set goes into the same table
+    const SetPart& sp = parts[p];
+    if (sp.n == 0) continue;
+    const unsigned g = ah_stream_grid(c, ah_ceil_div(sp.n, kBlock), 8);
+    if constexpr (W <= 2) build_bitmap_kernel<W><<<g, kBlock, 0, c->stream>>>(sp.values, sp.valid, sp.valid_off, sp.n, (unsigned*)tab, flags);
+    else build_hash_kernel<W><<<g, kBlock, 0, c->stream>>>(sp.values, sp.valid, sp.valid_off, sp.n, (unsigned long long*)tab, (unsigned)(cap - 1), shift, flags);
     AH_LAUNCH_CHECK(c);
   }
   const int64_t nchunks = ah_ceil_div(n, 64);
@@ -259,6 +234,20 @@ int run_is_in(ah_ctx* c, const void* values, const uint8_t* valid, int64_t off, 
 
 }  // namespace
 
+int ah_is_in_parts(ah_ctx* c, int byte_width, const void* values, const uint8_t* valid, int64_t off, int64_t n, int nparts, const SetPart* parts,
+                   int null_behavior, uint8_t* out_data, uint8_t* out_valid, int64_t out_bit_offset) {
+  if (((uintptr_t)values) & (uintptr_t)(byte_width - 1)) return ah_fail(c, AH_EINVALID, "is_in: buffer not element-aligned");
+  for (int p = 0; p < nparts; p++)
+    if (((uintptr_t)parts[p].values) & (uintptr_t)(byte_width - 1)) return ah_fail(c, AH_EINVALID, "is_in: buffer not element-aligned");
+  switch (byte_width) {
+    case 1: return run_is_in<1>(c, values, valid, off, n, nparts, parts, null_behavior, out_data, out_valid, out_bit_offset);
+    case 2: return run_is_in<2>(c, values, valid, off, n, nparts, parts, null_behavior, out_data, out_valid, out_bit_offset);
+    case 4: return run_is_in<4>(c, values, valid, off, n, nparts, parts, null_behavior, out_data, out_valid, out_bit_offset);
+    case 8: return run_is_in<8>(c, values, valid, off, n, nparts, parts, null_behavior, out_data, out_valid, out_bit_offset);
+  }
+  return ah_fail(c, AH_ENOTIMPL, "is_in: fixed-width values of 1, 2, 4 or 8 bytes only (got %d)", byte_width);
+}
+
 AH_EXPORT int ah_is_in(ah_ctx* c, int byte_width, const void* values, const uint8_t* valid, int64_t off, int64_t n, const void* set_values,
                        const uint8_t* set_valid, int64_t set_off, int64_t set_n, int null_behavior, uint8_t* out_data, uint8_t* out_valid,
                        int64_t out_bit_offset) {
@@ -267,12 +256,6 @@ AH_EXPORT int ah_is_in(ah_ctx* c, int byte_width, const void* values, const uint
   if (null_behavior < AH_NULL_MATCH || null_behavior > AH_NULL_INCONCLUSIVE) return ah_fail(c, AH_EINVALID, "is_in: bad null matching behavior %d", null_behavior);
   if (n == 0) return AH_OK;
   if (!values || !out_data || !out_valid || (set_n > 0 && !set_values)) return ah_fail(c, AH_EINVALID, "is_in: null buffer");
-  if (((uintptr_t)values | (uintptr_t)set_values) & (uintptr_t)(byte_width - 1)) return ah_fail(c, AH_EINVALID, "is_in: buffer not element-aligned");
-  switch (byte_width) {
-    case 1: return run_is_in<1>(c, values, valid, off, n, set_values, set_valid, set_off, set_n, null_behavior, out_data, out_valid, out_bit_offset);
-    case 2: return run_is_in<2>(c, values, valid, off, n, set_values, set_valid, set_off, set_n, null_behavior, out_data, out_valid, out_bit_offset);
-    case 4: return run_is_in<4>(c, values, valid, off, n, set_values, set_valid, set_off, set_n, null_behavior, out_data, out_valid, out_bit_offset);
-    case 8: return run_is_in<8>(c, values, valid, off, n, set_values, set_valid, set_off, set_n, null_behavior, out_data, out_valid, out_bit_offset);
-  }
-  return ah_fail(c, AH_ENOTIMPL, "is_in: fixed-width values of 1, 2, 4 or 8 bytes only (got %d)", byte_width);
+  const SetPart part{set_values, set_valid, set_off, set_n};
+  return ah_is_in_parts(c, byte_width, values, valid, off, n, 1, &part, null_behavior, out_data, out_valid, out_bit_offset);
 }

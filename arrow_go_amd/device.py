@@ -243,6 +243,11 @@ class Comm:
         check(self.ctx.handle, lib.ah_comm_alltoallv(self.handle, _ptr(send), arr(send_bytes), arr(send_offs), _ptr(recv), arr(recv_bytes), arr(recv_offs)))
 
 
+class _SetChunk(C.Structure):  # ah_set_chunk (arrowhip.h)
+    _fields_ = [("offset_width", C.c_int), ("offsets", C.c_void_p), ("data", C.c_void_p), ("valid", C.c_void_p), ("off", C.c_int64),
+                ("n", C.c_int64)]
+
+
 class Context:
     """ah_ctx: one GPU, a compute stream and a copy stream."""
 
@@ -511,6 +516,31 @@ class Context:
               null_behavior: int, out_data, out_valid, out_bit_offset: int = 0) -> None:
         check(self.handle, lib.ah_is_in(self.handle, byte_width, _ptr(values), _ptr(valid), off, n, _ptr(set_values), _ptr(set_valid),
                                         set_off, set_n, null_behavior, _ptr(out_data), _ptr(out_valid), out_bit_offset))
+
+    @staticmethod
+    def _set_pieces(pieces):
+        """[(offset_width, offsets, data, valid, off, n), …] → an ah_set_chunk table (offset_width 0: fixed-width piece)"""
+        tbl = (_SetChunk * max(len(pieces), 1))()
+        for i, (ow, offs, data, valid, off, n) in enumerate(pieces):
+            tbl[i] = _SetChunk(ow, _ptr(offs), _ptr(data), _ptr(valid), off, n)
+        return tbl
+
+    def is_in_binary(self, offset_width: int, offsets, data, valid, off: int, n: int, set_pieces, null_behavior: int, out_data, out_valid,
+                     out_bit_offset: int = 0) -> None:
+        tbl = self._set_pieces(set_pieces)
+        check(self.handle, lib.ah_is_in_binary(self.handle, offset_width, _ptr(offsets), _ptr(data), _ptr(valid), off, n, len(set_pieces), tbl,
+                                               null_behavior, _ptr(out_data), _ptr(out_valid), out_bit_offset))
+
+    def is_in_fixed(self, byte_width: int, data, valid, off: int, n: int, set_pieces, null_behavior: int, out_data, out_valid,
+                    out_bit_offset: int = 0) -> None:
+        tbl = self._set_pieces(set_pieces)
+        check(self.handle, lib.ah_is_in_fixed(self.handle, byte_width, _ptr(data), _ptr(valid), off, n, len(set_pieces), tbl, null_behavior,
+                                              _ptr(out_data), _ptr(out_valid), out_bit_offset))
+
+    def is_in_dict_gather(self, index_width: int, indices, valid, off: int, n: int, lut_data, lut_valid, lut_n: int, out_data, out_valid,
+                          out_bit_offset: int = 0) -> None:
+        check(self.handle, lib.ah_is_in_dict_gather(self.handle, index_width, _ptr(indices), _ptr(valid), off, n, _ptr(lut_data), _ptr(lut_valid),
+                                                     lut_n, _ptr(out_data), _ptr(out_valid), out_bit_offset))
 
     # ---- min / max ----------------------------------------------------------------------
     def min_max(self, type_id: int, values, n: int, dtype):

@@ -284,6 +284,10 @@ struct CastOptions : FunctionOptions {
 enum NullMatchingBehavior { NullMatchingMatch = 0, NullMatchingSkip = 1, NullMatchingEmitNull = 2, NullMatchingInconclusive = 3 };
 struct SetOptions : FunctionOptions {
   ArrayDataPtr ValueSet;  // device array (ArrayDatum)
+  // a ChunkedDatum value set (initSetLookup's KindChunked case, compute/scalar_set_lookup.go:126-131): used when ValueSet is
+  // null; every chunk goes into the one lookup table
+  std::vector<ArrayDataPtr> ValueSetChunks;
+  const DataType* ValueSetChunkedType = nullptr;
   NullMatchingBehavior NullBehavior = NullMatchingMatch;
   const char* TypeName() const override { return "SetOptions"; }
 };

@@ -365,6 +365,7 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
       if (k == "value_set" && v.size() > 1 && v[0] == '@') {
         ahc_datum* d = (ahc_datum*)(uintptr_t)strtoull(v.c_str() + 1, nullptr, 16);
         if (d && d->d.kind == DatumKind::Array) p->set.ValueSet = d->d.array;
+        if (d && d->d.kind == DatumKind::Chunked) { p->set.ValueSetChunks = d->d.chunks; p->set.ValueSetChunkedType = d->d.chunked_type; }
         p->pick = &p->set;
       }
       if (k == "null_matching_behavior") {

@@ -1261,6 +1261,16 @@ Status CallTemporal(ExecCtx* ctx, const std::string& name, const FunctionOptions
       for (size_t i = 1; i < args.size(); i++) if (!SameTemporal(lg[0], lg[i])) return refuse();
       if (name == "is_in") {
         auto* so = dynamic_cast<const SetOptions*>(opts);
+        if (so && !so->ValueSet && !so->ValueSetChunks.empty()) {  // a chunked value set: every chunk of the column's type
+          SetOptions plain = *so;
+          for (auto& c : plain.ValueSetChunks) {
+            if (!SameTemporal(lg[0], c->logical))
+              return Status::Make(StatusCode::TypeError, "is_in: the value set (" + Describe(c->logical, Datum::Of(c)) + ") is not of the column's type " + lg[0]);
+            c = std::make_shared<ArrayData>(*c);
+            c->logical.clear();
+          }
+          return CallFunction(ctx, name, &plain, bare, out);
+        }
         if (!so || !so->ValueSet || !SameTemporal(lg[0], so->ValueSet->logical))
           return Status::Make(StatusCode::TypeError, "is_in: the value set (" + (so && so->ValueSet ? Describe(so->ValueSet->logical, Datum::Of(so->ValueSet)) : "none") + ") is not of the column's type " + lg[0]);
         SetOptions plain = *so;

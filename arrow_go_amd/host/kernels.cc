@@ -1176,42 +1176,142 @@ void RegisterScalarCast(FunctionRegistry* reg) {
 }
 
 // ---- is_in -------------------------------------------------------------------------------------------
-// initSetLookup + execIsIn (compute/scalar_set_lookup.go:67-172): the value set is SAFE-cast to the
-// input type when the types differ; the kernel writes data and validity (NullComputedPrealloc)
+static std::string SetTypeText(const DataType* t) {
+  return IsFixedWidthBinary(t->id) ? std::string(t->name) + "<" + t->format + ">" : std::string(t->name);
+}
+static bool IsUtf8(Type id) { return id == Type::STRING || id == Type::LARGE_STRING; }
+
+// initSetLookup (compute/scalar_set_lookup.go:67-135): the value set as pieces in the input's layout.  Numeric inputs: a value set
+// of another type is SAFE-cast to the input type, piece by piece.  Byte-string inputs take their own type, String ↔ LargeString and
+// Binary ↔ LargeBinary (the offset width differs, the bytes compare the same); the mixes the reference would cast and this layer has
+// no cast for (String ↔ Binary: UTF-8 validation; decimals of another precision or scale: a rescale; FixedSizeBinary of another
+// width) are refused with NotImplemented — DESIGN.md "Reference quirks — decisions".
+static Status IsInValueSet(Session* s, const SetOptions* opts, const DataType* in_type, std::vector<ArrayDataPtr>* parts) {
+  const DataType* vt = nullptr;
+  if (opts->ValueSet) { *parts = {opts->ValueSet}; vt = opts->ValueSet->type; }
+  else if (opts->ValueSetChunkedType) { *parts = opts->ValueSetChunks; vt = opts->ValueSetChunkedType; }
+  else return Status::Make(StatusCode::Invalid, "expected array-like datum, got nil");
+  const Type iid = in_type->id, vid = vt->id;
+  auto mismatch = [&]() {
+    return Status::Make(StatusCode::Invalid, "array type doesn't match type of values set: " + SetTypeText(in_type) + " vs " + SetTypeText(vt));
+  };
+  if (IsUtf8(iid) && !IsBaseBinary(vid)) return mismatch();  // :87-93: no implicit cast from a non-binary type to string
+  if (vt == in_type) return Status::OK();                    // interned types: the same pointer ⇔ arrow.TypeEqual
+  if (IsBaseBinary(iid) || IsFixedWidthBinary(iid)) {
+    const bool both_binary = IsBaseBinary(iid) && IsBaseBinary(vid), both_fixed = IsFixedWidthBinary(iid) && IsFixedWidthBinary(vid);
+    const bool both_decimal = both_fixed && iid != Type::FIXED_SIZE_BINARY && vid != Type::FIXED_SIZE_BINARY;
+    if (both_binary && IsUtf8(iid) == IsUtf8(vid)) return Status::OK();
+    if (both_binary || (both_fixed && (iid == vid || both_decimal)))
+      return Status::Make(StatusCode::NotImplemented, "is_in: a " + SetTypeText(in_type) + " column with a " + SetTypeText(vt) +
+                                                          " value set needs a cast this layer does not have");
+    return mismatch();
+  }
+  if (IsBaseBinary(vid) || IsFixedWidthBinary(vid)) return mismatch();
+  ExecCtx ectx;
+  ectx.session = s;
+  for (auto& pc : *parts) {
+    if (pc->type == in_type) continue;
+    Datum casted;
+    Status st = CastDatum(&ectx, Datum::Of(pc), CastOptions::Safe(in_type), &casted);
+    if (!st.ok()) return st.code == StatusCode::NotImplemented ? mismatch() : st;
+    pc = casted.array;
+  }
+  return Status::OK();
+}
+
+static Status ExecIsInDictionary(Session* s, const SetOptions* opts, const ArraySpan& in, ExecResult* out);
+
+// execIsIn (compute/scalar_set_lookup.go:137-172) → DispatchIsIn: the kernel writes data and validity (NullComputedPrealloc)
 static Status ExecIsIn(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
   Session* s = k->session;
   const SetOptions* opts = dynamic_cast<const SetOptions*>(static_cast<const FunctionOptions*>(k->state));
   if (!opts) return Status::Make(StatusCode::Invalid, "calling a set lookup function without SetOptions");
-  if (!opts->ValueSet) return Status::Make(StatusCode::Invalid, "expected array-like datum, got nil");
   const ArraySpan& in = b.values[0].array;
-  ArrayDataPtr vset = opts->ValueSet;
-  if (vset->type->id != in.type->id) {
-    ExecCtx ectx;
-    ectx.session = s;
-    Datum casted;
-    Status st = CastDatum(&ectx, Datum::Of(vset), CastOptions::Safe(in.type), &casted);
-    if (!st.ok()) {
-      if (st.code == StatusCode::NotImplemented)
-        return Status::Make(StatusCode::Invalid, std::string("array type doesn't match type of values set: ") + in.type->name + " vs " + vset->type->name);
-      return st;
-    }
-    vset = casted.array;
-  }
+  if (in.type->id == Type::DICTIONARY) return ExecIsInDictionary(s, opts, in, out);
+  std::vector<ArrayDataPtr> parts;
+  AHC_RETURN_NOT_OK(IsInValueSet(s, opts, in.type, &parts));
   if (out->len == 0) return Status::OK();
-  int w = in.type->bit_width / 8;
-  const uint8_t* set_vals = vset->length ? (const uint8_t*)vset->buffers[1]->dptr + vset->offset * w : nullptr;
-  const uint8_t* set_valid = vset->buffers[0] ? (const uint8_t*)vset->buffers[0]->dptr : nullptr;
-  AHC_RETURN_NOT_OK(s->FromStatus(ah_is_in(s->ctx(), w, Values(in), in.MayHaveNulls() ? in.buffers[0].buf : nullptr, in.offset, in.len, set_vals,
-                                           set_valid, vset->offset, vset->length, opts->NullBehavior, out->buffers[1].buf, out->buffers[0].buf,
-                                           out->offset)));
+  const uint8_t* valid = in.MayHaveNulls() ? in.buffers[0].buf : nullptr;
+  const Type id = in.type->id;
+  if ((IsInteger(id) || IsFloating(id)) && opts->ValueSet) {  // one array: ah_is_in as before
+    const ArrayDataPtr& vset = parts[0];
+    const int w = in.type->bit_width / 8;
+    const uint8_t* set_vals = vset->length ? (const uint8_t*)vset->buffers[1]->dptr + vset->offset * w : nullptr;
+    const uint8_t* set_valid = vset->buffers[0] ? (const uint8_t*)vset->buffers[0]->dptr : nullptr;
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_is_in(s->ctx(), w, Values(in), valid, in.offset, in.len, set_vals, set_valid, vset->offset, vset->length,
+                                             opts->NullBehavior, out->buffers[1].buf, out->buffers[0].buf, out->offset)));
+    out->nulls = kUnknownNullCount;
+    return Status::OK();
+  }
+  std::vector<ah_set_chunk> set;
+  for (auto& pc : parts) {
+    ah_set_chunk c{};
+    auto dptr = [&](int i) -> const void* { return pc->buffers[i] ? pc->buffers[i]->dptr : nullptr; };
+    c.valid = pc->null_count != 0 ? (const uint8_t*)dptr(0) : nullptr;
+    c.off = pc->offset;
+    c.n = pc->length;
+    if (IsBaseBinary(pc->type->id)) {
+      c.offset_width = pc->type->bit_width / 8;
+      c.offsets = dptr(1);
+      c.data = (const uint8_t*)dptr(2);
+    } else {
+      c.data = (const uint8_t*)dptr(1);
+    }
+    set.push_back(c);
+  }
+  int rc;
+  if (IsBaseBinary(id))
+    rc = ah_is_in_binary(s->ctx(), in.type->bit_width / 8, in.buffers[1].buf, in.buffers[2].buf, valid, in.offset, in.len, (int)set.size(), set.data(),
+                         opts->NullBehavior, out->buffers[1].buf, out->buffers[0].buf, out->offset);
+  else
+    rc = ah_is_in_fixed(s->ctx(), in.type->bit_width / 8, in.buffers[1].buf, valid, in.offset, in.len, (int)set.size(), set.data(), opts->NullBehavior,
+                        out->buffers[1].buf, out->buffers[0].buf, out->offset);
+  AHC_RETURN_NOT_OK(s->FromStatus(rc));
   out->nulls = kUnknownNullCount;
   return Status::OK();
 }
 
-// RegisterScalarSetLookup (compute/scalar_set_lookup.go:175-232), fixed-width numeric inputs
+// setLookupFunc.DispatchBest decodes a dictionary input first (ensureDictionaryDecoded, compute/scalar_set_lookup.go:37-61).  Here
+// the column stays encoded: is_in runs over the dictionary's entries plus one null value behind them (a short array), and every
+// row takes the bit of its index — a null index the bit of the null value.  Same data and validity as decode-then-is_in.
+static Status ExecIsInDictionary(Session* s, const SetOptions* opts, const ArraySpan& in, ExecResult* out) {
+  const ArrayDataPtr& dict = in.dictionary;
+  if (!dict) return Status::Make(StatusCode::Invalid, "is_in: dictionary array without a dictionary");
+  const DataType* vt = dict->type;
+  auto null1 = std::make_shared<ArrayData>();
+  null1->type = vt;
+  null1->length = 1;
+  null1->null_count = 1;
+  null1->logical = dict->logical;
+  AHC_RETURN_NOT_OK(s->AllocateBitmap(1, &null1->buffers[0]));
+  AHC_RETURN_NOT_OK(s->Allocate(IsBaseBinary(vt->id) ? 2 * (vt->bit_width / 8) : std::max(1, vt->bit_width / 8), &null1->buffers[1]));  // zeroed
+  if (IsBaseBinary(vt->id)) AHC_RETURN_NOT_OK(s->Allocate(8, &null1->buffers[2]));
+  ArrayDataPtr entries;
+  AHC_RETURN_NOT_OK(Concatenate(s, {dict, null1}, vt, &entries));
+  ExecCtx ectx;
+  ectx.session = s;
+  Datum lut;
+  AHC_RETURN_NOT_OK(CallFunction(&ectx, "is_in", opts, {Datum::Of(entries)}, &lut));
+  if (out->len == 0) return Status::OK();
+  const ArrayData& l = *lut.array;
+  if (l.offset != 0 || !l.buffers[0] || !l.buffers[1]) return Status::Make(StatusCode::Invalid, "is_in: unexpected layout of the dictionary's result");
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_is_in_dict_gather(s->ctx(), in.type->bit_width / 8, in.buffers[1].buf, in.MayHaveNulls() ? in.buffers[0].buf : nullptr,
+                                                       in.offset, in.len, (const uint8_t*)l.buffers[1]->dptr, (const uint8_t*)l.buffers[0]->dptr,
+                                                       dict->length, out->buffers[1].buf, out->buffers[0].buf, out->offset)));
+  out->nulls = kUnknownNullCount;
+  return Status::OK();
+}
+
+// RegisterScalarSetLookup (compute/scalar_set_lookup.go:175-232): fixed-width numeric inputs, String / Binary / LargeString /
+// LargeBinary, FixedSizeBinary, Decimal128 / Decimal256, and dictionary inputs of any of them (setLookupFunc.DispatchBest).
+// Boolean stays unregistered.
 void RegisterScalarSetLookup(FunctionRegistry* reg) {
   auto fn = std::make_shared<ScalarFunction>("is_in", Arity{1, false});
-  for (Type t : kNumericTypes) {
+  std::vector<Type> types(std::begin(kNumericTypes), std::end(kNumericTypes));
+  for (Type t : {Type::STRING, Type::BINARY, Type::LARGE_STRING, Type::LARGE_BINARY, Type::FIXED_SIZE_BINARY, Type::DECIMAL128, Type::DECIMAL256,
+                 Type::DICTIONARY})
+    types.push_back(t);
+  for (Type t : types) {
     exec::ScalarKernel k;
     k.sig.in_types = {t};
     k.sig.out_is_first_input = false;

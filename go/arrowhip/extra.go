@@ -297,3 +297,56 @@ func (i *Ingest) SlotDownload(slot, which int, srcOffset int, host []byte) error
 }
 
 func (i *Ingest) Wait() error { return i.ctx.err(C.ah_ingest_wait(i.g)) }
+
+// SetPiece is one piece of an is_in value set (ah_set_chunk): a plain array is one piece, a chunked value set one piece per
+// chunk.  Base-binary pieces: OffsetWidth 4 or 8, Offsets the offsets buffer, Data the value bytes.  Fixed-width pieces:
+// OffsetWidth 0, Data the slots.  Row i of the piece is element Off + i of every buffer and bit Off + i of Valid.
+type SetPiece struct {
+	OffsetWidth int
+	Offsets     unsafe.Pointer
+	Data        unsafe.Pointer
+	Valid       unsafe.Pointer
+	Off, N      int64
+}
+
+func setPieces(set []SetPiece) (unsafe.Pointer, func()) {
+	if len(set) == 0 {
+		return nil, func() {}
+	}
+	var one C.ah_set_chunk
+	tbl := C.malloc(C.size_t(len(set)) * C.size_t(unsafe.Sizeof(one)))
+	ps := unsafe.Slice((*C.ah_set_chunk)(tbl), len(set))
+	for i, p := range set {
+		ps[i].offset_width, ps[i].offsets, ps[i].data = C.int(p.OffsetWidth), p.Offsets, (*C.uint8_t)(p.Data)
+		ps[i].valid, ps[i].off, ps[i].n = (*C.uint8_t)(p.Valid), C.int64_t(p.Off), C.int64_t(p.N)
+	}
+	return tbl, func() { C.free(tbl) }
+}
+
+// IsInBinary mirrors SetLookupState[[]byte] + isInKernelExec for String / Binary / LargeString / LargeBinary rows
+// (kernels/scalar_set_lookup.go:192-244, 270-300, 374-413): bytewise membership, every piece of the value set in one table.
+func (x *Context) IsInBinary(offsetWidth int, offsets, data, valid unsafe.Pointer, off, n int64, set []SetPiece, nullBehavior int,
+	outData, outValid unsafe.Pointer, outBitOffset int64) error {
+	tbl, free := setPieces(set)
+	defer free()
+	return x.err(C.ah_is_in_binary(x.c, C.int(offsetWidth), offsets, (*C.uint8_t)(data), (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n),
+		C.int(len(set)), (*C.ah_set_chunk)(tbl), C.int(nullBehavior), (*C.uint8_t)(outData), (*C.uint8_t)(outValid), C.int64_t(outBitOffset)))
+}
+
+// IsInFixed mirrors is_in of fixed-width rows — FixedSizeBinary, Decimal128 / Decimal256 and the numeric types
+// (visitBinary / visitNumeric, kernels/scalar_set_lookup.go:106-133, 270-300): raw-byte membership.
+func (x *Context) IsInFixed(byteWidth int, data, valid unsafe.Pointer, off, n int64, set []SetPiece, nullBehavior int,
+	outData, outValid unsafe.Pointer, outBitOffset int64) error {
+	tbl, free := setPieces(set)
+	defer free()
+	return x.err(C.ah_is_in_fixed(x.c, C.int(byteWidth), (*C.uint8_t)(data), (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), C.int(len(set)),
+		(*C.ah_set_chunk)(tbl), C.int(nullBehavior), (*C.uint8_t)(outData), (*C.uint8_t)(outValid), C.int64_t(outBitOffset)))
+}
+
+// IsInDictGather finishes is_in of a dictionary column (ensureDictionaryDecoded + execIsIn, compute/scalar_set_lookup.go:56-61)
+// without decoding it: bits 0 … lutN − 1 of lutData / lutValid are is_in of the dictionary's entries, bit lutN that of a null.
+func (x *Context) IsInDictGather(indexWidth int, indices, valid unsafe.Pointer, off, n int64, lutData, lutValid unsafe.Pointer, lutN int64,
+	outData, outValid unsafe.Pointer, outBitOffset int64) error {
+	return x.err(C.ah_is_in_dict_gather(x.c, C.int(indexWidth), indices, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), (*C.uint8_t)(lutData),
+		(*C.uint8_t)(lutValid), C.int64_t(lutN), (*C.uint8_t)(outData), (*C.uint8_t)(outValid), C.int64_t(outBitOffset)))
+}

@@ -599,6 +599,42 @@ int ah_cast_bool_to_numeric(ah_ctx* ctx, int out_type, const uint8_t* bits, int6
 int ah_is_in(ah_ctx* ctx, int byte_width, const void* values, const uint8_t* valid, int64_t off, int64_t n,
              const void* set_values, const uint8_t* set_valid, int64_t set_off, int64_t set_n, int null_behavior,
              uint8_t* out_data, uint8_t* out_valid, int64_t out_bit_offset);
+/* One piece of a value set for ah_is_in_binary / ah_is_in_fixed (a plain array is one piece; a chunked value set, one piece per
+ * chunk: SetLookupOptions.ValueSet, kernels/scalar_set_lookup.go:40-45, filled per chunk by initSetLookup, compute/
+ * scalar_set_lookup.go:118-131).  Row i of the piece is element off + i of `offsets` / `data` and bit off + i of `valid`
+ * (nullable).  Base-binary pieces: offset_width 4 or 8, `offsets` the offsets buffer, `data` the value bytes.  Fixed-width
+ * pieces: offset_width 0, `offsets` unused, `data` the slots (byte_width each).  The table of pieces is HOST memory. */
+typedef struct ah_set_chunk {
+  int offset_width;
+  const void* offsets;
+  const uint8_t* data;
+  const uint8_t* valid;
+  int64_t off, n;
+} ah_set_chunk;
+/* is_in of String / Binary / LargeString / LargeBinary rows (SetLookupState[[]byte].Init + visitBinary + isInKernelExec,
+ * kernels/scalar_set_lookup.go:192-244, 270-300, 374-413, behind compute's "is_in", compute/scalar_set_lookup.go:207-214):
+ * values compare bytewise, so "" is a value.  Row i of the input is offsets[off + i] … offsets[off + i + 1] (offset_width 4
+ * or 8) of `data`, validity bit off + i.  Every piece of the value set is inserted into ONE table (pieces may have either
+ * offset width: String ↔ LargeString and Binary ↔ LargeBinary compare as bytes).  Null behaviours and the output contract
+ * as ah_is_in.  No host synchronisation. */
+int ah_is_in_binary(ah_ctx* ctx, int offset_width, const void* offsets, const uint8_t* data, const uint8_t* valid, int64_t off, int64_t n,
+                    int set_nchunks, const ah_set_chunk* set, int null_behavior, uint8_t* out_data, uint8_t* out_valid,
+                    int64_t out_bit_offset);
+/* is_in of fixed-width rows of byte_width bytes — FixedSizeBinary, Decimal128 (16), Decimal256 (32) and every numeric type
+ * (visitBinary / visitNumeric, kernels/scalar_set_lookup.go:106-133, 270-300): raw bytes compare.  Widths 1, 2, 4 and 8 take
+ * ah_is_in's kernels (the reference's FixedSizeBinary fast path, SetLookupState[uintN]); other widths the byte-string table of
+ * ah_is_in_binary.  Row i of the input is data + (off + i)·byte_width, validity bit off + i; value-set pieces have
+ * offset_width 0 and the same byte_width.  Null behaviours and output as ah_is_in.  No host synchronisation. */
+int ah_is_in_fixed(ah_ctx* ctx, int byte_width, const uint8_t* data, const uint8_t* valid, int64_t off, int64_t n, int set_nchunks,
+                   const ah_set_chunk* set, int null_behavior, uint8_t* out_data, uint8_t* out_valid, int64_t out_bit_offset);
+/* is_in of a dictionary array from is_in of its dictionary (what ensureDictionaryDecoded + execIsIn compute, compute/
+ * scalar_set_lookup.go:56-61, without decoding the column): lut_data / lut_valid (bits 0 … lut_n − 1) hold is_in of the
+ * dictionary's entries, bit lut_n the result for a NULL value.  Row i (index_width 1, 2, 4 or 8, signed; element off + i of
+ * `indices`, validity bit off + i) gets bit indices[off + i] of the table, a null index gets bit lut_n; an index outside
+ * [0, lut_n) gives a null row.  Writes data and validity bits [out_bit_offset, out_bit_offset + n).  No host synchronisation. */
+int ah_is_in_dict_gather(ah_ctx* ctx, int index_width, const void* indices, const uint8_t* valid, int64_t off, int64_t n,
+                         const uint8_t* lut_data, const uint8_t* lut_valid, int64_t lut_n, uint8_t* out_data, uint8_t* out_valid,
+                         int64_t out_bit_offset);
 
 /* ---- sort_indices (row §8(f)-2) ----------------------------------------------------------------
  * replaces kernels.SortIndices for one key over one array (kernels/vector_sort.go:388-481 →
