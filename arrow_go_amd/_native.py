@@ -146,6 +146,8 @@ _SIGS = {
     "ah_is_in_binary": [_vp, _int, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _vp, _vp, _i64],
     "ah_is_in_fixed": [_vp, _int, _vp, _vp, _i64, _i64, _int, _vp, _int, _vp, _vp, _i64],
     "ah_is_in_dict_gather": [_vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64],
+    "ah_compare_binary": [_vp, _int, _vp, _vp, _i64, _vp, _i64],
+    "ah_compare_decimal": [_vp, _int, _int, _vp, _i64, _int, _int, _int, _vp, _i64, _int, _int, _i64, _vp, _i64],
     "ah_sort_indices": [_vp, _int, _vp, _vp, _i64, _i64, _int, _int, _vp],
     "ah_wait_event": [_vp, _vp],
     "ah_device_id": [_vp],

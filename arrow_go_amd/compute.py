@@ -63,6 +63,7 @@ lib.ahc_ipc_field.argtypes = [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c
 lib.ahc_ipc_next.argtypes = [_vp, C.POINTER(_vp), C.POINTER(C.c_int64)]
 lib.ahc_datum_logical.argtypes = [_vp]
 lib.ahc_datum_logical.restype = C.c_char_p
+lib.ahc_scalar_bytes.argtypes = [_vp, C.c_char_p, C.c_int, C.c_char_p, C.c_int64, C.POINTER(_vp)]
 lib.ahc_scalar_set_logical.argtypes = [_vp, _vp, C.c_char_p]
 lib.ahc_ipc_bytes_uploaded.argtypes = [_vp]
 lib.ahc_ipc_bytes_uploaded.restype = C.c_int64
@@ -202,6 +203,21 @@ def _temporal_format(t):
         return "tdm"
     if pa.types.is_time32(t) or pa.types.is_time64(t):
         return "tt" + short[t.unit]
+    return None
+
+
+def _bytes_format(t):
+    """the Arrow C Data format of a byte-payload type (String, Binary, Large*, FixedSizeBinary, Decimal128 / 256), None otherwise"""
+    import pyarrow as pa
+    simple = {pa.string(): "u", pa.binary(): "z", pa.large_string(): "U", pa.large_binary(): "Z"}
+    if t in simple:
+        return simple[t]
+    if pa.types.is_fixed_size_binary(t):
+        return "w:%d" % t.byte_width
+    if pa.types.is_decimal128(t):
+        return "d:%d,%d" % (t.precision, t.scale)
+    if pa.types.is_decimal256(t):
+        return "d:%d,%d,256" % (t.precision, t.scale)
     return None
 
 
@@ -351,6 +367,20 @@ class Session:
 
     def _scalar(self, sc):
         import pyarrow as pa
+        fmt = _bytes_format(sc.type)
+        if fmt is not None:  # String / Binary / Large* / FixedSizeBinary / Decimal128 / Decimal256: ahc_scalar_bytes
+            raw = b""
+            if sc.is_valid:
+                if pa.types.is_fixed_size_binary(sc.type) or pa.types.is_decimal(sc.type):
+                    arr = pa.array([sc.as_py()], type=sc.type)
+                    w = sc.type.byte_width
+                    raw = arr.buffers()[1].to_pybytes()[arr.offset * w:(arr.offset + 1) * w]
+                else:
+                    v = sc.as_py()
+                    raw = v.encode() if isinstance(v, str) else bytes(v)
+            d = _vp()
+            self._check(lib.ahc_scalar_bytes(self.h, fmt.encode(), int(sc.is_valid), raw, len(raw), C.byref(d)))
+            return d
         logical = _temporal_format(sc.type)
         tid = _TYPE_IDS[("int32" if sc.type.bit_width == 32 else "int64") if logical else str(sc.type)]
         valid = sc.is_valid

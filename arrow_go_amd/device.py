@@ -248,6 +248,11 @@ class _SetChunk(C.Structure):  # ah_set_chunk (arrowhip.h)
                 ("n", C.c_int64)]
 
 
+class _CmpOperand(C.Structure):  # ah_cmp_operand (arrowhip.h)
+    _fields_ = [("offset_width", C.c_int), ("byte_width", C.c_int), ("offsets", C.c_void_p), ("data", C.c_void_p), ("off", C.c_int64),
+                ("broadcast", C.c_int)]
+
+
 class Context:
     """ah_ctx: one GPU, a compute stream and a copy stream."""
 
@@ -541,6 +546,20 @@ class Context:
                           out_bit_offset: int = 0) -> None:
         check(self.handle, lib.ah_is_in_dict_gather(self.handle, index_width, _ptr(indices), _ptr(valid), off, n, _ptr(lut_data), _ptr(lut_valid),
                                                      lut_n, _ptr(out_data), _ptr(out_valid), out_bit_offset))
+
+    def compare_binary(self, cmpop: int, left, right, n: int, out_bits, out_bit_offset: int = 0) -> None:
+        """left / right: (offset_width, byte_width, offsets, data, off, broadcast) — offset_width 4 / 8 for base-binary operands,
+        0 for fixed slots of byte_width bytes; broadcast 1 for a scalar (every row reads element off)."""
+        lo = _CmpOperand(left[0], left[1], _ptr(left[2]), _ptr(left[3]), left[4], left[5])
+        ro = _CmpOperand(right[0], right[1], _ptr(right[2]), _ptr(right[3]), right[4], right[5])
+        check(self.handle, lib.ah_compare_binary(self.handle, cmpop, C.byref(lo), C.byref(ro), n, _ptr(out_bits), out_bit_offset))
+
+    def compare_decimal(self, cmpop: int, left, right, n: int, out_bits, out_bit_offset: int = 0) -> None:
+        """left / right: (width 16 | 32, data, off, broadcast, scale-up exponent)"""
+        lw, ld, loff, lb, lk = left
+        rw, rd, roff, rb, rk = right
+        check(self.handle, lib.ah_compare_decimal(self.handle, cmpop, lw, _ptr(ld), loff, lb, lk, rw, _ptr(rd), roff, rb, rk, n, _ptr(out_bits),
+                                                  out_bit_offset))
 
     # ---- min / max ----------------------------------------------------------------------
     def min_max(self, type_id: int, values, n: int, dtype):

@@ -62,6 +62,7 @@ bool IsNumeric(Type id);
 // Temporal types by their C Data format: the integer type that stores them (nullptr: not a temporal format this layer takes)
 const DataType* TemporalStorage(const std::string& format);
 bool IsBaseBinary(Type id);  // String, Binary, LargeString, LargeBinary: buffers = [validity, offsets, data]
+inline bool IsDecimal(Type id) { return id == Type::DECIMAL128 || id == Type::DECIMAL256; }
 
 // ---- errors (arrow/errors.go) ---------------------------------------------------------
 enum class StatusCode { OK = 0, Invalid, Index, NotImplemented, TypeError, KeyError, Hip };
@@ -167,6 +168,9 @@ struct Scalar {
   bool valid = false;
   alignas(8) uint8_t value[8] = {0};  // little-endian payload of width type->bit_width (bool: value[0])
   std::string logical;                // as ArrayData::logical
+  // String / Binary / LargeString / LargeBinary / FixedSizeBinary / Decimal128 / Decimal256: the value's bytes (BinaryScalar.Data(),
+  // a decimal as its little-endian two's complement); `value` is unused.  Empty for a null scalar.
+  std::vector<uint8_t> bytes;
 };
 using ScalarPtr = std::shared_ptr<Scalar>;
 
@@ -236,6 +240,9 @@ struct ScalarKernel {  // kernel.go:632-672
   NullHandling null_handling = NullHandling::NullIntersection;  // defaults :660-661
   MemAlloc mem_alloc = MemAlloc::MemPrealloc;
   std::shared_ptr<void> data;
+  // the kernel reads its arguments in the types they arrive in: the executor inserts none of the implicit casts DispatchBest
+  // reported (the byte-string and decimal comparisons compare String ∘ LargeBinary or decimals of different scales directly)
+  bool consumes_uncast = false;
 };
 using FinalizeFn = std::function<Status(KernelCtx*, std::vector<ArraySpan>*)>;
 struct VectorKernel {  // kernel.go:686-727
@@ -343,6 +350,8 @@ struct Datum {
 // boolean data through the bit-offset bitmap copy, fixed-width values with one device copy per chunk,
 // var-length offsets rebased with the arr∘scalar Add kernel.  A single chunk is returned as is.
 Status Concatenate(Session* s, const std::vector<ArrayDataPtr>& chunks, const DataType* type, ArrayDataPtr* out);
+// a scalar as a length-1 device array (the executor's all-scalar path; byte-payload scalars get offsets [0, len] + data)
+Status ScalarToArray(Session* s, const Scalar& sc, ArrayDataPtr* out);
 // array.NewSliceData: zero-copy view
 ArrayDataPtr SliceData(const ArrayDataPtr& a, int64_t off, int64_t len);
 
@@ -412,6 +421,9 @@ class ScalarFunction : public Function {  // functions.go:239-290
   // commonNumeric (utils.go:178-240) and implicitly SAFE-cast (exec.go:105-114)
   bool promote_numeric = false;
   bool promote_to_float = false;  // unary floating-point functions: integer arguments are cast to float64
+  // compareFunction.DispatchBest's other two steps (scalar_compare.go:37-63): castBinaryDecimalArgs(decPromoteAdd) when an
+  // argument is a decimal (utils.go:261-326) and commonBinary (utils.go:401-436) when no numeric type is common
+  bool promote_binary_decimal = false;
   Status DispatchBest(std::vector<const DataType*>* types, const exec::ScalarKernel** out) const;
  private:
   std::vector<exec::ScalarKernel> kernels_;
@@ -479,6 +491,10 @@ void RegisterScalarCast(FunctionRegistry* reg);
 void RegisterScalarSetLookup(FunctionRegistry* reg);
 void RegisterVectorSort(FunctionRegistry* reg);
 const DataType* CommonNumeric(const std::vector<const DataType*>& types);  // utils.go:178-240; nullptr if none
+const DataType* CommonBinary(const std::vector<const DataType*>& types);   // utils.go:401-436; nullptr if none
+Status CastBinaryDecimalArgs(std::vector<const DataType*>* types);         // utils.go:261-326, decPromoteAdd
+bool DecimalParams(const DataType* t, int* precision, int* scale);          // false: not a decimal
+int MaxDecimalDigitsForInt(Type id);                                        // kernels/helpers.go:705-719; −1: not an integer
 // compute.CastDatum / CastArray (cast.go:917-935)
 Status CastDatum(ExecCtx* ctx, const Datum& in, const CastOptions& opts, Datum* out);
 void RegisterVectorSelection(FunctionRegistry* reg);

@@ -259,6 +259,25 @@ AHC_EXPORT int ahc_scalar(ahc_session* s, int type_id, int valid, const void* va
   return 0;
 }
 
+// BinaryScalar / FixedSizeBinaryScalar / Decimal128Scalar / Decimal256Scalar (arrow/scalar/binary.go, scalar.go): the type by
+// its C Data format, the value's bytes (a decimal: its little-endian two's complement, 16 or 32 bytes)
+AHC_EXPORT int ahc_scalar_bytes(ahc_session* s, const char* format, int valid, const void* data, int64_t len, ahc_datum** out) {
+  *out = nullptr;
+  const DataType* t = TypeFromFormat(format);
+  if (!t || (!IsBaseBinary(t->id) && !IsFixedWidthBinary(t->id)))
+    return Fail(s, Status::Make(StatusCode::NotImplemented, std::string("unsupported byte-payload scalar format '") + (format ? format : "") + "'"));
+  if (len < 0 || (valid && len > 0 && !data)) return Fail(s, Status::Make(StatusCode::Invalid, "scalar bytes: bad length or null data"));
+  if (valid && IsFixedWidthBinary(t->id) && len != t->bit_width / 8)
+    return Fail(s, Status::Make(StatusCode::Invalid, std::string("scalar bytes: ") + format + " takes " + std::to_string(t->bit_width / 8) +
+                                                          " bytes, got " + std::to_string(len)));
+  auto sc = std::make_shared<Scalar>();
+  sc->type = t;
+  sc->valid = valid != 0;
+  if (sc->valid && len > 0) sc->bytes.assign((const uint8_t*)data, (const uint8_t*)data + len);
+  *out = new ahc_datum{Datum::Of(sc)};
+  return 0;
+}
+
 // the temporal label of a datum ("" for a plain one), and setting it on a scalar built with ahc_scalar
 AHC_EXPORT const char* ahc_datum_logical(ahc_datum* d) {
   static thread_local std::string keep;

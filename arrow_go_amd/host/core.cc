@@ -354,11 +354,32 @@ static Status PropagateNulls(Session* s, const exec::ExecSpan& batch, exec::Arra
 // all-scalar calls: arrow-go promotes scalars to length-1 arrays and unboxes the result
 // (executor.go:462-496 execute → haveAllScalars; exec.go:172 WrapResults).  Here: upload 1
 // element, run the same array kernel, download 1 element.
-static Status ScalarToArray(Session* s, const Scalar& sc, ArrayDataPtr* out) {
+Status ScalarToArray(Session* s, const Scalar& sc, ArrayDataPtr* out) {
   auto d = std::make_shared<ArrayData>();
   d->type = sc.type;
   d->length = 1;
   d->null_count = sc.valid ? 0 : 1;
+  if (IsBaseBinary(sc.type->id) || IsFixedWidthBinary(sc.type->id)) {  // byte payload: a null scalar holds empty bytes / zeros
+    const int64_t len = sc.valid ? (int64_t)sc.bytes.size() : 0;
+    if (IsBaseBinary(sc.type->id)) {
+      const int ow = sc.type->bit_width / 8;
+      uint8_t offs[16] = {0};
+      if (ow == 4) { const int32_t e = (int32_t)len; memcpy(offs + 4, &e, 4); }
+      else memcpy(offs + 8, &len, 8);
+      AHC_RETURN_NOT_OK(s->Allocate(2 * ow, &d->buffers[1]));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_upload_async(s->ctx(), d->buffers[1]->dptr, offs, (size_t)(2 * ow))));
+      AHC_RETURN_NOT_OK(s->Allocate(std::max<int64_t>(len, 1), &d->buffers[2]));
+      if (len) AHC_RETURN_NOT_OK(s->FromStatus(ah_upload_async(s->ctx(), d->buffers[2]->dptr, sc.bytes.data(), (size_t)len)));
+    } else {
+      const int64_t w = sc.type->bit_width / 8;
+      AHC_RETURN_NOT_OK(s->Allocate(std::max<int64_t>(w, 1), &d->buffers[1]));  // zeroed
+      if (len == w && w > 0) AHC_RETURN_NOT_OK(s->FromStatus(ah_upload_async(s->ctx(), d->buffers[1]->dptr, sc.bytes.data(), (size_t)w)));
+    }
+    if (!sc.valid) AHC_RETURN_NOT_OK(s->AllocateBitmap(1, &d->buffers[0]));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_sync(s->ctx())));  // the host bytes may go as soon as this returns
+    *out = d;
+    return Status::OK();
+  }
   AHC_RETURN_NOT_OK(s->Allocate(8, &d->buffers[1]));
   AHC_RETURN_NOT_OK(s->FromStatus(ah_upload_async(s->ctx(), d->buffers[1]->dptr, sc.value, 8)));
   if (!sc.valid) AHC_RETURN_NOT_OK(s->AllocateBitmap(1, &d->buffers[0]));  // zero = null
@@ -396,7 +417,7 @@ Status ScalarFunction::Execute(ExecCtx* ctx, const FunctionOptions* opts, const 
   const exec::ScalarKernel* kernel = nullptr;
   AHC_RETURN_NOT_OK(DispatchBest(&types, &kernel));
   // cast arguments if necessary (execInternal, exec.go:105-114): implicit casts are SAFE casts
-  for (size_t i = 0; i < args.size(); i++) {
+  for (size_t i = 0; i < args.size() && !kernel->consumes_uncast; i++) {
     if (args[i].type()->id == types[i]->id) continue;
     Datum casted;
     AHC_RETURN_NOT_OK(CastDatum(ctx, args[i], CastOptions::Safe(types[i]), &casted));
@@ -543,6 +564,8 @@ Status ScalarFunction::DispatchBest(std::vector<const DataType*>* types, const e
     (*types)[1] = sw[0];
     return fs;
   }
+  if (promote_binary_decimal && types->size() == 2 && (IsDecimal((*types)[0]->id) || IsDecimal((*types)[1]->id)))
+    AHC_RETURN_NOT_OK(CastBinaryDecimalArgs(types));
   Status st = DispatchExact(*types, out);
   if (!st.ok() && promote_to_float && types->size() == 1 && IsInteger((*types)[0]->id)) {
     std::vector<const DataType*> promoted{GetDataType(Type::FLOAT64)};
@@ -555,7 +578,77 @@ Status ScalarFunction::DispatchBest(std::vector<const DataType*>* types, const e
     Status st2 = DispatchExact(promoted, out);
     if (st2.ok()) { *types = promoted; return st2; }
   }
+  if (promote_binary_decimal)
+    if (const DataType* common = CommonBinary(*types)) {
+      std::vector<const DataType*> promoted(types->size(), common);
+      Status st2 = DispatchExact(promoted, out);
+      if (st2.ok()) { *types = promoted; return st2; }
+    }
   return st;
+}
+
+// commonBinary (compute/utils.go:401-436): nullptr when an argument is not binary-like or when all are FixedSizeBinary (compared
+// as they are, whatever their widths)
+const DataType* CommonBinary(const std::vector<const DataType*>& types) {
+  bool all_utf8 = true, all_offset32 = true, all_fixed = true;
+  for (auto* t : types) {
+    switch (t->id) {
+      case Type::STRING: all_fixed = false; break;
+      case Type::BINARY: all_fixed = all_utf8 = false; break;
+      case Type::FIXED_SIZE_BINARY: all_utf8 = false; break;
+      case Type::LARGE_BINARY: all_offset32 = all_fixed = all_utf8 = false; break;
+      case Type::LARGE_STRING: all_offset32 = all_fixed = false; break;
+      default: return nullptr;
+    }
+  }
+  if (all_fixed) return nullptr;
+  if (all_utf8) return GetDataType(all_offset32 ? Type::STRING : Type::LARGE_STRING);
+  return GetDataType(all_offset32 ? Type::BINARY : Type::LARGE_BINARY);
+}
+
+bool DecimalParams(const DataType* t, int* precision, int* scale) {
+  if (t->id != Type::DECIMAL128 && t->id != Type::DECIMAL256) return false;
+  return sscanf(t->format, "d:%d,%d", precision, scale) == 2;
+}
+
+// MaxDecimalDigitsForInt (kernels/helpers.go:705-719): −1 for a non-integer
+int MaxDecimalDigitsForInt(Type id) {
+  switch (id) {
+    case Type::INT8: case Type::UINT8: return 3;
+    case Type::INT16: case Type::UINT16: return 5;
+    case Type::INT32: case Type::UINT32: return 10;
+    case Type::INT64: return 19;
+    case Type::UINT64: return 20;
+    default: return -1;
+  }
+}
+
+// castBinaryDecimalArgs(decPromoteAdd) (compute/utils.go:261-326): decimal ∘ float → the float type on both sides; decimal ∘
+// integer → the integer as a decimal of MaxDecimalDigitsForInt digits; both rescaled to the larger scale, precision growing by
+// the same amount; Decimal128 ∘ Decimal256 → Decimal256.  A promoted precision beyond 38 / 76 is refused the way Arrow C++
+// refuses it (DecimalType::Make: "Decimal precision out of range [1, 38]: 48"; the reference only debug-asserts) — DESIGN.md §4
+// quirk 10.  An argument of another kind leaves the types alone (DispatchExact then reports no matching kernel).
+Status CastBinaryDecimalArgs(std::vector<const DataType*>* types) {
+  const DataType *l = (*types)[0], *r = (*types)[1];
+  if (IsFloating(l->id)) { (*types)[1] = l; return Status::OK(); }
+  if (IsFloating(r->id)) { (*types)[0] = r; return Status::OK(); }
+  int p[2], sc[2] = {0, 0};
+  for (int i = 0; i < 2; i++) {
+    const DataType* t = (*types)[i];
+    if (DecimalParams(t, &p[i], &sc[i])) continue;
+    if ((p[i] = MaxDecimalDigitsForInt(t->id)) < 0) return Status::OK();
+  }
+  if (sc[0] < 0 || sc[1] < 0) return Status::Make(StatusCode::NotImplemented, "decimals with negative scales not supported");
+  const bool wide = l->id == Type::DECIMAL256 || r->id == Type::DECIMAL256;
+  const int max_p = wide ? 76 : 38, s = std::max(sc[0], sc[1]);
+  for (int i = 0; i < 2; i++) {
+    const int pp = p[i] + s - sc[i];
+    if (pp > max_p)
+      return Status::Make(StatusCode::Invalid, "Decimal precision out of range [1, " + std::to_string(max_p) + "]: " + std::to_string(pp));
+    const std::string f = "d:" + std::to_string(pp) + "," + std::to_string(s) + (wide ? ",256" : "");
+    (*types)[i] = FixedWidthBinaryFromFormat(f);
+  }
+  return Status::OK();
 }
 
 Status CastDatum(ExecCtx* ctx, const Datum& in, const CastOptions& opts, Datum* out) {

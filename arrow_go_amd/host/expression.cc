@@ -193,6 +193,13 @@ static bool HasTemporalLiteral(const Expression& e) {
   for (auto& a : e.args) if (a && HasTemporalLiteral(*a)) return true;
   return false;
 }
+static bool IsBytesType(const DataType* t) { return t && (IsBaseBinary(t->id) || IsFixedWidthBinary(t->id)); }
+// a String / Binary / FixedSizeBinary / decimal literal: the fused kernel carries 8-byte literals only
+static bool HasBytesLiteral(const Expression& e) {
+  if (e.kind == Expression::LITERAL) return e.literal.kind == DatumKind::Scalar && IsBytesType(e.literal.scalar->type);
+  for (auto& a : e.args) if (a && HasBytesLiteral(*a)) return true;
+  return false;
+}
 
 Status ExecuteScalarExpression(ExecCtx* ctx, const ExprPtr& expr, const ExecBatch& batch, Datum* out, bool fuse, bool* fused_out) {
   if (fused_out) *fused_out = false;
@@ -209,6 +216,10 @@ Status ExecuteScalarExpression(ExecCtx* ctx, const ExprPtr& expr, const ExecBatc
   for (auto& v : batch.values)
     if (v.kind == DatumKind::Array && !v.array->logical.empty()) fuse = false;
   if (fuse && HasTemporalLiteral(*expr)) fuse = false;
+  // byte-string and decimal operands likewise run node by node (their comparisons are not in the JIT's vocabulary)
+  for (auto& v : batch.values)
+    if (v.kind == DatumKind::Array && IsBytesType(v.array->type)) fuse = false;
+  if (fuse && HasBytesLiteral(*expr)) fuse = false;
   for (auto& v : batch.values)
     if (v.kind == DatumKind::Array && v.array->length != batch.len)
       return Status::Make(StatusCode::Invalid, "all columns of the batch must have the batch length");

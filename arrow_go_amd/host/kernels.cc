@@ -258,6 +258,105 @@ static Status ExecCompare(KernelCtx* k, const ExecSpan& b, ExecResult* out, int 
 
 static Status ExecBoolBinary(KernelCtx* k, const ExecSpan& b, ExecResult* out, int bitop);
 
+// ---- comparisons of byte strings and decimals ----------------------------------------------------------------------------
+// The kernels take their arguments uncast (ScalarKernel::consumes_uncast): the String ∘ Binary, LargeString ∘ FixedSizeBinary …
+// pairings commonBinary resolves, and decimals of different scales or widths, are compared as they arrive.  A scalar operand
+// becomes a length-1 device array read by every row (broadcast).
+
+static std::string DecimalText(const DataType* t) {
+  int p = 0, sc = 0;
+  return DecimalParams(t, &p, &sc) ? std::string(t->name) + "(" + std::to_string(p) + ", " + std::to_string(sc) + ")" : std::string(t->name);
+}
+
+// one side of the call as a device array (a scalar: uploaded) + whether it is broadcast
+static Status CompareSide(Session* s, const exec::ExecValue& v, ArrayDataPtr* keep, const void** b1, const void** b2, int64_t* off, int* bcast) {
+  if (v.IsScalar()) {
+    AHC_RETURN_NOT_OK(ScalarToArray(s, *v.scalar, keep));
+    *b1 = (*keep)->buffers[1] ? (*keep)->buffers[1]->dptr : nullptr;
+    *b2 = (*keep)->buffers[2] ? (*keep)->buffers[2]->dptr : nullptr;
+    *off = 0;
+    *bcast = 1;
+  } else {
+    *b1 = v.array.buffers[1].buf;
+    *b2 = v.array.buffers[2].buf;
+    *off = v.array.offset;
+    *bcast = 0;
+  }
+  return Status::OK();
+}
+
+// getBinaryCmp over NewVarBinaryIter / NewFSBIter (kernels/scalar_comparisons.go:520-540, 694-713).  NewFSBIter ignores the
+// span's offset (exec/utils.go:266-277); here the offset is honoured, as for every other layout — DESIGN.md §4 quirk 10.
+static Status ExecCompareBytes(KernelCtx* k, const ExecSpan& b, ExecResult* out, int cmpop) {
+  Session* s = k->session;
+  if (out->len == 0) return Status::OK();
+  ah_cmp_operand o[2];
+  ArrayDataPtr keep[2];
+  for (int i = 0; i < 2; i++) {
+    const exec::ExecValue& v = b.values[i];
+    const DataType* t = v.type();
+    const void *b1, *b2;
+    AHC_RETURN_NOT_OK(CompareSide(s, v, &keep[i], &b1, &b2, &o[i].off, &o[i].broadcast));
+    if (IsBaseBinary(t->id)) {
+      o[i].offset_width = t->bit_width / 8;
+      o[i].byte_width = 0;
+      o[i].offsets = b1;
+      o[i].data = (const uint8_t*)b2;
+    } else {
+      o[i].offset_width = 0;
+      o[i].byte_width = t->bit_width / 8;
+      o[i].offsets = nullptr;
+      o[i].data = (const uint8_t*)b1;
+    }
+  }
+  return s->FromStatus(ah_compare_binary(s->ctx(), cmpop, &o[0], &o[1], out->len, out->buffers[1].buf, out->offset));
+}
+
+// genDecimalCompareKernel (kernels/scalar_comparisons.go:370-392) after castBinaryDecimalArgs: each side is rescaled in the
+// kernel (value · 10^k, k = the larger scale − its scale), never cast.  An integer scalar becomes a decimal of scale 0 on the
+// host, exactly; an integer array would need an integer → decimal cast, which this layer does not have.
+static Status ExecCompareDecimal(KernelCtx* k, const ExecSpan& b, ExecResult* out, int cmpop) {
+  Session* s = k->session;
+  const DataType* t[2] = {b.values[0].type(), b.values[1].type()};
+  Scalar as_dec[2];
+  exec::ExecValue vals[2] = {b.values[0], b.values[1]};
+  int prec, sc[2] = {0, 0};  // an integer side has scale 0
+  for (int i = 0; i < 2; i++) {
+    if (DecimalParams(t[i], &prec, &sc[i])) continue;
+    const DataType* other = t[1 - i];
+    if (!IsInteger(t[i]->id) || !vals[i].IsScalar())
+      return Status::Make(StatusCode::NotImplemented, std::string("unsupported cast to ") + DecimalText(other) + " from " + t[i]->name);
+    const Scalar& in = *vals[i].scalar;
+    uint64_t u = 0;
+    memcpy(&u, in.value, 8);
+    const int bits = t[i]->bit_width;
+    if (bits < 64) {
+      u &= (1ull << bits) - 1;
+      if (IsSignedInteger(t[i]->id) && (u >> (bits - 1)) & 1) u |= ~0ull << bits;  // sign-extend
+    }
+    const bool neg = IsSignedInteger(t[i]->id) && (int64_t)u < 0;
+    as_dec[i].type = FixedWidthBinaryFromFormat("d:76,0,256");
+    as_dec[i].valid = in.valid;
+    as_dec[i].bytes.assign(32, neg ? 0xFF : 0x00);
+    memcpy(as_dec[i].bytes.data(), &u, 8);
+    vals[i].scalar = &as_dec[i];
+    t[i] = as_dec[i].type;
+  }
+  if (out->len == 0) return Status::OK();
+  const int target = std::max(sc[0], sc[1]);
+  const void* data[2];
+  int64_t off[2];
+  int bcast[2];
+  ArrayDataPtr keep[2];
+  for (int i = 0; i < 2; i++) {
+    const void* unused;
+    AHC_RETURN_NOT_OK(CompareSide(s, vals[i], &keep[i], &data[i], &unused, &off[i], &bcast[i]));
+  }
+  return s->FromStatus(ah_compare_decimal(s->ctx(), cmpop, t[0]->bit_width / 8, (const uint8_t*)data[0], off[0], bcast[0], target - sc[0],
+                                          t[1]->bit_width / 8, (const uint8_t*)data[1], off[1], bcast[1], target - sc[1], out->len,
+                                          out->buffers[1].buf, out->offset));
+}
+
 void RegisterScalarComparisons(FunctionRegistry* reg) {
   struct C { const char* name; int op; };
   for (C c : {C{"equal", AH_CMP_EQ}, C{"not_equal", AH_CMP_NE}, C{"greater", AH_CMP_GT}, C{"greater_equal", AH_CMP_GE}}) {
@@ -282,7 +381,22 @@ void RegisterScalarComparisons(FunctionRegistry* reg) {
       k.exec_fn = [op](KernelCtx* kc, const ExecSpan& b, ExecResult* o) { return ExecCompare(kc, b, o, op); };
       fn->AddKernel(std::move(k));
     }
+    // base-binary, decimal and FixedSizeBinary kernels (CompareKernels, kernels/scalar_comparisons.go:694-713): each matches its
+    // own type id on both sides; the mixed pairings DispatchBest resolves reach them uncast
+    for (Type t : {Type::STRING, Type::BINARY, Type::LARGE_STRING, Type::LARGE_BINARY, Type::DECIMAL128, Type::DECIMAL256,
+                   Type::FIXED_SIZE_BINARY}) {
+      exec::ScalarKernel k;
+      k.sig.in_types = {t, t};
+      k.sig.out_is_first_input = false;
+      k.sig.out_type = Type::BOOL;
+      k.consumes_uncast = true;
+      int op = c.op;
+      if (IsDecimal(t)) k.exec_fn = [op](KernelCtx* kc, const ExecSpan& b, ExecResult* o) { return ExecCompareDecimal(kc, b, o, op); };
+      else k.exec_fn = [op](KernelCtx* kc, const ExecSpan& b, ExecResult* o) { return ExecCompareBytes(kc, b, o, op); };
+      fn->AddKernel(std::move(k));
+    }
     fn->promote_numeric = true;  // compareFunction.DispatchBest (scalar_compare.go:37-63)
+    fn->promote_binary_decimal = true;
     reg->AddFunction(fn, false);
   }
   // scalar_compare.go:73-99: less / less_equal = flipped greater / greater_equal

@@ -350,3 +350,38 @@ func (x *Context) IsInDictGather(indexWidth int, indices, valid unsafe.Pointer, 
 	return x.err(C.ah_is_in_dict_gather(x.c, C.int(indexWidth), indices, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), (*C.uint8_t)(lutData),
 		(*C.uint8_t)(lutValid), C.int64_t(lutN), (*C.uint8_t)(outData), (*C.uint8_t)(outValid), C.int64_t(outBitOffset)))
 }
+
+// CmpOperand is one side of CompareBinary (ah_cmp_operand).  Base-binary: OffsetWidth 4 or 8, Offsets the offsets buffer, Data the
+// value bytes.  FixedSizeBinary: OffsetWidth 0, Data the slots of ByteWidth bytes.  Row i is element Off + i; Broadcast: a scalar,
+// every row reads element Off.
+type CmpOperand struct {
+	OffsetWidth, ByteWidth int
+	Offsets, Data          unsafe.Pointer
+	Off                    int64
+	Broadcast              bool
+}
+
+func (o CmpOperand) c() C.ah_cmp_operand {
+	var r C.ah_cmp_operand
+	r.offset_width, r.byte_width, r.offsets, r.data, r.off = C.int(o.OffsetWidth), C.int(o.ByteWidth), o.Offsets, (*C.uint8_t)(o.Data), C.int64_t(o.Off)
+	if o.Broadcast {
+		r.broadcast = 1
+	}
+	return r
+}
+
+// CompareBinary mirrors getBinaryCmp over the base-binary and FixedSizeBinary kernels of CompareKernels
+// (kernels/scalar_comparisons.go:520-540, 694-713): bytes.Equal / bytes.Compare of every row, null slots included, into bits
+// [outBitOffset, outBitOffset + n) of outBits.  The two sides may have different layouts.
+func (x *Context) CompareBinary(cmpOp int, l, r CmpOperand, n int64, outBits unsafe.Pointer, outBitOffset int64) error {
+	lc, rc := l.c(), r.c()
+	return x.err(C.ah_compare_binary(x.c, C.int(cmpOp), &lc, &rc, C.int64_t(n), (*C.uint8_t)(outBits), C.int64_t(outBitOffset)))
+}
+
+// CompareDecimal mirrors genDecimalCompareKernel (kernels/scalar_comparisons.go:370-392) after castBinaryDecimalArgs: each side
+// 16 or 32 bytes wide, compared as value · 10^scaleUp by signed value.  lBroadcast / rBroadcast 1: that side is a scalar.
+func (x *Context) CompareDecimal(cmpOp int, lWidth int, l unsafe.Pointer, lOff int64, lBroadcast int, lScaleUp int,
+	rWidth int, r unsafe.Pointer, rOff int64, rBroadcast int, rScaleUp int, n int64, outBits unsafe.Pointer, outBitOffset int64) error {
+	return x.err(C.ah_compare_decimal(x.c, C.int(cmpOp), C.int(lWidth), (*C.uint8_t)(l), C.int64_t(lOff), C.int(lBroadcast), C.int(lScaleUp),
+		C.int(rWidth), (*C.uint8_t)(r), C.int64_t(rOff), C.int(rBroadcast), C.int(rScaleUp), C.int64_t(n), (*C.uint8_t)(outBits), C.int64_t(outBitOffset)))
+}

@@ -312,6 +312,34 @@ int ah_round(ah_ctx* ctx, int type, const void* values, const uint8_t* valid, in
  * [prefix, prefix+length) are written. */
 int ah_comparison(ah_ctx* ctx, int cmpop, int shape, int type, const void* l, const void* r,
                   uint8_t* out_bits, int64_t length, int out_bit_offset);
+/* One operand of ah_compare_binary.  Base-binary (String / Binary / LargeString / LargeBinary): offset_width 4 or 8,
+ * `offsets` the offsets buffer, `data` the value bytes; row i is data[offsets[off + i] … offsets[off + i + 1]).  Fixed
+ * slots (FixedSizeBinary): offset_width 0, row i is the byte_width bytes at data + (off + i)·byte_width.  broadcast = 1:
+ * a scalar, every row reads element `off`.  Buffers are DEVICE memory; the descriptor itself is host memory. */
+typedef struct ah_cmp_operand {
+  int offset_width;
+  int byte_width;
+  const void* offsets;
+  const uint8_t* data;
+  int64_t off;
+  int broadcast;
+} ah_cmp_operand;
+/* equal / not_equal / greater / greater_equal of byte strings (getBinaryCmp, kernels/scalar_comparisons.go:520-540, in
+ * the base-binary and FixedSizeBinary kernels of CompareKernels, :694-713): bytes.Equal / bytes.Compare — unsigned
+ * bytewise, a proper prefix first.  The two operands may have different layouts (String ∘ LargeBinary, FixedSizeBinary[3]
+ * ∘ FixedSizeBinary[1], FixedSizeBinary ∘ String) and need no cast.  Every row is computed, null slots included (the
+ * caller owns the validity).  Writes bits [out_bit_offset, out_bit_offset + n) of out_bits, every other bit kept.  No host
+ * synchronisation. */
+int ah_compare_binary(ah_ctx* ctx, int cmpop, const ah_cmp_operand* l, const ah_cmp_operand* r, int64_t n, uint8_t* out_bits,
+                      int64_t out_bit_offset);
+/* the same comparisons of Decimal128 / Decimal256 values (genDecimalCompareKernel, kernels/scalar_comparisons.go:370-392)
+ * by signed value.  Each side: width 16 or 32 (two's complement, little-endian; a 16-byte side is sign-extended),
+ * element offset, broadcast flag (a scalar: every row reads element off) and scale-up exponent k (0 … 76): the side is
+ * compared as value · 10^k, the rescale castBinaryDecimalArgs asks for (compute/utils.go:261-326) — exact for every
+ * value within the promoted precision (≤ 76 digits).  Output as ah_compare_binary.  No host synchronisation. */
+int ah_compare_decimal(ah_ctx* ctx, int cmpop, int l_width, const uint8_t* l, int64_t l_off, int l_broadcast, int l_scaleup,
+                       int r_width, const uint8_t* r, int64_t r_off, int r_broadcast, int r_scaleup, int64_t n,
+                       uint8_t* out_bits, int64_t out_bit_offset);
 
 /* ---- null-bitmap utilities -----------------------------------------------------
  * replace bitutil.BitmapAnd/Or/Xor/AndNot/Xnor (arrow/bitutil/bitmaps.go:592-637 →

@@ -152,6 +152,10 @@ int ahc_import_device(ahc_session* s, struct ArrowDeviceArray* darr, struct Arro
 int ahc_export_device(ahc_session* s, ahc_datum* d, struct ArrowDeviceArray* out, struct ArrowSchema* schema);
 /* scalar.Scalar of arrow.Type `type_id` (ids as in arrowhip.h; 1 = BOOL); value8: little-endian payload, 8 bytes */
 int ahc_scalar(ahc_session* s, int type_id, int valid, const void* value8, ahc_datum** out);
+/* a String / Binary / LargeString / LargeBinary / FixedSizeBinary / Decimal scalar: `format` its Arrow C Data format ("u", "z",
+ * "U", "Z", "w:16", "d:10,2", "d:40,5,256"), data / len the value's bytes (a decimal: little-endian two's complement of the
+ * unscaled value, 16 or 32 bytes; a FixedSizeBinary: exactly its width).  Copied; ignored when valid = 0. */
+int ahc_scalar_bytes(ahc_session* s, const char* format, int valid, const void* data, int64_t len, ahc_datum** out);
 /* temporal label of a datum as its C Data format ("tsu:UTC", "tdD", …; "" = plain); valid until the next call on
  * this thread.  ahc_scalar_set_logical labels a scalar made by ahc_scalar (AHC_ETYPE if the storage width differs). */
 const char* ahc_datum_logical(ahc_datum* d);
