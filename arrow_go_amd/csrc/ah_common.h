@@ -342,3 +342,35 @@ __device__ __forceinline__ uint64_t ah_load_bits64(const uint8_t* __restrict__ b
   if (shift != 0 && shift + nvalid > 64) lo |= w[1] << (64 - shift);
   return lo & mask;
 }
+
+// Bits [pos, pos + cnt) of a bitmap := the low cnt bits of `word`, every other bit preserved.  A whole aligned word is one
+// store; a general position is up to three aligned 32-bit words, atomics because a neighbouring chunk may own the other
+// bits of the same word.
+__device__ __forceinline__ void put_bits(uint8_t* __restrict__ bm, int64_t pos, unsigned long long word, int cnt) {
+  const uintptr_t addr = (uintptr_t)bm + (uintptr_t)(pos >> 3);
+  const int sub = (int)(pos & 7);
+  if (cnt == 64 && sub == 0 && (addr & 7) == 0) {
+    *(unsigned long long*)addr = word;
+    return;
+  }
+  const uintptr_t base = addr & ~(uintptr_t)3;
+  int shift = (int)((addr - base) * 8) + sub;  // 0..31
+  const unsigned long long m = cnt >= 64 ? ~0ull : ((1ull << cnt) - 1);
+  word &= m;
+  unsigned* w = (unsigned*)base;
+  // 96-bit window
+  const unsigned long long mlo = m << shift, vlo = word << shift;
+  const unsigned long long mhi = shift ? (m >> (64 - shift)) : 0ull, vhi = shift ? (word >> (64 - shift)) : 0ull;
+  const unsigned m0 = (unsigned)mlo, m1 = (unsigned)(mlo >> 32), m2 = (unsigned)mhi;
+  const unsigned v0 = (unsigned)vlo, v1 = (unsigned)(vlo >> 32), v2 = (unsigned)vhi;
+  if (m0) { atomicAnd(&w[0], ~m0); if (v0) atomicOr(&w[0], v0); }
+  if (m1) { atomicAnd(&w[1], ~m1); if (v1) atomicOr(&w[1], v1); }
+  if (m2) { atomicAnd(&w[2], ~m2); if (v2) atomicOr(&w[2], v2); }
+}
+
+// The ballot of 64-row chunk `chunk` (cnt ≤ 64 rows) into bits out_off + 64·chunk … of `out`: one 64-bit store when the
+// output is word-aligned (aligned: out_off % 64 == 0 and `out` 8-byte aligned) and the chunk is full, else put_bits.
+__device__ __forceinline__ void put_word(uint8_t* __restrict__ out, int64_t out_off, int aligned, int64_t chunk, unsigned long long word, int cnt) {
+  if (aligned && cnt == 64) *(unsigned long long*)(out + (out_off + chunk * 64) / 8) = word;
+  else put_bits(out, out_off + chunk * 64, word, cnt);
+}

@@ -5,21 +5,21 @@
 // :370-392) behind compute's "equal", "not_equal", "greater", "greater_equal" (+ "less" / "less_equal" by operand swap,
 // compute/scalar_compare.go:73-99).
 //
-// Byte strings (bytes.Equal / bytes.Compare: unsigned, bytewise, a proper prefix first).  Each operand is a descriptor —
-// 4- or 8-byte offsets + data, or fixed slots of byte_width bytes — so String ∘ LargeBinary, FixedSizeBinary[3] ∘
+// Byte strings (bytes.Equal / bytes.Compare: unsigned, bytewise, a proper prefix first).  Each operand is a ByteRows column
+// (ah_bytes.h) — 4- or 8-byte offsets + data, or fixed slots of byte_width bytes — so String ∘ LargeBinary, FixedSizeBinary[3] ∘
 // FixedSizeBinary[1] and FixedSizeBinary ∘ String compare as they are, with no cast.  One row per lane, one ballot per
 // 64 rows, written as one 64-bit word.  equal / not_equal decide from the two lengths first: only rows of equal length
 // read bytes.  Ordering compares byte-swapped 8-byte words; the first word that differs decides, else the lengths do.
 // A lane compares at most kLaneCmp bytes itself; a row whose common prefix goes further is handed to the whole wave,
 // which compares 512 bytes per step (64 lanes × 8 bytes), one pending row after another — a 4 KiB value does not
-// serialise its 63 neighbours (the long-value path of ah_setlookup_binary.hip).  A broadcast (scalar) operand is read
-// once per workgroup into LDS when it is at most kScalarLds bytes, else read from global memory.
+// serialise its 63 neighbours (wave_compare of ah_bytes.h, shared with is_in).  A broadcast (scalar) operand is read once per
+// workgroup into LDS when it is at most kScalarLds bytes, else read from global memory.  The word orders (order_words,
+// order_range) are ah_bytes.h's; the result word is stored by put_word (ah_common.h).
 //
 // Decimals: one 16- or 32-byte load per row, sign-extended to 256 bits, multiplied by 10^k (the side's scale-up, from a
 // table of 64-bit powers of ten) and compared as signed two's complement: top word signed, lower words unsigned.
 #include "ah_common.h"
 #include "ah_bytes.h"
-#include "ah_setlookup.h"
 
 namespace {
 
@@ -28,79 +28,30 @@ constexpr int64_t kLaneFast = 64;  // bytes of the lane's first, unrolled compar
 constexpr int64_t kLaneCmp = 256;  // bytes a lane compares on its own (32 words: a 65-byte shared prefix stays lane-local)
 constexpr int kScalarLds = 4096;  // a broadcast value up to this many bytes is staged in LDS
 
-struct Side {
-  const void* offsets;
-  const uint8_t* data;
-  int64_t off;
-  int w;
-  int bcast;
-};
-
-// row i's bytes: OW = 4 / 8 offsets of that width, OW = 0 fixed slots of s.w bytes
-template <int OW>
-__device__ __forceinline__ void bytes_at(const Side& s, int64_t i, const uint8_t** p, int64_t* len) {
-  if constexpr (OW == 4) {
-    const int32_t* o = (const int32_t*)s.offsets + s.off + i;
-    const int64_t b = o[0], e = o[1];
-    *p = s.data + b;
-    *len = e - b;
-  } else if constexpr (OW == 8) {
-    const long long* o = (const long long*)s.offsets + s.off + i;
-    const long long b = o[0], e = o[1];
-    *p = s.data + b;
-    *len = e - b;
-  } else {
-    *p = s.data + (s.off + i) * (int64_t)s.w;
-    *len = s.w;
-  }
-}
-
 // a broadcast operand's value: into `lds` when it fits (every thread of the block calls this)
 template <int OW>
-__device__ __forceinline__ void stage(const Side& s, uint8_t* lds, const uint8_t** p, int64_t* len) {
-  bytes_at<OW>(s, 0, p, len);
+__device__ __forceinline__ void stage(const ByteRows& s, uint8_t* lds, const uint8_t** p, int64_t* len) {
+  row_at<OW>(s, 0, p, len);
   if (*len <= kScalarLds) {
     for (int64_t j = threadIdx.x; j < *len; j += kBlock) lds[j] = (*p)[j];
     *p = lds;
   }
 }
 
-__device__ __forceinline__ int order_words(unsigned long long x, unsigned long long y) {
-  if (x == y) return 0;
-  return __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;
-}
-
-// bytes.Compare of bytes [from, to) of a and b (both at least `to` long): −1 / 0 / 1.  `from` is a multiple of 8, so a
-// value staged in LDS is read in aligned words.
-__device__ __forceinline__ int order_range(const uint8_t* a, const uint8_t* b, int64_t from, int64_t to) {
-  int64_t j = from;
-  for (; j + 8 <= to; j += 8) {
-    const int c = order_words(load8(a + j), load8(b + j));
-    if (c) return c;
-  }
-  if (j < to) return order_words(load_tail(a + j, (int)(to - j)), load_tail(b + j, (int)(to - j)));
-  return 0;
-}
-
 __device__ __forceinline__ bool decide(int op, int c) {
   return op == AH_CMP_EQ ? c == 0 : op == AH_CMP_NE ? c != 0 : op == AH_CMP_GT ? c > 0 : c >= 0;
 }
 
-__device__ __forceinline__ void emit(uint8_t* out, int64_t out_off, int aligned, int64_t ch, unsigned long long word, int cnt) {
-  if (aligned && cnt == 64) ((unsigned long long*)out)[(out_off >> 6) + ch] = word;
-  else put_bits(out, out_off + ch * 64, word, cnt);
-}
-
 template <int OWL, int OWR>
-__global__ __launch_bounds__(kBlock) void compare_bytes_kernel(Side L, Side R, int op, int64_t n, uint8_t* __restrict__ out, int64_t out_off,
-                                                               int aligned) {
+__global__ __launch_bounds__(kBlock) void compare_bytes_kernel(ByteRows L, ByteRows R, int l_bcast, int r_bcast, int op, int64_t n,
+                                                               uint8_t* __restrict__ out, int64_t out_off, int aligned) {
   __shared__ unsigned long long s_l[kScalarLds / 8], s_r[kScalarLds / 8];  // 8-byte aligned: staged values are read in words
   const uint8_t* lp = nullptr;
   const uint8_t* rp = nullptr;
   int64_t ll = 0, lr = 0;
-  if (L.bcast) stage<OWL>(L, (uint8_t*)s_l, &lp, &ll);
-  if (R.bcast) stage<OWR>(R, (uint8_t*)s_r, &rp, &lr);
-  if (L.bcast || R.bcast) __syncthreads();
+  if (l_bcast) stage<OWL>(L, (uint8_t*)s_l, &lp, &ll);
+  if (r_bcast) stage<OWR>(R, (uint8_t*)s_r, &rp, &lr);
+  if (l_bcast || r_bcast) __syncthreads();
   const bool eq_op = op == AH_CMP_EQ || op == AH_CMP_NE;
   const int lane = threadIdx.x & 63;
   const int64_t nchunks = (n + 63) >> 6;
@@ -117,8 +68,8 @@ __global__ __launch_bounds__(kBlock) void compare_bytes_kernel(Side L, Side R, i
     bool pend = false;
     int64_t m = 0;
     if (active) {
-      if (!L.bcast) bytes_at<OWL>(L, row, &a, &la);
-      if (!R.bcast) bytes_at<OWR>(R, row, &b, &lb);
+      if (!l_bcast) row_at<OWL>(L, row, &a, &la);
+      if (!r_bcast) row_at<OWR>(R, row, &b, &lb);
       m = la < lb ? la : lb;
       if (eq_op && la != lb) {
         c = 1;
@@ -142,32 +93,9 @@ __global__ __launch_bounds__(kBlock) void compare_bytes_kernel(Side L, Side R, i
       need = __ballot(pend);
     }
     // rows whose first kLaneCmp bytes tie and go on: the wave compares the rest, 512 bytes per step
-    while (need) {
-      const int l = __ffsll((long long)need) - 1;
-      need &= need - 1;
-      const uint8_t* wa = (const uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)a, l);
-      const uint8_t* wb = (const uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)b, l);
-      const int64_t wla = __shfl((long long)la, l), wlb = __shfl((long long)lb, l);
-      const int64_t m = wla < wlb ? wla : wlb;
-      int r = 0;
-      for (int64_t base = kLaneCmp; base < m; base += 64 * 8) {
-        const int64_t j = base + (int64_t)lane * 8;
-        int cc = 0;
-        if (j < m) {
-          const int64_t rest = m - j;
-          cc = rest >= 8 ? order_words(load8(wa + j), load8(wb + j)) : order_words(load_tail(wa + j, (int)rest), load_tail(wb + j, (int)rest));
-        }
-        const unsigned long long d = __ballot(cc != 0);
-        if (d) {
-          r = __shfl(cc, __ffsll((long long)d) - 1);
-          break;
-        }
-      }
-      if (r == 0) r = (wla > wlb) - (wla < wlb);
-      if (lane == l) c = r;
-    }
+    wave_compare<true>(need, a, b, m, kLaneCmp, [&](int r) { c = r != 0 ? r : (la > lb) - (la < lb); });
     const unsigned long long word = __ballot(active && decide(op, c));
-    if (lane == 0) emit(out, out_off, aligned, ch, word, cnt);
+    if (lane == 0) put_word(out, out_off, aligned, ch, word, cnt);
   }
 }
 
@@ -257,7 +185,7 @@ __global__ __launch_bounds__(kBlock) void compare_decimal_kernel(const uint8_t* 
       bit = decide(op, order_i256(a, b));
     }
     const unsigned long long word = __ballot(bit);
-    if (lane == 0) emit(out, out_off, aligned, ch, word, cnt);
+    if (lane == 0) put_word(out, out_off, aligned, ch, word, cnt);
   }
 }
 
@@ -273,14 +201,16 @@ unsigned chunk_grid(ah_ctx* c, int64_t n) { return ah_stream_grid(c, ah_ceil_div
 int out_aligned(const uint8_t* out, int64_t out_off) { return (out_off & 63) == 0 && ((uintptr_t)out & 7) == 0; }
 
 template <int OWL, int OWR>
-void launch_bytes(ah_ctx* c, const Side& l, const Side& r, int op, int64_t n, uint8_t* out, int64_t out_off) {
-  compare_bytes_kernel<OWL, OWR><<<chunk_grid(c, n), kBlock, 0, c->stream>>>(l, r, op, n, out, out_off, out_aligned(out, out_off));
+void launch_bytes(ah_ctx* c, const ah_cmp_operand* l, const ah_cmp_operand* r, int op, int64_t n, uint8_t* out, int64_t out_off) {
+  compare_bytes_kernel<OWL, OWR><<<chunk_grid(c, n), kBlock, 0, c->stream>>>(
+      byte_rows(OWL, l->offsets, l->data, l->byte_width, l->off), byte_rows(OWR, r->offsets, r->data, r->byte_width, r->off), l->broadcast ? 1 : 0,
+      r->broadcast ? 1 : 0, op, n, out, out_off, out_aligned(out, out_off));
 }
 
 template <int OWL>
-void launch_bytes_r(ah_ctx* c, int owr, const Side& l, const Side& r, int op, int64_t n, uint8_t* out, int64_t out_off) {
-  if (owr == 4) launch_bytes<OWL, 4>(c, l, r, op, n, out, out_off);
-  else if (owr == 8) launch_bytes<OWL, 8>(c, l, r, op, n, out, out_off);
+void launch_bytes_r(ah_ctx* c, const ah_cmp_operand* l, const ah_cmp_operand* r, int op, int64_t n, uint8_t* out, int64_t out_off) {
+  if (r->offset_width == 4) launch_bytes<OWL, 4>(c, l, r, op, n, out, out_off);
+  else if (r->offset_width == 8) launch_bytes<OWL, 8>(c, l, r, op, n, out, out_off);
   else launch_bytes<OWL, 0>(c, l, r, op, n, out, out_off);
 }
 
@@ -309,11 +239,9 @@ AH_EXPORT int ah_compare_binary(ah_ctx* c, int cmpop, const ah_cmp_operand* l, c
     if (o->offset_width != 0 && !o->offsets) return ah_fail(c, AH_EINVALID, "comparison: null offsets");
     if (!o->data && o->offset_width == 0 && o->byte_width > 0) return ah_fail(c, AH_EINVALID, "comparison: null data");
   }
-  const Side L{l->offsets, l->data, l->off, l->byte_width, l->broadcast ? 1 : 0};
-  const Side R{r->offsets, r->data, r->off, r->byte_width, r->broadcast ? 1 : 0};
-  if (l->offset_width == 4) launch_bytes_r<4>(c, r->offset_width, L, R, cmpop, n, out_bits, out_bit_offset);
-  else if (l->offset_width == 8) launch_bytes_r<8>(c, r->offset_width, L, R, cmpop, n, out_bits, out_bit_offset);
-  else launch_bytes_r<0>(c, r->offset_width, L, R, cmpop, n, out_bits, out_bit_offset);
+  if (l->offset_width == 4) launch_bytes_r<4>(c, l, r, cmpop, n, out_bits, out_bit_offset);
+  else if (l->offset_width == 8) launch_bytes_r<8>(c, l, r, cmpop, n, out_bits, out_bit_offset);
+  else launch_bytes_r<0>(c, l, r, cmpop, n, out_bits, out_bit_offset);
   AH_LAUNCH_CHECK(c);
   return AH_OK;
 }

@@ -63,15 +63,18 @@ struct U64Keys {  // Table[uint64] (xxh3_memo_table_types.go): the word is the k
 
 // BinaryMemoTable (internal/hashing/xxh3_memo_table.go): the slot word is {hash bits 63..32 | a row that
 // holds the value}; a slot is "mine" when the tags agree and the bytes of that row equal mine.  Both
-// halves arrive in one CAS, so a reader never sees a tag without its row.
-template <typename OffT>
-struct BinKeys {
-  const OffT* offsets;  // of row 0 of the call (buffer + array offset)
-  const uint8_t* data;
+// halves arrive in one CAS, so a reader never sees a tag without its row.  Rows are read through ah_bytes.h's
+// ByteRows: OW = 4 / 8 for String / Binary / LargeString / LargeBinary, OW = 0 for FixedSizeBinary / Decimal128 /
+// Decimal256 keys (kernels/vector_hash.go:608-609, 698: the same BinaryMemoTable, every value `w` bytes).
+template <int OW>
+struct ByteKeys {
+  ByteRows rows;  // of row 0 of the call
   static constexpr bool kLdsTable = false;
   __device__ __forceinline__ bool load(int64_t i, unsigned long long* word, uint64_t* h) const {
-    const int64_t b = (int64_t)offsets[i], e = (int64_t)offsets[i + 1];
-    *h = hash_bytes(data + b, e - b);
+    const uint8_t* p;
+    int64_t len;
+    row_at<OW>(rows, i, &p, &len);
+    *h = hash_bytes(p, len);
     *word = (*h & 0xFFFFFFFF00000000ull) | (unsigned long long)(unsigned)i;  // never all-ones: i < 2^32 − 1
     return true;
   }
@@ -79,26 +82,11 @@ struct BinKeys {
     if ((cur ^ word) >> 32) return false;
     const int64_t r = (int64_t)(unsigned)cur;
     if (r == i) return true;
-    const int64_t b = (int64_t)offsets[i], e = (int64_t)offsets[i + 1], rb = (int64_t)offsets[r], re = (int64_t)offsets[r + 1];
-    return e - b == re - rb && equal_bytes(data + b, data + rb, e - b);
-  }
-};
-
-// FixedSizeBinary / Decimal128 / Decimal256 keys (kernels/vector_hash.go:608-609, 698: the same BinaryMemoTable, every value
-// `w` bytes): the BinKeys scheme with the offsets implied — value i lives at data + i·w.
-struct FixKeys {
-  const uint8_t* data;  // of row 0 of the call
-  int w;
-  static constexpr bool kLdsTable = false;
-  __device__ __forceinline__ bool load(int64_t i, unsigned long long* word, uint64_t* h) const {
-    *h = hash_bytes(data + i * w, w);
-    *word = (*h & 0xFFFFFFFF00000000ull) | (unsigned long long)(unsigned)i;
-    return true;
-  }
-  __device__ __forceinline__ bool same(unsigned long long cur, unsigned long long word, int64_t i) const {
-    if ((cur ^ word) >> 32) return false;
-    const int64_t r = (int64_t)(unsigned)cur;
-    return r == i || equal_bytes(data + i * w, data + r * w, w);
+    const uint8_t *p, *q;
+    int64_t len, qlen;
+    row_at<OW>(rows, i, &p, &len);
+    row_at<OW>(rows, r, &q, &qlen);
+    return len == qlen && equal_bytes(p, q, len);
   }
 };
 
@@ -1128,8 +1116,8 @@ AH_EXPORT int ah_hash_binary_encode(ah_ctx* c, int offset_width, const void* off
   if ((uintptr_t)offsets & (uintptr_t)(offset_width - 1)) return ah_fail(c, AH_EINVALID, "hash: offsets not element-aligned");
   EncodeResult res;
   int rc = offset_width == 4
-               ? encode_core(c, BinKeys<int32_t>{(const int32_t*)offsets + off, data}, valid, off, n, encode_nulls, out_ids, nullptr, &res, out_first_rows)
-               : encode_core(c, BinKeys<int64_t>{(const int64_t*)offsets + off, data}, valid, off, n, encode_nulls, out_ids, nullptr, &res, out_first_rows);
+               ? encode_core(c, ByteKeys<4>{byte_rows(4, offsets, data, 0, off)}, valid, off, n, encode_nulls, out_ids, nullptr, &res, out_first_rows)
+               : encode_core(c, ByteKeys<8>{byte_rows(8, offsets, data, 0, off)}, valid, off, n, encode_nulls, out_ids, nullptr, &res, out_first_rows);
   if (rc != AH_OK) return rc;
   if (out_ids_valid && (rc = ids_validity(c, valid, off, n, encode_nulls, out_ids_valid)) != AH_OK) return rc;
   if (out_ndict_host) *out_ndict_host = res.ndict;
@@ -1148,7 +1136,7 @@ AH_EXPORT int ah_hash_fixed_encode(ah_ctx* c, int byte_width, const uint8_t* dat
   if (n == 0) return AH_OK;
   if (!data || !out_first_rows) return ah_fail(c, AH_EINVALID, "hash: null buffer");
   EncodeResult res;
-  int rc = encode_core(c, FixKeys{data + off * (int64_t)byte_width, byte_width}, valid, off, n, encode_nulls, out_ids, nullptr, &res, out_first_rows);
+  int rc = encode_core(c, ByteKeys<0>{byte_rows(0, nullptr, data, byte_width, off)}, valid, off, n, encode_nulls, out_ids, nullptr, &res, out_first_rows);
   if (rc != AH_OK) return rc;
   if (out_dict && res.ndict > 0) {
     fixed_dict_kernel<<<ah_stream_grid(c, ah_ceil_div(res.ndict * byte_width, kBlock), 8), kBlock, 0, c->stream>>>(data + off * (int64_t)byte_width, byte_width,

@@ -17,8 +17,9 @@
 // word (read-modify-write only where the output range is not word-aligned).
 // Long values: a lane hashes at most the first kHashPrefix bytes (plus the length and the last 8 bytes) and compares at
 // most kLaneCmp bytes itself.  A tag hit on a longer value is handed to the whole wave, which compares it 512 bytes per
-// step (64 lanes × 8 bytes), one pending row after another.  So no lane walks more than kHashPrefix + kLaneCmp bytes on
-// its own, whatever the longest value of its wave.
+// step (64 lanes × 8 bytes), one pending row after another (wave_compare of ah_bytes.h, shared with the comparisons).  So
+// no lane walks more than kHashPrefix + kLaneCmp bytes on its own, whatever the longest value of its wave.  Rows are read
+// through ah_bytes.h's ByteRows; result words are stored by put_word (ah_common.h).
 #include <vector>
 
 #include "ah_common.h"
@@ -45,25 +46,10 @@ __device__ __forceinline__ uint64_t key_hash(const uint8_t* p, int64_t len) {
   return h ^ (h >> 32);
 }
 
-// row i's bytes: OW = 4 / 8 offsets of that width, OW = 0 fixed width w
-template <int OW>
-__device__ __forceinline__ void row_bytes(const void* offsets, const uint8_t* data, int w, int64_t i, const uint8_t** p, int64_t* len) {
-  if constexpr (OW == 4) {
-    const int64_t b = ((const int32_t*)offsets)[i], e = ((const int32_t*)offsets)[i + 1];
-    *p = data + b; *len = e - b;
-  } else if constexpr (OW == 8) {
-    const int64_t b = ((const long long*)offsets)[i], e = ((const long long*)offsets)[i + 1];
-    *p = data + b; *len = e - b;
-  } else {
-    *p = data + i * (int64_t)w; *len = w;
-  }
-}
-
 // ---- build -------------------------------------------------------------------------------------------------------------
 // side table entries [base, base + n) for one piece: (pointer, length) of each value, length −1 for a null
 template <int OW>
-__global__ __launch_bounds__(kBlock) void set_refs_kernel(const void* __restrict__ offsets, const uint8_t* __restrict__ data, int w,
-                                                          const uint8_t* __restrict__ valid, int64_t off, int64_t n, int64_t base,
+__global__ __launch_bounds__(kBlock) void set_refs_kernel(ByteRows rows, const uint8_t* __restrict__ valid, int64_t off, int64_t n, int64_t base,
                                                           unsigned long long* __restrict__ ref_ptr, long long* __restrict__ ref_len,
                                                           unsigned* __restrict__ flags) {
   const int64_t stride = (int64_t)gridDim.x * kBlock;
@@ -76,7 +62,7 @@ __global__ __launch_bounds__(kBlock) void set_refs_kernel(const void* __restrict
     }
     const uint8_t* p;
     int64_t len;
-    row_bytes<OW>(offsets, data, w, off + i, &p, &len);
+    row_at<OW>(rows, i, &p, &len);
     ref_ptr[base + i] = (unsigned long long)(uintptr_t)p;
     ref_len[base + i] = len;
   }
@@ -109,8 +95,7 @@ __global__ __launch_bounds__(kBlock) void set_insert_kernel(const unsigned long 
 // ---- probe -------------------------------------------------------------------------------------------------------------
 // MODE 1: table in LDS (≤ kLdsSlots) · 2: table in HBM · 3: table in LDS, kLdsSlotsBig slots, 1024-thread workgroups
 template <int OW, int MODE, bool HAS_VALID, int BLOCK = (MODE == 3 ? kBlockBig : kBlock)>
-__global__ __launch_bounds__(BLOCK) void is_in_bytes_kernel(const void* __restrict__ offsets, const uint8_t* __restrict__ data, int w,
-                                                            const uint8_t* __restrict__ valid, int64_t off, int64_t n,
+__global__ __launch_bounds__(BLOCK) void is_in_bytes_kernel(ByteRows rows, const uint8_t* __restrict__ valid, int64_t off, int64_t n,
                                                             const unsigned long long* __restrict__ table, unsigned mask,
                                                             const unsigned long long* __restrict__ ref_ptr, const long long* __restrict__ ref_len,
                                                             const unsigned* __restrict__ flags, int null_behavior, int aligned,
@@ -136,7 +121,7 @@ __global__ __launch_bounds__(BLOCK) void is_in_bytes_kernel(const void* __restri
     int64_t len = 0;
     unsigned idx = 0, tag = 0;
     if (pend) {
-      row_bytes<OW>(offsets, data, w, off + row, &p, &len);
+      row_at<OW>(rows, row, &p, &len);
       const uint64_t h = key_hash(p, len);
       idx = (unsigned)h & mask;
       tag = (unsigned)(h >> 32);
@@ -159,58 +144,41 @@ __global__ __launch_bounds__(BLOCK) void is_in_bytes_kernel(const void* __restri
       }
       unsigned long long need = __ballot(coop);
       if (!need) break;  // every lane is done
-      while (need) {     // the wave compares each pending long value, 512 bytes per step
-        const int l = __ffsll((long long)need) - 1;
-        need &= need - 1;
-        const uint8_t* a = (const uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)p, l);
-        const uint8_t* b = (const uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)q, l);
-        const int64_t L = __shfl((long long)len, l);
-        bool diff = false;
-        for (int64_t j = (int64_t)lane * 8; j < L; j += 64 * 8) {
-          const int64_t rest = L - j;
-          diff |= rest >= 8 ? load8(a + j) != load8(b + j) : load_tail(a + j, (int)rest) != load_tail(b + j, (int)rest);
-        }
-        const bool eq = __ballot(diff) == 0ull;
-        if (lane == l) {
-          coop = false;
-          if (eq) { found = true; pend = false; }
-          else idx = (idx + 1) & mask;
-        }
-      }
+      wave_compare<false>(need, p, q, len, 0, [&](int diff) {  // the wave compares each pending long value
+        coop = false;
+        if (!diff) { found = true; pend = false; }
+        else idx = (idx + 1) & mask;
+      });
     }
     const unsigned long long fw = __ballot(found);
     const unsigned long long nulls = ~in_valid & range;
     const unsigned long long dword = fw | (rule.dnull ? nulls : 0ull);
     const unsigned long long vword = fw | (rule.vmiss ? in_valid : 0ull) | (rule.vnull ? nulls : 0ull);
     if (lane == 0) {
-      if (aligned && cnt == 64) {
-        ((unsigned long long*)out_data)[(out_off >> 6) + ch] = dword;
-        ((unsigned long long*)out_valid)[(out_off >> 6) + ch] = vword;
-      } else {
-        put_bits(out_data, out_off + ch * 64, dword, cnt);
-        put_bits(out_valid, out_off + ch * 64, vword, cnt);
-      }
+      put_word(out_data, out_off, aligned, ch, dword, cnt);
+      put_word(out_valid, out_off, aligned, ch, vword, cnt);
     }
   }
 }
 
 template <int OW, int MODE>
-void launch_bytes_probe(ah_ctx* c, unsigned grid, const void* offsets, const uint8_t* data, int w, const uint8_t* valid, int64_t off, int64_t n,
+void launch_bytes_probe(ah_ctx* c, unsigned grid, const ByteRows& rows, const uint8_t* valid, int64_t off, int64_t n,
                         const unsigned long long* table, unsigned mask, const unsigned long long* ref_ptr, const long long* ref_len,
                         const unsigned* flags, int nb, uint8_t* out_data, uint8_t* out_valid, int64_t out_off) {
   const int aligned = (out_off & 63) == 0 && (((uintptr_t)out_data | (uintptr_t)out_valid) & 7) == 0;
   constexpr int block = MODE == 3 ? kBlockBig : kBlock;
   if (valid)
-    is_in_bytes_kernel<OW, MODE, true><<<grid, block, 0, c->stream>>>(offsets, data, w, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb,
-                                                                     aligned, out_data, out_valid, out_off);
+    is_in_bytes_kernel<OW, MODE, true><<<grid, block, 0, c->stream>>>(rows, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb, aligned,
+                                                                     out_data, out_valid, out_off);
   else
-    is_in_bytes_kernel<OW, MODE, false><<<grid, block, 0, c->stream>>>(offsets, data, w, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb,
-                                                                      aligned, out_data, out_valid, out_off);
+    is_in_bytes_kernel<OW, MODE, false><<<grid, block, 0, c->stream>>>(rows, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb, aligned,
+                                                                      out_data, out_valid, out_off);
 }
 
 template <int OW>
 int run_bytes_probe(ah_ctx* c, const void* offsets, const uint8_t* data, int w, const uint8_t* valid, int64_t off, int64_t n, int nset,
                     const ah_set_chunk* set, int nb, uint8_t* out_data, uint8_t* out_valid, int64_t out_off) {
+  const ByteRows rows = byte_rows(OW, offsets, data, w, off);
   int64_t set_n = 0;
   for (int i = 0; i < nset; i++) set_n += set[i].n;
   unsigned long long cap = 64;  // load ≤ ¼
@@ -232,12 +200,10 @@ int run_bytes_probe(ah_ctx* c, const void* offsets, const uint8_t* data, int w, 
     const ah_set_chunk& sc = set[i];
     if (sc.n == 0) continue;
     const unsigned g = ah_stream_grid(c, ah_ceil_div(sc.n, kBlock), 8);
-    if (sc.offset_width == 4)
-      set_refs_kernel<4><<<g, kBlock, 0, c->stream>>>(sc.offsets, sc.data, 0, sc.valid, sc.off, sc.n, base, ref_ptr, ref_len, flags);
-    else if (sc.offset_width == 8)
-      set_refs_kernel<8><<<g, kBlock, 0, c->stream>>>(sc.offsets, sc.data, 0, sc.valid, sc.off, sc.n, base, ref_ptr, ref_len, flags);
-    else
-      set_refs_kernel<0><<<g, kBlock, 0, c->stream>>>(nullptr, sc.data, w, sc.valid, sc.off, sc.n, base, ref_ptr, ref_len, flags);
+    const ByteRows piece = byte_rows(sc.offset_width, sc.offsets, sc.data, w, sc.off);
+    if (sc.offset_width == 4) set_refs_kernel<4><<<g, kBlock, 0, c->stream>>>(piece, sc.valid, sc.off, sc.n, base, ref_ptr, ref_len, flags);
+    else if (sc.offset_width == 8) set_refs_kernel<8><<<g, kBlock, 0, c->stream>>>(piece, sc.valid, sc.off, sc.n, base, ref_ptr, ref_len, flags);
+    else set_refs_kernel<0><<<g, kBlock, 0, c->stream>>>(piece, sc.valid, sc.off, sc.n, base, ref_ptr, ref_len, flags);
     AH_LAUNCH_CHECK(c);
     base += sc.n;
   }
@@ -249,14 +215,14 @@ int run_bytes_probe(ah_ctx* c, const void* offsets, const uint8_t* data, int w, 
   const unsigned mask = (unsigned)(cap - 1);
   if (cap <= (unsigned long long)kLdsSlots) {
     const unsigned grid = ah_stream_grid(c, ah_ceil_div(nchunks, kBlock / 64), 8);
-    launch_bytes_probe<OW, 1>(c, grid, offsets, data, w, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb, out_data, out_valid, out_off);
+    launch_bytes_probe<OW, 1>(c, grid, rows, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb, out_data, out_valid, out_off);
   } else if (cap <= (unsigned long long)kLdsSlotsBig) {
     const unsigned need = (unsigned)ah_ceil_div(nchunks, kBlockBig / 64), per_cu = (unsigned)c->num_cu;
-    launch_bytes_probe<OW, 3>(c, need < per_cu ? need : per_cu, offsets, data, w, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb, out_data,
-                              out_valid, out_off);
+    launch_bytes_probe<OW, 3>(c, need < per_cu ? need : per_cu, rows, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb, out_data, out_valid,
+                              out_off);
   } else {
     const unsigned grid = ah_stream_grid(c, ah_ceil_div(nchunks, kBlock / 64), 8);
-    launch_bytes_probe<OW, 2>(c, grid, offsets, data, w, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb, out_data, out_valid, out_off);
+    launch_bytes_probe<OW, 2>(c, grid, rows, valid, off, n, table, mask, ref_ptr, ref_len, flags, nb, out_data, out_valid, out_off);
   }
   AH_LAUNCH_CHECK(c);
   return AH_OK;
@@ -297,13 +263,8 @@ __global__ __launch_bounds__(kBlock) void dict_gather_kernel(const IdxT* __restr
     }
     const unsigned long long dword = __ballot(d), vword = __ballot(v);
     if (lane == 0) {
-      if (aligned && cnt == 64) {
-        ((unsigned long long*)out_data)[(out_off >> 6) + ch] = dword;
-        ((unsigned long long*)out_valid)[(out_off >> 6) + ch] = vword;
-      } else {
-        put_bits(out_data, out_off + ch * 64, dword, cnt);
-        put_bits(out_valid, out_off + ch * 64, vword, cnt);
-      }
+      put_word(out_data, out_off, aligned, ch, dword, cnt);
+      put_word(out_valid, out_off, aligned, ch, vword, cnt);
     }
   }
 }

@@ -14,8 +14,9 @@
 //               that byte puts "ab" (2) before "ab\0" (3), and a row is still undecided after the round only while it is 8;
 //   fixed-size: bytes [8r, 8r + 8) big-endian, zero-padded; rows continue until the width is used up;
 //   decimal:    word (words − 1 − r), most significant first, the sign bit of the top word flipped;
-// complemented for descending.  Values are read with aligned 8-byte loads and a funnel shift: a load is issued only for an
-// aligned word that holds at least one byte of the value, so no read leaves the pages of the value's bytes.
+// complemented for descending.  A row's bytes are found through ah_bytes.h's ByteRows (layout chosen at run time).  Values are
+// read with aligned 8-byte loads and a funnel shift (load_le): a load is issued only for an aligned word that holds at least one
+// byte of the value, so no read leaves the pages of the value's bytes.
 //   round 0: one stable partition pass (null / rest, respecting rows_in) creates (key, row) pairs, then the stable LSD passes
 //            of ah_sort_radix.h over the key bytes that vary — the numeric sort with a different key;
 //   then:    the runs of equal, continuing keys are the rows still tied.  A flag scan compacts their positions in b.ra and
@@ -29,18 +30,18 @@
 // value (every row tied in every round, L / 7 rounds of ≈ 120 B/row plus two read-backs each; no LSD pass runs, because
 // neither the key nor the run index varies).
 #include "ah_sort_radix.h"
+#include "ah_bytes.h"
 
 namespace {
 
 constexpr int kWaveSeg = 512;  // longest run the one-wave bitonic network sorts
-enum { kVar32 = 0, kVar64 = 1, kFixed = 2, kDecimal = 3 };
+enum { kVar = 0, kFixed = 1, kDecimal = 2 };
 
 struct BinDesc {
-  int kind, width, nrounds, descending;
-  const uint8_t* data;
-  const void* offsets;
+  int kind, ow, nrounds, descending;  // ow: the offset width of a var-length key, 0 for a fixed-width one
+  ByteRows rows;                      // of row 0 of the column (ah_bytes.h)
   const uint8_t* valid;
-  int64_t off;
+  int64_t off;                        // validity bit off + row
 };
 
 // nb ≤ 8 bytes at p, byte 0 in the low bits, zeros above nb; only aligned words holding a byte of [p, p + nb) are loaded
@@ -56,20 +57,19 @@ __device__ __forceinline__ unsigned long long load_le(const uint8_t* p, int nb) 
 }
 
 __device__ __forceinline__ unsigned long long bin_key(const BinDesc& d, unsigned row, int r) {
+  const uint8_t* p;
+  int64_t len;
+  row_at(d.ow, d.rows, row, &p, &len);
   unsigned long long k;
-  const int64_t o = d.off + (int64_t)row;
-  if (d.kind == kVar32 || d.kind == kVar64) {
-    int64_t s, e;
-    if (d.kind == kVar32) { s = ((const int32_t*)d.offsets)[o]; e = ((const int32_t*)d.offsets)[o + 1]; }
-    else { s = ((const int64_t*)d.offsets)[o]; e = ((const int64_t*)d.offsets)[o + 1]; }
-    const int64_t p = s + 7 * (int64_t)r, rem = e - p;
+  if (d.kind == kVar) {
+    const int64_t rem = len - 7 * (int64_t)r;
     const int nb = rem < 7 ? (rem > 0 ? (int)rem : 0) : 7;
-    k = __builtin_bswap64(load_le(d.data + p, nb)) | (unsigned long long)(rem < 8 ? (rem > 0 ? rem : 0) : 8);
+    k = __builtin_bswap64(load_le(p + 7 * (int64_t)r, nb)) | (unsigned long long)(rem < 8 ? (rem > 0 ? rem : 0) : 8);
   } else if (d.kind == kFixed) {
-    const int left = d.width - 8 * r;
-    k = __builtin_bswap64(load_le(d.data + o * d.width + 8 * r, left < 8 ? left : 8));
+    const int left = (int)len - 8 * r;
+    k = __builtin_bswap64(load_le(p + 8 * r, left < 8 ? left : 8));
   } else {
-    k = load_le(d.data + o * d.width + 8 * (d.width / 8 - 1 - r), 8);
+    k = load_le(p + 8 * ((int)len / 8 - 1 - r), 8);
     if (r == 0) k ^= 1ull << 63;
   }
   return d.descending ? ~k : k;
@@ -77,7 +77,7 @@ __device__ __forceinline__ unsigned long long bin_key(const BinDesc& d, unsigned
 
 // does a row whose round-r key is k take part in round r + 1?
 __device__ __forceinline__ bool continues(const BinDesc& d, unsigned long long k, int r) {
-  if (d.kind == kVar32 || d.kind == kVar64) return ((d.descending ? ~k : k) & 0xFFull) == 8;
+  if (d.kind == kVar) return ((d.descending ? ~k : k) & 0xFFull) == 8;
   return r + 1 < d.nrounds;
 }
 
@@ -247,12 +247,11 @@ bool ah_sort_is_binary(int type) {
 
 int ah_sort_by_binary(ah_ctx* c, SortBuffers& b, const SortCol& col, int64_t n, const unsigned* rows_in) {
   BinDesc d;
-  d.kind = col.type == AH_BINARY ? kVar32 : col.type == AH_LARGE_BINARY ? kVar64 : col.type == AH_FIXED_SIZE_BINARY ? kFixed : kDecimal;
-  d.width = col.width;
+  d.kind = col.type == AH_BINARY || col.type == AH_LARGE_BINARY ? kVar : col.type == AH_FIXED_SIZE_BINARY ? kFixed : kDecimal;
+  d.ow = col.type == AH_BINARY ? 4 : col.type == AH_LARGE_BINARY ? 8 : 0;
   d.nrounds = d.kind == kFixed ? (col.width + 7) / 8 : d.kind == kDecimal ? col.width / 8 : 0;
   d.descending = col.descending;
-  d.data = col.data;
-  d.offsets = col.offsets;
+  d.rows = byte_rows(d.ow, col.offsets, col.data, col.width, col.off);
   d.valid = col.valid;
   d.off = col.off;
   const int64_t ntiles = ah_ceil_div(n, (int64_t)kTile * tiles_per_block(n));
@@ -286,7 +285,7 @@ int ah_sort_by_binary(ah_ctx* c, SortBuffers& b, const SortCol& col, int64_t n, 
   const unsigned long long* keys = kcur;
   int64_t m = rest_n;
   for (int r = 0;; r++) {
-    if (d.kind != kVar32 && d.kind != kVar64 && r + 1 >= d.nrounds) break;  // the last chunk of a fixed width: ties are final
+    if (d.kind != kVar && r + 1 >= d.nrounds) break;  // the last chunk of a fixed width: ties are final
     Ties t{d, r, keys, r == 0 ? nullptr : pos, r == 0 ? nullptr : head, (unsigned)rest_lo, m};
     const unsigned grid = ah_stream_grid(c, ah_ceil_div(m, kBlock), 8);
     tie_flags_kernel<<<grid, kBlock, 0, c->stream>>>(t, run);

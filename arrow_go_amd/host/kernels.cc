@@ -26,6 +26,34 @@ static const Type kNumericTypes[] = {Type::UINT8, Type::INT8,  Type::UINT16, Typ
 static inline const uint8_t* Values(const ArraySpan& a) { return a.buffers[1].buf + a.offset * (a.type->bit_width / 8); }
 static inline uint8_t* Values(ArraySpan* a) { return a->buffers[1].buf + a->offset * (a->type->bit_width / 8); }
 
+// Where the bytes of a base-binary or fixed-width array are, as the kernels' descriptors (ah_cmp_operand, ah_set_chunk,
+// ah_sort_key, ah_hash_*_encode) take them: String / Binary / LargeString / LargeBinary have offset_width 4 or 8, offsets in
+// buffer 1 and bytes in buffer 2; FixedSizeBinary / Decimal have byte_width-byte slots in buffer 1.
+struct ByteLayout {
+  int offset_width = 0, byte_width = 0;
+  const void* offsets = nullptr;
+  const uint8_t* data = nullptr;
+  int64_t offset = 0;
+};
+static ByteLayout LayoutOf(const DataType* t, const void* b1, const void* b2, int64_t offset) {
+  ByteLayout l;
+  l.offset = offset;
+  if (IsBaseBinary(t->id)) {
+    l.offset_width = t->bit_width / 8;
+    l.offsets = b1;
+    l.data = (const uint8_t*)b2;
+  } else {
+    l.byte_width = t->bit_width / 8;
+    l.data = (const uint8_t*)b1;
+  }
+  return l;
+}
+static ByteLayout LayoutOf(const ArraySpan& a) { return LayoutOf(a.type, a.buffers[1].buf, a.buffers[2].buf, a.offset); }
+static ByteLayout LayoutOf(const ArrayData& a) {
+  auto dptr = [&](int i) -> const void* { return a.buffers[i] ? a.buffers[i]->dptr : nullptr; };
+  return LayoutOf(a.type, dptr(1), dptr(2), a.offset);
+}
+
 static int ShapeOf(const ExecSpan& b) {
   if (b.values[0].IsArray()) return b.values[1].IsArray() ? AH_SHAPE_AA : AH_SHAPE_AS;
   return AH_SHAPE_SA;
@@ -269,19 +297,14 @@ static std::string DecimalText(const DataType* t) {
 }
 
 // one side of the call as a device array (a scalar: uploaded) + whether it is broadcast
-static Status CompareSide(Session* s, const exec::ExecValue& v, ArrayDataPtr* keep, const void** b1, const void** b2, int64_t* off, int* bcast) {
-  if (v.IsScalar()) {
-    AHC_RETURN_NOT_OK(ScalarToArray(s, *v.scalar, keep));
-    *b1 = (*keep)->buffers[1] ? (*keep)->buffers[1]->dptr : nullptr;
-    *b2 = (*keep)->buffers[2] ? (*keep)->buffers[2]->dptr : nullptr;
-    *off = 0;
-    *bcast = 1;
-  } else {
-    *b1 = v.array.buffers[1].buf;
-    *b2 = v.array.buffers[2].buf;
-    *off = v.array.offset;
-    *bcast = 0;
+static Status CompareSide(Session* s, const exec::ExecValue& v, ArrayDataPtr* keep, ByteLayout* l, int* bcast) {
+  *bcast = v.IsScalar() ? 1 : 0;
+  if (!v.IsScalar()) {
+    *l = LayoutOf(v.array);
+    return Status::OK();
   }
+  AHC_RETURN_NOT_OK(ScalarToArray(s, *v.scalar, keep));
+  *l = LayoutOf(**keep);
   return Status::OK();
 }
 
@@ -293,21 +316,9 @@ static Status ExecCompareBytes(KernelCtx* k, const ExecSpan& b, ExecResult* out,
   ah_cmp_operand o[2];
   ArrayDataPtr keep[2];
   for (int i = 0; i < 2; i++) {
-    const exec::ExecValue& v = b.values[i];
-    const DataType* t = v.type();
-    const void *b1, *b2;
-    AHC_RETURN_NOT_OK(CompareSide(s, v, &keep[i], &b1, &b2, &o[i].off, &o[i].broadcast));
-    if (IsBaseBinary(t->id)) {
-      o[i].offset_width = t->bit_width / 8;
-      o[i].byte_width = 0;
-      o[i].offsets = b1;
-      o[i].data = (const uint8_t*)b2;
-    } else {
-      o[i].offset_width = 0;
-      o[i].byte_width = t->bit_width / 8;
-      o[i].offsets = nullptr;
-      o[i].data = (const uint8_t*)b1;
-    }
+    ByteLayout l;
+    AHC_RETURN_NOT_OK(CompareSide(s, b.values[i], &keep[i], &l, &o[i].broadcast));
+    o[i] = ah_cmp_operand{l.offset_width, l.byte_width, l.offsets, l.data, l.offset, o[i].broadcast};
   }
   return s->FromStatus(ah_compare_binary(s->ctx(), cmpop, &o[0], &o[1], out->len, out->buffers[1].buf, out->offset));
 }
@@ -344,17 +355,12 @@ static Status ExecCompareDecimal(KernelCtx* k, const ExecSpan& b, ExecResult* ou
   }
   if (out->len == 0) return Status::OK();
   const int target = std::max(sc[0], sc[1]);
-  const void* data[2];
-  int64_t off[2];
+  ByteLayout l[2];
   int bcast[2];
   ArrayDataPtr keep[2];
-  for (int i = 0; i < 2; i++) {
-    const void* unused;
-    AHC_RETURN_NOT_OK(CompareSide(s, vals[i], &keep[i], &data[i], &unused, &off[i], &bcast[i]));
-  }
-  return s->FromStatus(ah_compare_decimal(s->ctx(), cmpop, t[0]->bit_width / 8, (const uint8_t*)data[0], off[0], bcast[0], target - sc[0],
-                                          t[1]->bit_width / 8, (const uint8_t*)data[1], off[1], bcast[1], target - sc[1], out->len,
-                                          out->buffers[1].buf, out->offset));
+  for (int i = 0; i < 2; i++) AHC_RETURN_NOT_OK(CompareSide(s, vals[i], &keep[i], &l[i], &bcast[i]));
+  return s->FromStatus(ah_compare_decimal(s->ctx(), cmpop, l[0].byte_width, l[0].data, l[0].offset, bcast[0], target - sc[0], l[1].byte_width, l[1].data,
+                                          l[1].offset, bcast[1], target - sc[1], out->len, out->buffers[1].buf, out->offset));
 }
 
 void RegisterScalarComparisons(FunctionRegistry* reg) {
@@ -950,6 +956,36 @@ void RegisterVectorSelection(FunctionRegistry* reg) {
 }
 
 // ---- hashing -----------------------------------------------------------------------------------
+// The common end of unique / dictionary_encode.  `d` is the dictionary (GetDictArrayData, arrow/array/util.go:321-390): its
+// type, length and value buffers are set; if the memo table holds a null (null_id ≥ 0), its validity is all ones with that
+// bit cleared (memory.Set(…, 0xFF), util.go:375-384).  unique returns the dictionary itself (uniqueFinalize,
+// vector_hash.go:721-741); dictionary_encode returns the ids with `d` attached (dictionaryEncodeAction.Flush :188-209).
+static Status FinishHash(KernelCtx* k, const ArraySpan& keys, const ArrayDataPtr& d, int32_t null_id, bool dict_encode, const BufferPtr& ids,
+                         const BufferPtr& ids_valid, ExecResult* out) {
+  Session* s = k->session;
+  d->null_count = null_id >= 0 ? 1 : 0;
+  if (null_id >= 0) {
+    BufferPtr dv;
+    AHC_RETURN_NOT_OK(k->AllocateBitmap(d->length, &dv));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_memset_async(s->ctx(), dv->dptr, 0xFF, (size_t)((d->length + 7) / 8))));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_set_bits_to(s->ctx(), (uint8_t*)dv->dptr, null_id, 1, 0)));
+    d->buffers[0] = dv;
+  }
+  if (!dict_encode) {
+    out->type = d->type;
+    out->len = d->length;
+    out->nulls = d->null_count;
+    for (int i = 0; i < 3; i++) out->buffers[i].WrapBuffer(d->buffers[i]);
+    return Status::OK();
+  }
+  out->len = keys.len;
+  out->nulls = ids_valid ? keys.nulls : 0;
+  out->buffers[0].WrapBuffer(ids_valid);
+  out->buffers[1].WrapBuffer(ids);
+  out->dictionary = d;
+  return Status::OK();
+}
+
 // regularHashState over Table[uint64] (vector_hash.go:243-286,359-385,604-607)
 static Status ExecHash(KernelCtx* k, const ExecSpan& b, ExecResult* out, bool dict_encode) {
   Session* s = k->session;
@@ -986,12 +1022,10 @@ static Status ExecHash(KernelCtx* k, const ExecSpan& b, ExecResult* out, bool di
     AHC_RETURN_NOT_OK(s->FromStatus(ah_hash_u64_encode(s->ctx(), keys64, valid, keys.offset, n, encode_nulls,
                                                        ids ? (int32_t*)ids->dptr : nullptr, ids_valid ? (uint8_t*)ids_valid->dptr : nullptr,
                                                        (uint64_t*)dict->dptr, &ndict, &null_id)));
-  // GetDictArrayData (arrow/array/util.go:321-390): values by memo index; if the table holds
-  // a null, validity = all ones with that bit cleared
+  // GetDictArrayData (arrow/array/util.go:321-390): values by memo index
   auto d = std::make_shared<ArrayData>();
   d->type = keys.type;
   d->length = ndict;
-  d->null_count = null_id >= 0 ? 1 : 0;
   if (is_bool) {
     BufferPtr bits;
     AHC_RETURN_NOT_OK(k->AllocateBitmap(ndict, &bits));
@@ -1007,27 +1041,7 @@ static Status ExecHash(KernelCtx* k, const ExecSpan& b, ExecResult* out, bool di
   }
   d->buffers[1] = dict;
   dict->size = is_bool ? (ndict + 7) / 8 : ndict * kw;
-  if (null_id >= 0) {
-    BufferPtr dv;
-    AHC_RETURN_NOT_OK(k->AllocateBitmap(ndict, &dv));
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_memset_async(s->ctx(), dv->dptr, 0xFF, (size_t)((ndict + 7) / 8))));  // memory.Set(…, 0xFF), util.go:381
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_set_bits_to(s->ctx(), (uint8_t*)dv->dptr, null_id, 1, 0)));
-    d->buffers[0] = dv;
-  }
-  if (!dict_encode) {  // uniqueFinalize (vector_hash.go:721-741): the result IS the dictionary
-    out->type = d->type;
-    out->len = d->length;
-    out->nulls = d->null_count;
-    out->buffers[0].WrapBuffer(d->buffers[0]);
-    out->buffers[1].WrapBuffer(d->buffers[1]);
-    return Status::OK();
-  }
-  out->len = n;
-  out->nulls = ids_valid ? keys.nulls : 0;  // dictionaryEncodeAction.Flush :188-209
-  out->buffers[0].WrapBuffer(ids_valid);
-  out->buffers[1].WrapBuffer(ids);
-  out->dictionary = d;
-  return Status::OK();
+  return FinishHash(k, keys, d, null_id, dict_encode, ids, ids_valid, out);
 }
 
 // regularHashState over BinaryMemoTable (vector_hash.go:288-325,612-618): ids on the device, the dictionary
@@ -1040,7 +1054,7 @@ static Status ExecHashBinary(KernelCtx* k, const ExecSpan& b, ExecResult* out, b
   AHC_RETURN_NOT_OK(keys.UpdateNullCount(s));
   const uint8_t* valid = keys.MayHaveNulls() ? keys.buffers[0].buf : nullptr;
   const int64_t n = keys.len;
-  const int ow = keys.type->bit_width / 8;
+  const ByteLayout l = LayoutOf(keys);
   BufferPtr ids, ids_valid, first_rows;
   AHC_RETURN_NOT_OK(k->Allocate((n + 1) * 8, &first_rows));
   if (dict_encode) {
@@ -1049,42 +1063,19 @@ static Status ExecHashBinary(KernelCtx* k, const ExecSpan& b, ExecResult* out, b
   }
   int64_t ndict = 0; int32_t null_id = -1;
   if (n > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_hash_binary_encode(s->ctx(), ow, keys.buffers[1].buf, keys.buffers[2].buf, valid, keys.offset, n, encode_nulls,
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_hash_binary_encode(s->ctx(), l.offset_width, l.offsets, l.data, valid, l.offset, n, encode_nulls,
                                                           ids ? (int32_t*)ids->dptr : nullptr, ids_valid ? (uint8_t*)ids_valid->dptr : nullptr,
                                                           (int64_t*)first_rows->dptr, &ndict, &null_id)));
-  // GetDictArrayData (arrow/array/util.go:341-366): offsets + values in memo order, a null entry has no
-  // bytes; validity = all ones with the null's bit cleared (:375-384)
+  // GetDictArrayData (arrow/array/util.go:341-366): offsets + values in memo order, a null entry has no bytes
   ExecResult dres;
   dres.type = keys.type;
   AHC_RETURN_NOT_OK(TakeBinaryCommon(k, keys, 8, true, first_rows->dptr, nullptr, 0, ndict, false, &dres));
   auto d = std::make_shared<ArrayData>();
   d->type = keys.type;
   d->length = ndict;
-  d->null_count = null_id >= 0 ? 1 : 0;
   d->buffers[1] = dres.buffers[1].owner;
   d->buffers[2] = dres.buffers[2].owner;
-  if (null_id >= 0) {
-    BufferPtr dv;
-    AHC_RETURN_NOT_OK(k->AllocateBitmap(ndict, &dv));
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_memset_async(s->ctx(), dv->dptr, 0xFF, (size_t)((ndict + 7) / 8))));
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_set_bits_to(s->ctx(), (uint8_t*)dv->dptr, null_id, 1, 0)));
-    d->buffers[0] = dv;
-  }
-  if (!dict_encode) {  // uniqueFinalize (vector_hash.go:721-741)
-    out->type = d->type;
-    out->len = d->length;
-    out->nulls = d->null_count;
-    out->buffers[0].WrapBuffer(d->buffers[0]);
-    out->buffers[1].WrapBuffer(d->buffers[1]);
-    out->buffers[2].WrapBuffer(d->buffers[2]);
-    return Status::OK();
-  }
-  out->len = n;
-  out->nulls = ids_valid ? keys.nulls : 0;
-  out->buffers[0].WrapBuffer(ids_valid);
-  out->buffers[1].WrapBuffer(ids);
-  out->dictionary = d;
-  return Status::OK();
+  return FinishHash(k, keys, d, null_id, dict_encode, ids, ids_valid, out);
 }
 
 // FixedSizeBinary / Decimal128 / Decimal256 keys (vector_hash.go:608-609, 698: the BinaryMemoTable over values of one byte width):
@@ -1097,7 +1088,8 @@ static Status ExecHashFixed(KernelCtx* k, const ExecSpan& b, ExecResult* out, bo
   AHC_RETURN_NOT_OK(keys.UpdateNullCount(s));
   const uint8_t* valid = keys.MayHaveNulls() ? keys.buffers[0].buf : nullptr;
   const int64_t n = keys.len;
-  const int w = keys.type->bit_width / 8;
+  const ByteLayout l = LayoutOf(keys);
+  const int w = l.byte_width;
   if (w <= 0) return Status::Make(StatusCode::Invalid, "fixed-size binary keys need a byte width");
   BufferPtr ids, ids_valid, first_rows, dict;
   AHC_RETURN_NOT_OK(k->Allocate((n + 1) * 8, &first_rows));
@@ -1108,35 +1100,14 @@ static Status ExecHashFixed(KernelCtx* k, const ExecSpan& b, ExecResult* out, bo
   }
   int64_t ndict = 0; int32_t null_id = -1;
   if (n > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_hash_fixed_encode(s->ctx(), w, keys.buffers[1].buf, valid, keys.offset, n, encode_nulls, ids ? (int32_t*)ids->dptr : nullptr,
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_hash_fixed_encode(s->ctx(), w, l.data, valid, l.offset, n, encode_nulls, ids ? (int32_t*)ids->dptr : nullptr,
                                                          ids_valid ? (uint8_t*)ids_valid->dptr : nullptr, (int64_t*)first_rows->dptr, (uint8_t*)dict->dptr,
                                                          &ndict, &null_id)));
   auto d = std::make_shared<ArrayData>();
   d->type = keys.type;
   d->length = ndict;
-  d->null_count = null_id >= 0 ? 1 : 0;
   d->buffers[1] = dict;
-  if (null_id >= 0) {   // GetDictArrayData (arrow/array/util.go:375-384): all ones with the null entry's bit cleared
-    BufferPtr dv;
-    AHC_RETURN_NOT_OK(k->AllocateBitmap(ndict, &dv));
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_memset_async(s->ctx(), dv->dptr, 0xFF, (size_t)((ndict + 7) / 8))));
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_set_bits_to(s->ctx(), (uint8_t*)dv->dptr, null_id, 1, 0)));
-    d->buffers[0] = dv;
-  }
-  if (!dict_encode) {  // uniqueFinalize (vector_hash.go:721-741)
-    out->type = d->type;
-    out->len = d->length;
-    out->nulls = d->null_count;
-    out->buffers[0].WrapBuffer(d->buffers[0]);
-    out->buffers[1].WrapBuffer(d->buffers[1]);
-    return Status::OK();
-  }
-  out->len = n;
-  out->nulls = ids_valid ? keys.nulls : 0;
-  out->buffers[0].WrapBuffer(ids_valid);
-  out->buffers[1].WrapBuffer(ids);
-  out->dictionary = d;
-  return Status::OK();
+  return FinishHash(k, keys, d, null_id, dict_encode, ids, ids_valid, out);
 }
 
 void RegisterVectorHash(FunctionRegistry* reg) {
@@ -1359,27 +1330,18 @@ static Status ExecIsIn(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
   }
   std::vector<ah_set_chunk> set;
   for (auto& pc : parts) {
-    ah_set_chunk c{};
-    auto dptr = [&](int i) -> const void* { return pc->buffers[i] ? pc->buffers[i]->dptr : nullptr; };
-    c.valid = pc->null_count != 0 ? (const uint8_t*)dptr(0) : nullptr;
-    c.off = pc->offset;
-    c.n = pc->length;
-    if (IsBaseBinary(pc->type->id)) {
-      c.offset_width = pc->type->bit_width / 8;
-      c.offsets = dptr(1);
-      c.data = (const uint8_t*)dptr(2);
-    } else {
-      c.data = (const uint8_t*)dptr(1);
-    }
-    set.push_back(c);
+    const ByteLayout l = LayoutOf(*pc);
+    const uint8_t* set_valid = pc->null_count != 0 && pc->buffers[0] ? (const uint8_t*)pc->buffers[0]->dptr : nullptr;
+    set.push_back(ah_set_chunk{l.offset_width, l.offsets, l.data, set_valid, l.offset, pc->length});
   }
+  const ByteLayout l = LayoutOf(in);
   int rc;
-  if (IsBaseBinary(id))
-    rc = ah_is_in_binary(s->ctx(), in.type->bit_width / 8, in.buffers[1].buf, in.buffers[2].buf, valid, in.offset, in.len, (int)set.size(), set.data(),
-                         opts->NullBehavior, out->buffers[1].buf, out->buffers[0].buf, out->offset);
+  if (l.offset_width)
+    rc = ah_is_in_binary(s->ctx(), l.offset_width, l.offsets, l.data, valid, l.offset, in.len, (int)set.size(), set.data(), opts->NullBehavior,
+                         out->buffers[1].buf, out->buffers[0].buf, out->offset);
   else
-    rc = ah_is_in_fixed(s->ctx(), in.type->bit_width / 8, in.buffers[1].buf, valid, in.offset, in.len, (int)set.size(), set.data(), opts->NullBehavior,
-                        out->buffers[1].buf, out->buffers[0].buf, out->offset);
+    rc = ah_is_in_fixed(s->ctx(), l.byte_width, l.data, valid, l.offset, in.len, (int)set.size(), set.data(), opts->NullBehavior, out->buffers[1].buf,
+                        out->buffers[0].buf, out->offset);
   AHC_RETURN_NOT_OK(s->FromStatus(rc));
   out->nulls = kUnknownNullCount;
   return Status::OK();
@@ -1480,19 +1442,16 @@ static Status SortIndicesImpl(ExecCtx* ctx, const FunctionOptions* o, const std:
       return Status::Make(StatusCode::Invalid, "sort key " + std::to_string(i) + " has invalid column index " + std::to_string(key.ColumnIndex));  // :158-160
     const ArrayData& a = *args[key.ColumnIndex].array;
     const Type id = a.type->id;
-    auto dptr = [&](int b) -> const void* { return a.buffers[b] ? a.buffers[b]->dptr : nullptr; };
     ah_sort_key k{};
     if (IsInteger(id) || IsFloating(id)) {
       k.type = (int)id;
-      k.values = a.length ? dptr(1) : nullptr;
-    } else if (id == Type::STRING || id == Type::BINARY || id == Type::LARGE_STRING || id == Type::LARGE_BINARY) {  // :225-232
-      k.type = (id == Type::STRING || id == Type::BINARY) ? AH_BINARY : AH_LARGE_BINARY;
-      k.offsets = dptr(1);
-      k.values = dptr(2);
-    } else if (IsFixedWidthBinary(id)) {  // FixedSizeBinary :233-234, Decimal128 / 256 :213-216
-      k.type = (int)id;
-      k.values = dptr(1);
-      k.byte_width = a.type->bit_width / 8;
+      k.values = a.length && a.buffers[1] ? a.buffers[1]->dptr : nullptr;
+    } else if (IsBaseBinary(id) || IsFixedWidthBinary(id)) {  // binary :225-232, FixedSizeBinary :233-234, Decimal128 / 256 :213-216
+      const ByteLayout l = LayoutOf(a);
+      k.type = l.offset_width == 4 ? AH_BINARY : l.offset_width == 8 ? AH_LARGE_BINARY : (int)id;
+      k.offsets = l.offsets;
+      k.values = l.data;
+      k.byte_width = l.byte_width;
     } else {
       return Status::Make(StatusCode::NotImplemented, std::string("sorting not supported for type ") + a.type->name);  // :266-268
     }

@@ -62,6 +62,18 @@ RESOURCES = {
     # the one-pass cumulative_sum: a workgroup of 1024 lanes per CU = 128 registers, and nothing of the tile in scratch (a CSE of the
     # sixteen null masks across the look-back once spilled 21 … 49 registers and every parity test stayed green: DESIGN.md §3.4)
     "ah_scan.hip": [(r"scan_onepass_kernelI[jyt]Lb", 128, 16), (r"scan_onepass_f64_kernel", 128, 0)],
+    # the byte-row kernels: the budgets they had before their byte-row code moved into ah_bytes.h
+    "ah_compare_binary.hip": [(r"compare_bytes_kernelILi4ELi4E", 50, 0), (r"compare_decimal_kernelILi16ELi16E", 42, 0)],
+    "ah_setlookup_binary.hip": [
+        (r"is_in_bytes_kernelILi[048]ELi1E", 81, 0),
+        (r"is_in_bytes_kernelILi[048]ELi2E", 58, 0),
+        (r"is_in_bytes_kernelILi[048]ELi3E", 97, 0),
+    ],
+    "ah_sort_binary.hip": [
+        (r"round_keys_kernel", 23, 0),
+        (r"hist_kernelINS_9BinColumnE", 18, 0),
+        (r"scatter_kernelINS_9BinColumnE", 97, 0),
+    ],
 }
 
 
