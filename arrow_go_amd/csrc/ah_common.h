@@ -374,3 +374,11 @@ __device__ __forceinline__ void put_word(uint8_t* __restrict__ out, int64_t out_
   if (aligned && cnt == 64) *(unsigned long long*)(out + (out_off + chunk * 64) / 8) = word;
   else put_bits(out, out_off + chunk * 64, word, cnt);
 }
+
+// The ballot of 64-row chunk `chunk` of a column of n rows into a bitmap that starts at row 0 (the output of a kernel that owns
+// whole chunks): the chunk's eight bytes, at the column's tail only those that hold a row.
+__device__ __forceinline__ void put_chunk_bytes(uint8_t* __restrict__ bm, int64_t chunk, int64_t n, unsigned long long word) {
+  const int64_t left = n - chunk * 64;
+  const int nbytes = left >= 64 ? 8 : (int)((left + 7) >> 3);
+  for (int b = 0; b < nbytes; b++) bm[chunk * 8 + b] = (uint8_t)(word >> (8 * b));
+}

@@ -29,7 +29,7 @@
 // Algorithmic bytes per input row (w = 8): 8 + 1/8 (+1/8 with value validity) read,
 // 8·s (+ s/8) written for selectivity s.
 #include <chrono>
-#include "ah_common.h"
+#include "ah_index.h"
 
 namespace {
 
@@ -40,11 +40,6 @@ constexpr int kBlock = 256;
 constexpr int kTileBytesMax = AH_FILTER_TILE_BYTES;  // values staged per workgroup (W = 1 is capped at 16 KiB: one lane per mask word)
 template <int W> constexpr int TileBytes() { return (W == 1 && kTileBytesMax > 16384) ? 16384 : kTileBytesMax; }
 
-template <int W> struct UIntOf;
-template <> struct UIntOf<1> { using type = uint8_t; };
-template <> struct UIntOf<2> { using type = uint16_t; };
-template <> struct UIntOf<4> { using type = uint32_t; };
-template <> struct UIntOf<8> { using type = uint64_t; };
 
 // selection word for 64 consecutive rows starting at row `pos` (cnt valid rows):
 //   DROP: data ∧ valid          EMIT: data ∨ ¬valid  (vector_selection.go:66-77)

@@ -17,8 +17,7 @@
 // granularity.  One output row per lane per step, kUnroll independent gathers in
 // flight per lane; index loads and value stores are fully coalesced; the output
 // validity word for 64 rows is one wave ballot, stored by lane 0.
-#include <type_traits>
-#include "ah_common.h"
+#include "ah_index.h"
 
 namespace {
 
@@ -28,16 +27,6 @@ constexpr int kBlock = 256;
 #endif
 constexpr int kUnroll = AH_TAKE_UNROLL;
 
-template <int W> struct UIntOf;
-template <> struct UIntOf<1> { using type = uint8_t; };
-template <> struct UIntOf<2> { using type = uint16_t; };
-template <> struct UIntOf<4> { using type = uint32_t; };
-template <> struct UIntOf<8> { using type = uint64_t; };
-// 16- and 32-byte values — Decimal128 / Decimal256 and FixedSizeBinary of those widths (FSBImpl, vector_selection.go:1997, takes any
-// width byte by byte; here the widths that are whole 16-byte accesses): moved as 2 / 4 × 64-bit vectors, the plain gather kernel only
-template <> struct UIntOf<16> { using type = unsigned long long __attribute__((ext_vector_type(2))); };
-template <> struct UIntOf<32> { using type = unsigned long long __attribute__((ext_vector_type(4))); };
-
 // NT: the index vector and the output are streamed once — nontemporal, so that they do not push the gathered values' lines out of L2
 template <int W, typename IdxT, bool HAS_VALID, bool NT>
 __global__ __launch_bounds__(kBlock) void take_kernel(const void* __restrict__ values_v, const uint8_t* __restrict__ vvalid, int64_t voff,
@@ -45,7 +34,6 @@ __global__ __launch_bounds__(kBlock) void take_kernel(const void* __restrict__ v
                                                        int64_t ioff, int64_t nidx, void* __restrict__ out_v, uint8_t* __restrict__ out_valid,
                                                        unsigned long long* __restrict__ first_bad, unsigned long long* __restrict__ valid_total) {
   using T = typename UIntOf<W>::type;
-  using UIdx = typename std::make_unsigned<IdxT>::type;
   const T* __restrict__ values = (const T*)values_v;
   T* __restrict__ out = (T*)out_v;
   const int lane = threadIdx.x & 63;
@@ -74,10 +62,9 @@ __global__ __launch_bounds__(kBlock) void take_kernel(const void* __restrict__ v
       ok[k] = false;
       u[k] = 0;
       if (i < nidx && ((ib[k] >> ((ioff + i) & 7)) & 1)) {
-        const IdxT s = raw[k];
-        u[k] = (uint64_t)(UIdx)s;  // reinterpret as unsigned of the same width
-        bool oob = (std::is_signed<IdxT>::value && s < 0) || u[k] >= nvalues;  // helpers.go:937-939
-        if (oob) atomicMin(first_bad, (unsigned long long)i);
+        const IndexRef x = index_ref(raw[k], nvalues);
+        u[k] = x.u;
+        if (x.oob) atomicMin(first_bad, (unsigned long long)i);
         else ok[k] = true;
       }
     }
@@ -172,7 +159,6 @@ __global__ __launch_bounds__(kBlock) void take_vec_kernel(const void* __restrict
                                                            int64_t ioff, int64_t nidx, void* __restrict__ out_v, uint8_t* __restrict__ out_valid,
                                                            unsigned long long* __restrict__ first_bad) {
   using T = typename UIntOf<W>::type;
-  using UIdx = typename std::make_unsigned<IdxT>::type;
   constexpr int V = 16 / W;          // rows per lane (2 or 4)
   const int64_t vbytes = (voff + (int64_t)nvalues + 7) >> 3;   // bytes of the value validity bitmap
   constexpr bool nt_idx = NT & 1, nt_val = NT & 2, nt_out = NT & 4;   // (a run-time switch would be merged away: the two loads of one address fold into a plain one)
@@ -232,13 +218,13 @@ __global__ __launch_bounds__(kBlock) void take_vec_kernel(const void* __restrict
 #pragma unroll
       for (int j = 0; j < V; j++) {
         const IdxT s = iv[k].v[j];
-        u[k][j] = (uint64_t)(UIdx)s;   // reinterpret as unsigned of the same width
-        neg = neg || (std::is_signed<IdxT>::value && s < 0);
+        const IndexRef x = index_ref(s, nvalues);
+        u[k][j] = x.u;
+        neg = neg || (std::is_signed<IdxT>::value && s < 0);   // (of EVERY slot, null ones included: a window needs all V in range)
         mn = u[k][j] < mn ? u[k][j] : mn;
         mx = u[k][j] > mx ? u[k][j] : mx;
         if ((ibits[k] >> j) & 1u) {
-          const bool oob = (std::is_signed<IdxT>::value && s < 0) || u[k][j] >= nvalues;   // helpers.go:937-939
-          if (oob) atomicMin(first_bad, (unsigned long long)(r + j));
+          if (x.oob) atomicMin(first_bad, (unsigned long long)(r + j));
           else okb[k] |= 1u << j;
         }
       }
@@ -368,21 +354,6 @@ int launch_take(ah_ctx* c, const void* values, const uint8_t* vvalid, int64_t vo
   return AH_OK;
 }
 
-template <int W>
-int dispatch_idx(ah_ctx* c, int iw, int is_signed, const void* values, const uint8_t* vvalid, int64_t voff, int64_t nvalues,
-                 const void* idx, const uint8_t* ivalid, int64_t ioff, int64_t nidx, void* out_values, uint8_t* out_valid,
-                 unsigned long long* first_bad, unsigned long long* valid_total) {
-#define AH_TAKE(IT) return launch_take<W, IT>(c, values, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_values, out_valid, first_bad, valid_total)
-  switch (iw) {
-    case 1: if (is_signed) AH_TAKE(int8_t); else AH_TAKE(uint8_t);
-    case 2: if (is_signed) AH_TAKE(int16_t); else AH_TAKE(uint16_t);
-    case 4: if (is_signed) AH_TAKE(int32_t); else AH_TAKE(uint32_t);
-    case 8: if (is_signed) AH_TAKE(int64_t); else AH_TAKE(uint64_t);
-  }
-#undef AH_TAKE
-  return ah_fail(c, AH_EINDEX, "invalid indices byte width");  // vector_selection.go:1157
-}
-
 // Boolean values (booleanTakeImpl, vector_selection.go:990-1074): out data bit i = value bit idx[i],
 // validity as for the other widths; a null output keeps data bit 0 (fresh zeroed buffer in the
 // reference).  64 rows per wave step, both output words come from ballots.
@@ -391,29 +362,15 @@ __global__ __launch_bounds__(kBlock) void take_bool_kernel(const uint8_t* __rest
                                                             uint64_t nvalues, const IdxT* __restrict__ idx, const uint8_t* __restrict__ ivalid,
                                                             int64_t ioff, int64_t nidx, uint8_t* __restrict__ out_data,
                                                             uint8_t* __restrict__ out_valid, unsigned long long* __restrict__ first_bad) {
-  using UIdx = typename std::make_unsigned<IdxT>::type;
-  const int lane = threadIdx.x & 63;
-  const int64_t nchunks = (nidx + 63) >> 6;
-  const int64_t wave_stride = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t c = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); c < nchunks; c += wave_stride) {
-    const int64_t i = c * 64 + lane;
-    bool ok = false, bit = false;
-    if (i < nidx && ah_bit(ivalid, ioff + i)) {
-      const IdxT s = idx[i];
-      const uint64_t u = (uint64_t)(UIdx)s;
-      if ((std::is_signed<IdxT>::value && s < 0) || u >= nvalues) atomicMin(first_bad, (unsigned long long)i);
-      else if (ah_bit(vvalid, voff + (int64_t)u)) { ok = true; bit = ah_bit(data, voff + (int64_t)u); }
+  for_wave_chunks<kBlock>(nidx, [&](int64_t c, int64_t i) {
+    const LaneIndex x = lane_index(idx, ivalid, ioff, i, nidx, vvalid, voff, nvalues, first_bad);
+    const bool bit = x.ok && ah_bit(data, voff + (int64_t)x.u);
+    const unsigned long long dword = __ballot(bit), vword = __ballot(x.ok);
+    if (ah_lane() == 0) {
+      put_chunk_bytes(out_data, c, nidx, dword);
+      if (out_valid) put_chunk_bytes(out_valid, c, nidx, vword);
     }
-    const unsigned long long dword = __ballot(ok && bit), vword = __ballot(ok);
-    if (lane == 0) {
-      const int64_t left = nidx - c * 64;
-      const int nbytes = left >= 64 ? 8 : (int)((left + 7) >> 3);
-      for (int b = 0; b < nbytes; b++) {
-        out_data[c * 8 + b] = (uint8_t)(dword >> (8 * b));
-        if (out_valid) out_valid[c * 8 + b] = (uint8_t)(vword >> (8 * b));
-      }
-    }
-  }
+  });
 }
 
 // Slots of ANY byte width (FSBImpl, vector_selection.go:1997-2031: `copy(buf, valueData[start:start+valueSize])` per row) — what the
@@ -424,32 +381,16 @@ __global__ __launch_bounds__(kBlock) void take_bytes_kernel(int w, const uint8_t
                                                              uint64_t nvalues, const IdxT* __restrict__ idx, const uint8_t* __restrict__ ivalid,
                                                              int64_t ioff, int64_t nidx, uint8_t* __restrict__ out, uint8_t* __restrict__ out_valid,
                                                              unsigned long long* __restrict__ first_bad) {
-  using UIdx = typename std::make_unsigned<IdxT>::type;
-  const int lane = threadIdx.x & 63;
-  const int64_t nchunks = (nidx + 63) >> 6;
-  const int64_t wave_stride = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t c = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); c < nchunks; c += wave_stride) {
-    const int64_t i = c * 64 + lane;
-    bool ok = false;
-    uint64_t u = 0;
-    if (i < nidx && ah_bit(ivalid, ioff + i)) {
-      const IdxT s = idx[i];
-      u = (uint64_t)(UIdx)s;
-      if ((std::is_signed<IdxT>::value && s < 0) || u >= nvalues) atomicMin(first_bad, (unsigned long long)i);   // helpers.go:937-939
-      else ok = ah_bit(vvalid, voff + (int64_t)u);
-    }
+  for_wave_chunks<kBlock>(nidx, [&](int64_t c, int64_t i) {
+    const LaneIndex x = lane_index(idx, ivalid, ioff, i, nidx, vvalid, voff, nvalues, first_bad);
     if (i < nidx) {
       uint8_t* dst = out + i * (int64_t)w;
-      const uint8_t* src = values + u * (uint64_t)w;
-      for (int b = 0; b < w; b++) dst[b] = ok ? src[b] : (uint8_t)0;   // a null output keeps the zero of a fresh buffer
+      const uint8_t* src = values + x.u * (uint64_t)w;
+      for (int b = 0; b < w; b++) dst[b] = x.ok ? src[b] : (uint8_t)0;   // a null output keeps the zero of a fresh buffer
     }
-    const unsigned long long vword = __ballot(ok);
-    if (out_valid && lane == 0) {
-      const int64_t left = nidx - c * 64;
-      const int nbytes = left >= 64 ? 8 : (int)((left + 7) >> 3);
-      for (int b = 0; b < nbytes; b++) out_valid[c * 8 + b] = (uint8_t)(vword >> (8 * b));
-    }
-  }
+    const unsigned long long vword = __ballot(x.ok);
+    if (out_valid && ah_lane() == 0) put_chunk_bytes(out_valid, c, nidx, vword);
+  });
 }
 
 // *_dev flavour: {position of the first offending index or UINT64_MAX, output null count} stay in device memory
@@ -503,8 +444,9 @@ namespace {
 int take_primitive_core(ah_ctx* c, int byte_width, const void* values, const uint8_t* vvalid, int64_t voff, int64_t nvalues, int idx_byte_width,
                         int idx_signed, const void* idx, const uint8_t* ivalid, int64_t ioff, int64_t nidx, void* out_values, uint8_t* out_valid,
                         int64_t* out_null_count_host, int64_t* bad_index_host, uint64_t* status_dev) {
-  if (nidx < 0 || nvalues < 0 || voff < 0 || ioff < 0) return ah_fail(c, AH_EINVALID, "take: negative length/offset");
-  if (out_null_count_host) *out_null_count_host = 0;
+  int rc = take_enter(c, nidx, nvalues, voff, ioff, nidx == 0 || (idx && out_values && (values || nvalues == 0)), out_valid, &vvalid, &ivalid,
+                      out_null_count_host);
+  if (rc != AH_OK) return rc;
   if (nidx == 0) {
     if (status_dev) {
       AH_HIP(c, hipMemsetAsync(status_dev, 0xFF, 8, c->stream));
@@ -512,18 +454,11 @@ int take_primitive_core(ah_ctx* c, int byte_width, const void* values, const uin
     }
     return AH_OK;
   }
-  if (!idx || !out_values || (!values && nvalues > 0)) return ah_fail(c, AH_EINVALID, "take: null buffer");
-  if (!out_valid && (vvalid || ivalid)) {
-    // the caller decided there are no nulls (PrimitiveTake :1176 uses the null COUNTS);
-    // validity inputs are then ignored exactly like the reference's no-null path
-    vvalid = nullptr;
-    ivalid = nullptr;
-  }
   unsigned long long* first_bad = (unsigned long long*)&c->dscalars[1];
   unsigned long long* valid_total = (unsigned long long*)&c->dscalars[2];
   take_prep_kernel<<<1, 1, 0, c->stream>>>(first_bad, valid_total, (unsigned long long*)&c->dscalars[3]);
   AH_LAUNCH_CHECK(c);
-  int rc, binned = 0;
+  int binned = 0;
   c->take_clustered_hint = c->opt_take_vec == 2;
   // random indices into a column beyond the caches: bin → gather in L2-sized windows → unpermute (ah_take_binned.hip)
   rc = ah_take_binned_try(c, byte_width, values, vvalid, voff, nvalues, idx_byte_width, idx_signed, idx, ivalid, ioff, nidx, out_values, out_valid,
@@ -532,26 +467,20 @@ int take_primitive_core(ah_ctx* c, int byte_width, const void* values, const uin
   // 16- and 32-byte slots move as 16-byte vectors: a buffer that is only 8-byte aligned (a sliced FixedSizeBinary / Decimal column, a
   // zero-copy import) takes the arbitrary-width kernel instead of relying on the hardware's unaligned-access mode
   const bool wide_misaligned = (byte_width == 16 || byte_width == 32) && ((((uintptr_t)values) | ((uintptr_t)out_values)) & 15) != 0;
-  if (!binned) switch (wide_misaligned ? 0 : byte_width) {
-    case 1: rc = dispatch_idx<1>(c, idx_byte_width, idx_signed, values, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_values, out_valid, first_bad, valid_total); break;
-    case 2: rc = dispatch_idx<2>(c, idx_byte_width, idx_signed, values, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_values, out_valid, first_bad, valid_total); break;
-    case 4: rc = dispatch_idx<4>(c, idx_byte_width, idx_signed, values, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_values, out_valid, first_bad, valid_total); break;
-    case 8: rc = dispatch_idx<8>(c, idx_byte_width, idx_signed, values, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_values, out_valid, first_bad, valid_total); break;
-    case 16: rc = dispatch_idx<16>(c, idx_byte_width, idx_signed, values, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_values, out_valid, first_bad, valid_total); break;
-    case 32: rc = dispatch_idx<32>(c, idx_byte_width, idx_signed, values, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_values, out_valid, first_bad, valid_total); break;
-    default: {
-      if (byte_width < 1 || byte_width > 4096) return ah_fail(c, AH_EINVALID, "invalid values byte width for take");  // :1189
+  if (!binned) {
+    if (byte_width < 1 || byte_width > 4096) return ah_fail(c, AH_EINVALID, "invalid values byte width for take");  // :1189
+    const bool known = with_index_type(idx_byte_width, idx_signed, [&](auto it) {
+      using IdxT = typename decltype(it)::type;
+      const bool slot = with_value_width<1, 2, 4, 8, 16, 32>(wide_misaligned ? 0 : byte_width, [&](auto w) {
+        rc = launch_take<decltype(w)::value, IdxT>(c, values, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_values, out_valid, first_bad, valid_total);
+      });
+      if (slot) return;
       const unsigned grid = ah_stream_grid(c, ah_ceil_div(ah_ceil_div(nidx, 64), kBlock / 64), 8);
-#define AH_TBY(IT) take_bytes_kernel<IT><<<grid, kBlock, 0, c->stream>>>(byte_width, (const uint8_t*)values, vvalid, voff, (uint64_t)nvalues, (const IT*)idx, ivalid, ioff, nidx, (uint8_t*)out_values, out_valid, first_bad); break
-      switch (idx_byte_width * 2 + (idx_signed ? 1 : 0)) {
-        case 2: AH_TBY(uint8_t); case 3: AH_TBY(int8_t); case 4: AH_TBY(uint16_t); case 5: AH_TBY(int16_t);
-        case 8: AH_TBY(uint32_t); case 9: AH_TBY(int32_t); case 16: AH_TBY(uint64_t); case 17: AH_TBY(int64_t);
-        default: return ah_fail(c, AH_EINDEX, "invalid indices byte width");
-      }
-#undef AH_TBY
-      AH_LAUNCH_CHECK(c);
-      rc = AH_OK;
-    }
+      take_bytes_kernel<IdxT><<<grid, kBlock, 0, c->stream>>>(byte_width, (const uint8_t*)values, vvalid, voff, (uint64_t)nvalues, (const IdxT*)idx, ivalid, ioff,
+                                                              nidx, (uint8_t*)out_values, out_valid, first_bad);
+    });
+    if (!known) return ah_fail(c, AH_EINDEX, "invalid indices byte width");  // vector_selection.go:1157
+    AH_LAUNCH_CHECK(c);
   }
   if (rc != AH_OK) return rc;
   if (status_dev) {   // no round trip: the caller looks at the two words when (and if) it wants to
@@ -569,21 +498,7 @@ int take_primitive_core(ah_ctx* c, int byte_width, const void* values, const uin
   } else if ((rc = ah_mailbox_read(c, (const unsigned long long*)&c->dscalars[1], 2, (unsigned long long*)c->pinned)) != AH_OK) return rc;
   uint64_t bad_pos = *(volatile uint64_t*)&c->pinned[0];
   uint64_t nvalid = *(volatile uint64_t*)&c->pinned[1];
-  if (bad_pos != ~0ull) {
-    // fetch the offending index value for the message ("%d out of bounds", helpers.go:950)
-    uint64_t raw = 0;
-    AH_HIP(c, hipMemcpy(&raw, (const uint8_t*)idx + bad_pos * (uint64_t)idx_byte_width, (size_t)idx_byte_width, hipMemcpyDeviceToHost));
-    int64_t val;
-    switch (idx_byte_width) {
-      case 1: val = idx_signed ? (int64_t)(int8_t)raw : (int64_t)(uint8_t)raw; break;
-      case 2: val = idx_signed ? (int64_t)(int16_t)raw : (int64_t)(uint16_t)raw; break;
-      case 4: val = idx_signed ? (int64_t)(int32_t)raw : (int64_t)(uint32_t)raw; break;
-      default: val = (int64_t)raw; break;
-    }
-    if (bad_index_host) *bad_index_host = val;
-    if (idx_signed || idx_byte_width < 8) return ah_fail(c, AH_EINDEX, "%lld out of bounds", (long long)val);
-    return ah_fail(c, AH_EINDEX, "%llu out of bounds", (unsigned long long)raw);
-  }
+  if (bad_pos != ~0ull) return take_fail_bad_index(c, idx, idx_byte_width, idx_signed, bad_pos, bad_index_host);
   if (out_null_count_host) *out_null_count_host = out_valid ? nidx - (int64_t)nvalid : 0;
   take_leave_hint(c, idx, byte_width, nidx, out_values, out_valid);
   return AH_OK;
@@ -596,45 +511,25 @@ AH_EXPORT int ah_take_boolean(ah_ctx* c, const uint8_t* data, const uint8_t* vva
                               uint8_t* out_data, uint8_t* out_valid, int64_t* out_null_count_host, int64_t* bad_index_host) {
   AH_ENTER(c);
   (void)bounds_check;
-  if (nidx < 0 || nvalues < 0 || voff < 0 || ioff < 0) return ah_fail(c, AH_EINVALID, "take: negative length/offset");
-  if (out_null_count_host) *out_null_count_host = 0;
-  if (nidx == 0) return AH_OK;
-  if (!idx || !out_data || (!data && nvalues > 0)) return ah_fail(c, AH_EINVALID, "take: null buffer");
-  if (!out_valid && (vvalid || ivalid)) { vvalid = nullptr; ivalid = nullptr; }
+  int rc = take_enter(c, nidx, nvalues, voff, ioff, nidx == 0 || (idx && out_data && (data || nvalues == 0)), out_valid, &vvalid, &ivalid,
+                      out_null_count_host);
+  if (rc != AH_OK || nidx == 0) return rc;
   unsigned long long* first_bad = (unsigned long long*)&c->dscalars[1];
   unsigned long long* valid_total = (unsigned long long*)&c->dscalars[2];
   AH_HIP(c, hipMemsetAsync(first_bad, 0xFF, sizeof(*first_bad), c->stream));
   AH_HIP(c, hipMemsetAsync(valid_total, 0, sizeof(*valid_total), c->stream));
   const unsigned grid = ah_stream_grid(c, ah_ceil_div(ah_ceil_div(nidx, 64), kBlock / 64), 8);
-#define AH_TB(IT) take_bool_kernel<IT><<<grid, kBlock, 0, c->stream>>>(data, vvalid, voff, (uint64_t)nvalues, (const IT*)idx, ivalid, ioff, nidx, out_data, out_valid, first_bad); break
-  switch (idx_byte_width * 2 + (idx_signed ? 1 : 0)) {
-    case 2: AH_TB(uint8_t); case 3: AH_TB(int8_t); case 4: AH_TB(uint16_t); case 5: AH_TB(int16_t);
-    case 8: AH_TB(uint32_t); case 9: AH_TB(int32_t); case 16: AH_TB(uint64_t); case 17: AH_TB(int64_t);
-    default: return ah_fail(c, AH_EINDEX, "invalid indices byte width");
-  }
-#undef AH_TB
+  const bool known = with_index_type(idx_byte_width, idx_signed, [&](auto it) {
+    using IdxT = typename decltype(it)::type;
+    take_bool_kernel<IdxT><<<grid, kBlock, 0, c->stream>>>(data, vvalid, voff, (uint64_t)nvalues, (const IdxT*)idx, ivalid, ioff, nidx, out_data, out_valid, first_bad);
+  });
+  if (!known) return ah_fail(c, AH_EINDEX, "invalid indices byte width");
   AH_LAUNCH_CHECK(c);
-  if (out_valid && out_null_count_host) {
-    int rc = ah_popcount_async(c, out_valid, 0, nidx, valid_total);
-    if (rc != AH_OK) return rc;
-  }
-  { int mrc = ah_mailbox_read(c, (const unsigned long long*)&c->dscalars[1], 2, (unsigned long long*)c->pinned); if (mrc != AH_OK) return mrc; }
+  if (out_valid && out_null_count_host && (rc = ah_popcount_async(c, out_valid, 0, nidx, valid_total)) != AH_OK) return rc;
+  if ((rc = ah_mailbox_read(c, (const unsigned long long*)&c->dscalars[1], 2, (unsigned long long*)c->pinned)) != AH_OK) return rc;
   const uint64_t bad_pos = *(volatile uint64_t*)&c->pinned[0];
   const uint64_t nvalid = *(volatile uint64_t*)&c->pinned[1];
-  if (bad_pos != ~0ull) {
-    uint64_t raw = 0;
-    AH_HIP(c, hipMemcpy(&raw, (const uint8_t*)idx + bad_pos * (uint64_t)idx_byte_width, (size_t)idx_byte_width, hipMemcpyDeviceToHost));
-    int64_t val;
-    switch (idx_byte_width) {
-      case 1: val = idx_signed ? (int64_t)(int8_t)raw : (int64_t)(uint8_t)raw; break;
-      case 2: val = idx_signed ? (int64_t)(int16_t)raw : (int64_t)(uint16_t)raw; break;
-      case 4: val = idx_signed ? (int64_t)(int32_t)raw : (int64_t)(uint32_t)raw; break;
-      default: val = (int64_t)raw; break;
-    }
-    if (bad_index_host) *bad_index_host = val;
-    if (idx_signed || idx_byte_width < 8) return ah_fail(c, AH_EINDEX, "%lld out of bounds", (long long)val);
-    return ah_fail(c, AH_EINDEX, "%llu out of bounds", (unsigned long long)raw);
-  }
+  if (bad_pos != ~0ull) return take_fail_bad_index(c, idx, idx_byte_width, idx_signed, bad_pos, bad_index_host);
   if (out_null_count_host) *out_null_count_host = out_valid ? nidx - (int64_t)nvalid : 0;
   return AH_OK;
 }

@@ -22,8 +22,7 @@
 // observed dispatch rule; only speed depends on it) so that the runs neighbouring tiles append to a bin merge into
 // whole lines in that XCD's L2 before they are written back.
 // The in-run order of records depends on LDS atomic timing; the OUTPUT does not (each record carries its row).
-#include <type_traits>
-#include "ah_common.h"
+#include "ah_index.h"
 #include "ah_bins.h"
 
 namespace {
@@ -34,12 +33,6 @@ constexpr int kRowsPerThread = kTile / kThreads;  // 8 = two runs of 4 consecuti
 constexpr int kGatherBlock = 256;
 constexpr int kGatherPerThread = 8;
 constexpr int kGatherChunk = kGatherBlock * kGatherPerThread;  // 2048 records per workgroup
-
-template <int W> struct UIntW;
-template <> struct UIntW<1> { using type = uint8_t; };
-template <> struct UIntW<2> { using type = uint16_t; };
-template <> struct UIntW<4> { using type = uint32_t; };
-template <> struct UIntW<8> { using type = uint64_t; };
 
 // the tile's index slots of one thread: kGroups runs of 4 consecutive rows, each run ONE vector load (16 bytes for int32
 // indices) — all of them issued before anything is used, so a workgroup has its whole 32 KiB of indices in flight at once.
@@ -56,7 +49,6 @@ template <typename IdxT, int THREADS, int ROWS, bool FULL, bool HAS_IV>
 __device__ __forceinline__ void load_tile_indices(const IdxT* __restrict__ idx, const uint8_t* __restrict__ ivalid, int64_t ioff, int64_t base,
                                                    int64_t nidx, uint64_t nvalues, unsigned (&u)[ROWS], bool (&live)[ROWS],
                                                    unsigned long long* first_oob) {
-  using UIdx = typename std::make_unsigned<IdxT>::type;
   constexpr int GROUPS = ROWS / 4;
   IdxVec4<IdxT> raw[GROUPS];
   unsigned vbits[GROUPS];
@@ -82,14 +74,12 @@ __device__ __forceinline__ void load_tile_indices(const IdxT* __restrict__ idx, 
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const int k = g * 4 + j;
-      const IdxT s = raw[g].v[j];
-      const uint64_t w = (uint64_t)(UIdx)s;
+      const IndexRef x = index_ref(raw[g].v[j], nvalues);
       const bool valid = (vbits[g] >> j) & 1u;     // in range of the column AND a non-null index slot
-      const bool oob = (std::is_signed<IdxT>::value && s < 0) || w >= nvalues;  // helpers.go:937-939
       const int64_t row = base + (int64_t)g * 4 * THREADS + 4 * (int64_t)threadIdx.x + j;
       live[k] = FULL ? true : (row < nidx);
-      u[k] = valid ? (oob ? 0u : (unsigned)w) : (HAS_IV ? (((unsigned)row * 2654435761u) >> 1) >> (31 - lgv) : 0u);
-      any_oob |= valid && oob;
+      u[k] = valid ? (x.oob ? 0u : (unsigned)x.u) : (HAS_IV ? (((unsigned)row * 2654435761u) >> 1) >> (31 - lgv) : 0u);
+      any_oob |= valid && x.oob;
     }
   }
   *first_oob = ~0ull;
@@ -98,9 +88,7 @@ __device__ __forceinline__ void load_tile_indices(const IdxT* __restrict__ idx, 
     for (int g = GROUPS - 1; g >= 0; g--) {
 #pragma unroll
       for (int j = 3; j >= 0; j--) {
-        const IdxT s = raw[g].v[j];
-        const uint64_t w = (uint64_t)(UIdx)s;
-        if (((vbits[g] >> j) & 1u) && ((std::is_signed<IdxT>::value && s < 0) || w >= nvalues))
+        if (((vbits[g] >> j) & 1u) && index_ref(raw[g].v[j], nvalues).oob)
           *first_oob = (unsigned long long)(base + (int64_t)g * 4 * THREADS + 4 * (int64_t)threadIdx.x + j);
       }
     }
@@ -217,7 +205,7 @@ __global__ __launch_bounds__(kGatherBlock) void bin_gather_kernel(const void* __
                                                                   const unsigned* __restrict__ rec, const unsigned* __restrict__ binstart, int shift,
                                                                   int nb, int64_t nidx, int64_t nchunks, int seg_chunks, int ldmode,
                                                                   void* __restrict__ gval_v, unsigned long long* __restrict__ gvalid) {
-  using T = typename UIntW<W>::type;
+  using T = typename UIntOf<W>::type;
   const T* __restrict__ values = (const T*)values_v;
   T* __restrict__ gval = (T*)gval_v;
   __shared__ unsigned s_bs[kMaxBins + 1];
@@ -294,7 +282,7 @@ __global__ __launch_bounds__(kThreads) void bin_gather_lds_kernel(const void* __
                                                                    const unsigned* __restrict__ binstart, int shift, int nb, int64_t nidx,
                                                                    int64_t nunits, int seg_units, void* __restrict__ gval_v,
                                                                    unsigned long long* __restrict__ gvalid) {
-  using T = typename UIntW<W>::type;
+  using T = typename UIntOf<W>::type;
   const T* __restrict__ values = (const T*)values_v;
   T* __restrict__ gval = (T*)gval_v;
   __shared__ unsigned s_bs[kMaxBins + 1];
@@ -382,7 +370,7 @@ __global__ __launch_bounds__(kThreads) void unpermute_kernel(const void* __restr
                                                               const unsigned* __restrict__ toffs, int shift, int nb, int64_t ntiles, int64_t nidx,
                                                               const uint8_t* __restrict__ ivalid, int64_t ioff, void* __restrict__ out_v,
                                                               uint8_t* __restrict__ out_valid) {
-  using T = typename UIntW<W>::type;
+  using T = typename UIntOf<W>::type;
   const T* __restrict__ gval = (const T*)gval_v;
   T* __restrict__ out = (T*)out_v;
   __shared__ unsigned s_cnt[kMaxBins], s_start[kMaxBins], s_goff[kMaxBins], s_wsum[kThreads / 64];
@@ -569,13 +557,11 @@ int ah_take_binned_try(ah_ctx* c, int byte_width, const void* values, const uint
       c->take_hint_uses++;
     } else {
       AH_HIP(c, hipMemsetAsync(hits, 0, sizeof(*hits), c->stream));
-#define AH_S(IT) sample_kernel<IT><<<64, 256, 0, c->stream>>>((const IT*)idx, nidx, near, hits); break
-      switch (kind) {
-        case 2: AH_S(uint8_t); case 3: AH_S(int8_t); case 4: AH_S(uint16_t); case 5: AH_S(int16_t);
-        case 8: AH_S(uint32_t); case 9: AH_S(int32_t); case 16: AH_S(uint64_t); case 17: AH_S(int64_t);
-        default: return AH_OK;
-      }
-#undef AH_S
+      const bool known = with_index_type(iw, is_signed, [&](auto it) {
+        using IdxT = typename decltype(it)::type;
+        sample_kernel<IdxT><<<64, 256, 0, c->stream>>>((const IdxT*)idx, nidx, near, hits);
+      });
+      if (!known) return AH_OK;   // not used: the direct path reports the width
       AH_LAUNCH_CHECK(c);
       { int mrc = ah_mailbox_read(c, hits, 1, (unsigned long long*)&c->pinned[8]); if (mrc != AH_OK) return mrc; }
       word = *(volatile uint64_t*)&c->pinned[8];
@@ -606,21 +592,14 @@ int ah_take_binned_try(ah_ctx* c, int byte_width, const void* values, const uint
   unsigned* rec = (unsigned*)take((size_t)nidx * 4);
   void* gval = take((size_t)nidx * byte_width);
   unsigned long long* gvalid = (unsigned long long*)take((size_t)(nidx / 64 + 2) * 8);
-#define AH_F(IT) rc = run_front<IT>(c, p, idx, ivalid, ioff, nidx, nvalues, cnt_tm, toffs, gsum, binstart, rec, first_bad); break
-  switch (iw * 2 + (is_signed ? 1 : 0)) {
-    case 2: AH_F(uint8_t); case 3: AH_F(int8_t); case 4: AH_F(uint16_t); case 5: AH_F(int16_t);
-    case 8: AH_F(uint32_t); case 9: AH_F(int32_t); case 16: AH_F(uint64_t); case 17: AH_F(int64_t);
-    default: return AH_OK;
-  }
-#undef AH_F
+  const bool known = with_index_type(iw, is_signed, [&](auto it) {
+    rc = run_front<typename decltype(it)::type>(c, p, idx, ivalid, ioff, nidx, nvalues, cnt_tm, toffs, gsum, binstart, rec, first_bad);
+  });
+  if (!known) return AH_OK;   // not used: the direct path reports the width
   if (rc != AH_OK) return rc;
-  switch (byte_width) {
-    case 1: rc = run_back<1>(c, p, values, vvalid, voff, nvalues, ivalid, ioff, nidx, cnt_tm, toffs, binstart, rec, gval, gvalid, out_values, out_valid); break;
-    case 2: rc = run_back<2>(c, p, values, vvalid, voff, nvalues, ivalid, ioff, nidx, cnt_tm, toffs, binstart, rec, gval, gvalid, out_values, out_valid); break;
-    case 4: rc = run_back<4>(c, p, values, vvalid, voff, nvalues, ivalid, ioff, nidx, cnt_tm, toffs, binstart, rec, gval, gvalid, out_values, out_valid); break;
-    case 8: rc = run_back<8>(c, p, values, vvalid, voff, nvalues, ivalid, ioff, nidx, cnt_tm, toffs, binstart, rec, gval, gvalid, out_values, out_valid); break;
-    default: return AH_OK;
-  }
+  with_value_width<1, 2, 4, 8>(byte_width, [&](auto w) {   // (no other width gets here)
+    rc = run_back<decltype(w)::value>(c, p, values, vvalid, voff, nvalues, ivalid, ioff, nidx, cnt_tm, toffs, binstart, rec, gval, gvalid, out_values, out_valid);
+  });
   if (rc != AH_OK) return rc;
   *used = 1;
   return AH_OK;

@@ -21,14 +21,11 @@
 // the reference filters record batches (compute/selection.go:687).
 // Traffic: 2·w_off + w_idx read and w_off (+1/8) written per row in the first call (+ the scan's
 // 24 B/row), the value bytes once in and once out in the second.
-#include <type_traits>
-#include "ah_common.h"
+#include "ah_index.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-
-template <typename IdxT> __device__ __forceinline__ unsigned long long as_unsigned(IdxT v) { return (unsigned long long)(typename std::make_unsigned<IdxT>::type)v; }
 
 // lens[i] = byte length of output row i (0 for a null), validity word per 64 rows, first out-of-bounds position
 template <typename OffT, typename IdxT>
@@ -37,34 +34,14 @@ __global__ __launch_bounds__(kBlock) void lens_kernel(const OffT* __restrict__ o
                                                        const uint8_t* __restrict__ ivalid, int64_t ioff, int64_t n,
                                                        long long* __restrict__ lens, uint8_t* __restrict__ out_valid,
                                                        unsigned long long* __restrict__ first_bad) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nchunks = (n + 63) >> 6;
-  const int64_t wave_stride = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t c = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); c < nchunks; c += wave_stride) {
-    const int64_t i = c * 64 + lane;
-    bool ok = false;
-    long long len = 0;
-    if (i < n && ah_bit(ivalid, ioff + i)) {
-      const IdxT s = idx[i];
-      const unsigned long long u = as_unsigned<IdxT>(s);
-      if ((std::is_signed<IdxT>::value && s < 0) || u >= nvalues) {
-        atomicMin(first_bad, (unsigned long long)i);  // helpers.go:937-939: only valid index slots are checked
-      } else if (ah_bit(vvalid, voff + (int64_t)u)) {
-        ok = true;
-        len = (long long)offsets[voff + (int64_t)u + 1] - (long long)offsets[voff + (int64_t)u];
-      }
-    }
-    if (i < n) lens[i] = len;
+  for_wave_chunks<kBlock>(n, [&](int64_t c, int64_t i) {
+    const LaneIndex x = lane_index(idx, ivalid, ioff, i, n, vvalid, voff, nvalues, first_bad);
+    if (i < n) lens[i] = x.ok ? (long long)offsets[voff + (int64_t)x.u + 1] - (long long)offsets[voff + (int64_t)x.u] : 0;
     if (out_valid) {
-      const unsigned long long word = __ballot(ok);
-      if (lane == 0) {
-        const int64_t left = n - c * 64;
-        const int nbytes = left >= 64 ? 8 : (int)((left + 7) >> 3);
-        uint8_t* p = out_valid + c * 8;
-        for (int b = 0; b < nbytes; b++) p[b] = (uint8_t)(word >> (8 * b));
-      }
+      const unsigned long long word = __ballot(x.ok);
+      if (ah_lane() == 0) put_chunk_bytes(out_valid, c, n, word);
     }
-  }
+  });
 }
 
 // out_offsets[0] = 0, out_offsets[i + 1] = incl[i]; int32 offsets: flag an overflow
@@ -97,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void copy_kernel(const OffT* __restrict__ o
     if (i < n) {
       dst = (long long)out_offsets[i];
       len = (long long)out_offsets[i + 1] - dst;
-      if (len > 0) src = (long long)offsets[voff + (int64_t)as_unsigned<IdxT>(idx[i])];  // len > 0 ⇒ a valid, in-bounds slot
+      if (len > 0) src = (long long)offsets[voff + (int64_t)idx[i]];  // len > 0 ⇒ a valid, in-bounds slot (IdxT is unsigned)
     }
     // rows that have bytes, compacted into LDS in row order
     const unsigned long long todo = __ballot(len > 0);
@@ -138,32 +115,14 @@ int run_offsets(ah_ctx* c, const void* offsets, const uint8_t* vvalid, int64_t v
 }
 
 template <typename OffT>
-int offsets_idx(ah_ctx* c, int iw, int is_signed, const void* offsets, const uint8_t* vvalid, int64_t voff, int64_t nvalues, const void* idx,
-                const uint8_t* ivalid, int64_t ioff, int64_t n, void* out_offsets, uint8_t* out_valid, long long* lens, long long* incl) {
-#define AH_VL(IT) return run_offsets<OffT, IT>(c, offsets, vvalid, voff, nvalues, idx, ivalid, ioff, n, out_offsets, out_valid, lens, incl)
-  switch (iw) {
-    case 1: if (is_signed) AH_VL(int8_t); else AH_VL(uint8_t);
-    case 2: if (is_signed) AH_VL(int16_t); else AH_VL(uint16_t);
-    case 4: if (is_signed) AH_VL(int32_t); else AH_VL(uint32_t);
-    case 8: if (is_signed) AH_VL(int64_t); else AH_VL(uint64_t);
-  }
-#undef AH_VL
-  return ah_fail(c, AH_EINDEX, "invalid indices byte width");
-}
-
-template <typename OffT>
-int copy_idx(ah_ctx* c, int iw, const void* offsets, const uint8_t* data, int64_t voff, const void* idx, int64_t n, const void* out_offsets,
+int run_copy(ah_ctx* c, int iw, const void* offsets, const uint8_t* data, int64_t voff, const void* idx, int64_t n, const void* out_offsets,
              uint8_t* out_data) {
   const unsigned grid = ah_stream_grid(c, ah_ceil_div(ah_ceil_div(n, 64), kBlock / 64), 16);
-#define AH_CP(IT) copy_kernel<OffT, IT><<<grid, kBlock, 0, c->stream>>>((const OffT*)offsets, data, voff, (const IT*)idx, n, (const OffT*)out_offsets, out_data); break
-  switch (iw) {  // the unsigned reinterpretation is all the copy needs
-    case 1: AH_CP(uint8_t);
-    case 2: AH_CP(uint16_t);
-    case 4: AH_CP(uint32_t);
-    case 8: AH_CP(uint64_t);
-    default: return ah_fail(c, AH_EINDEX, "invalid indices byte width");
-  }
-#undef AH_CP
+  const bool known = with_index_type(iw, /*is_signed=*/0, [&](auto it) {
+    using IdxT = typename std::make_unsigned<typename decltype(it)::type>::type;   // the unsigned reinterpretation is all the copy needs
+    copy_kernel<OffT, IdxT><<<grid, kBlock, 0, c->stream>>>((const OffT*)offsets, data, voff, (const IdxT*)idx, n, (const OffT*)out_offsets, out_data);
+  });
+  if (!known) return ah_fail(c, AH_EINDEX, "invalid indices byte width");
   AH_LAUNCH_CHECK(c);
   return AH_OK;
 }
@@ -176,28 +135,29 @@ AH_EXPORT int ah_take_binary_offsets(ah_ctx* c, int offset_width, const void* of
                                      int64_t* out_total_bytes_host, int64_t* bad_index_host) {
   AH_ENTER(c);
   (void)bounds_check;  // fused and always on, like ah_take_primitive
-  if (nidx < 0 || nvalues < 0 || voff < 0 || ioff < 0) return ah_fail(c, AH_EINVALID, "take: negative length/offset");
-  if (offset_width != 4 && offset_width != 8) return ah_fail(c, AH_EINVALID, "take: binary offsets are 4 or 8 bytes wide");
-  if (out_null_count_host) *out_null_count_host = 0;
   if (out_total_bytes_host) *out_total_bytes_host = 0;
-  if (!out_offsets || !offsets) return ah_fail(c, AH_EINVALID, "take: null buffer");
+  int rc = take_enter(c, nidx, nvalues, voff, ioff, out_offsets && offsets && (nidx == 0 || idx), out_valid, &vvalid, &ivalid, out_null_count_host);
+  if (rc != AH_OK) return rc;
+  if (offset_width != 4 && offset_width != 8) return ah_fail(c, AH_EINVALID, "take: binary offsets are 4 or 8 bytes wide");
   if (nidx == 0) {  // a lone closing offset
     AH_HIP(c, hipMemsetAsync(out_offsets, 0, (size_t)offset_width, c->stream));
     return AH_OK;
   }
-  if (!idx) return ah_fail(c, AH_EINVALID, "take: null buffer");
-  if (!out_valid && (vvalid || ivalid)) { vvalid = nullptr; ivalid = nullptr; }  // the caller's null counts say: no nulls (:1176)
   // temporaries in the context's temp arena (the scan called below uses the scratch arena)
   const size_t col = (((size_t)nidx * 8) + 255) & ~(size_t)255;
   void* arena;
-  int rc = ah_temp_reserve(c, 2 * col, &arena);
+  rc = ah_temp_reserve(c, 2 * col, &arena);
   if (rc != AH_OK) return rc;
   long long* lens = (long long*)arena;
   long long* incl = (long long*)((uint8_t*)arena + col);
   AH_HIP(c, hipMemsetAsync(&c->dscalars[1], 0xFF, sizeof(uint64_t), c->stream));  // first bad position
   AH_HIP(c, hipMemsetAsync(&c->dscalars[2], 0, 2 * sizeof(uint64_t), c->stream)); // valid count, overflow flag
-  rc = offset_width == 4 ? offsets_idx<int32_t>(c, idx_byte_width, idx_signed, offsets, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_offsets, out_valid, lens, incl)
-                         : offsets_idx<int64_t>(c, idx_byte_width, idx_signed, offsets, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_offsets, out_valid, lens, incl);
+  const bool known = with_index_type(idx_byte_width, idx_signed, [&](auto it) {
+    using IdxT = typename decltype(it)::type;
+    rc = offset_width == 4 ? run_offsets<int32_t, IdxT>(c, offsets, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_offsets, out_valid, lens, incl)
+                           : run_offsets<int64_t, IdxT>(c, offsets, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_offsets, out_valid, lens, incl);
+  });
+  if (!known) return ah_fail(c, AH_EINDEX, "invalid indices byte width");
   if (rc != AH_OK) return rc;
   if (out_valid && out_null_count_host) {
     rc = ah_popcount_async(c, out_valid, 0, nidx, (unsigned long long*)&c->dscalars[2]);
@@ -210,20 +170,7 @@ AH_EXPORT int ah_take_binary_offsets(ah_ctx* c, int offset_width, const void* of
   const uint64_t nvalid = *(volatile uint64_t*)&c->pinned[1];
   const unsigned overflow = *(volatile unsigned*)&c->pinned[2];
   const int64_t total = *(volatile int64_t*)&c->pinned[3];
-  if (bad_pos != ~0ull) {
-    uint64_t raw = 0;
-    AH_HIP(c, hipMemcpy(&raw, (const uint8_t*)idx + bad_pos * (uint64_t)idx_byte_width, (size_t)idx_byte_width, hipMemcpyDeviceToHost));
-    int64_t val;
-    switch (idx_byte_width) {
-      case 1: val = idx_signed ? (int64_t)(int8_t)raw : (int64_t)(uint8_t)raw; break;
-      case 2: val = idx_signed ? (int64_t)(int16_t)raw : (int64_t)(uint16_t)raw; break;
-      case 4: val = idx_signed ? (int64_t)(int32_t)raw : (int64_t)(uint32_t)raw; break;
-      default: val = (int64_t)raw; break;
-    }
-    if (bad_index_host) *bad_index_host = val;
-    if (idx_signed || idx_byte_width < 8) return ah_fail(c, AH_EINDEX, "%lld out of bounds", (long long)val);
-    return ah_fail(c, AH_EINDEX, "%llu out of bounds", (unsigned long long)raw);
-  }
+  if (bad_pos != ~0ull) return take_fail_bad_index(c, idx, idx_byte_width, idx_signed, bad_pos, bad_index_host);
   if (overflow & 1u) return ah_fail(c, AH_EINVALID, "binary output offset overflow");  // :1245
   if (out_null_count_host) *out_null_count_host = out_valid ? nidx - (int64_t)nvalid : 0;
   if (out_total_bytes_host) *out_total_bytes_host = total;
@@ -237,6 +184,6 @@ AH_EXPORT int ah_take_binary_data(ah_ctx* c, int offset_width, const void* offse
   if (offset_width != 4 && offset_width != 8) return ah_fail(c, AH_EINVALID, "take: binary offsets are 4 or 8 bytes wide");
   if (nidx == 0) return AH_OK;
   if (!offsets || !idx || !out_offsets) return ah_fail(c, AH_EINVALID, "take: null buffer");
-  return offset_width == 4 ? copy_idx<int32_t>(c, idx_byte_width, offsets, data, voff, idx, nidx, out_offsets, out_data)
-                           : copy_idx<int64_t>(c, idx_byte_width, offsets, data, voff, idx, nidx, out_offsets, out_data);
+  return offset_width == 4 ? run_copy<int32_t>(c, idx_byte_width, offsets, data, voff, idx, nidx, out_offsets, out_data)
+                           : run_copy<int64_t>(c, idx_byte_width, offsets, data, voff, idx, nidx, out_offsets, out_data);
 }

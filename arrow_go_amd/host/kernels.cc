@@ -597,30 +597,73 @@ static Status ExecFilter(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
   return Status::OK();
 }
 
+// An index operand of a Take: the indices of an array, or the selection vector a filter turned into.
+struct IndexOperand {
+  int width = 4;
+  bool is_signed = false;
+  const void* data = nullptr;
+  const uint8_t* valid = nullptr;   // null: no null slots
+  int64_t offset = 0, len = 0, nulls = 0;
+  BufferPtr data_buf, valid_buf;    // (a filter's indices: their owner)
+};
+static IndexOperand IndexOperandOf(const ArraySpan& indices) {   // null count known (UpdateNullCount)
+  IndexOperand ix;
+  ix.width = indices.type->bit_width / 8;
+  ix.is_signed = IsSignedInteger(indices.type->id);
+  ix.data = Values(indices);
+  ix.valid = indices.MayHaveNulls() ? indices.buffers[0].buf : nullptr;
+  ix.offset = indices.offset;
+  ix.len = indices.len;
+  ix.nulls = indices.nulls;
+  return ix;
+}
+// GetTakeIndices (vector_selection.go:102-236): the filter's first `rows` slots as uint32 selection indices, null slots (EmitNulls)
+// with their validity.  A filter of `limit` rows or more is refused with the caller's words (:229-235).
+static Status FilterToIndices(Session* s, ArraySpan& filter, int64_t rows, const FilterOptions* opts, int64_t limit, const char* too_long,
+                              IndexOperand* ix) {
+  const int null_sel = opts ? (int)opts->NullSelection : DropNulls;
+  AHC_RETURN_NOT_OK(filter.UpdateNullCount(s));
+  if (rows >= limit) return Status::Make(StatusCode::NotImplemented, too_long);
+  const uint8_t* fvalid = filter.MayHaveNulls() ? filter.buffers[0].buf : nullptr;
+  if (rows > 0)
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_count(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, filter.len, null_sel, &ix->len)));
+  AHC_RETURN_NOT_OK(s->Allocate(ix->len * 4, &ix->data_buf));
+  AHC_RETURN_NOT_OK(s->AllocateBitmap(ix->len, &ix->valid_buf));
+  if (ix->len > 0)
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_to_indices(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, rows, null_sel, ix->len,
+                                                         (uint32_t*)ix->data_buf->dptr, (uint8_t*)ix->valid_buf->dptr, &ix->nulls)));
+  ix->data = ix->data_buf->dptr;
+  ix->valid = ix->nulls ? (const uint8_t*)ix->valid_buf->dptr : nullptr;
+  return Status::OK();
+}
+
 // PrimitiveTake (vector_selection.go:1162-1192)
-static Status ExecTake(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+static Status TakeFixedCommon(KernelCtx* k, const ArraySpan& values, const IndexOperand& ix, bool allocate_validity, int bounds_check, ExecResult* out) {
   Session* s = k->session;
-  ArraySpan values = b.values[0].array, indices = b.values[1].array;
-  const TakeOptions* opts = static_cast<const TakeOptions*>(k->state);
-  AHC_RETURN_NOT_OK(values.UpdateNullCount(s));
-  AHC_RETURN_NOT_OK(indices.UpdateNullCount(s));
-  if (values.type->bit_width == 1)
-    return Status::Make(StatusCode::NotImplemented, "boolean-valued take is outside the accelerated path");
-  int w = values.type->bit_width / 8, iw = indices.type->bit_width / 8;
-  bool allocate_validity = values.nulls != 0 || indices.nulls != 0;  // :1176
-  out->len = indices.len;
+  const int w = values.type->bit_width / 8;
+  out->len = ix.len;
   BufferPtr vb, db;
-  if (allocate_validity) { AHC_RETURN_NOT_OK(k->AllocateBitmap(indices.len, &vb)); out->buffers[0].WrapBuffer(vb); }
-  AHC_RETURN_NOT_OK(k->Allocate(indices.len * w, &db, /*zero_all=*/false));
+  if (allocate_validity) { AHC_RETURN_NOT_OK(k->AllocateBitmap(ix.len, &vb)); out->buffers[0].WrapBuffer(vb); }
+  AHC_RETURN_NOT_OK(k->Allocate(ix.len * w, &db, /*zero_all=*/false));
   out->buffers[1].WrapBuffer(db);
-  if (indices.len == 0) { out->nulls = 0; return Status::OK(); }
+  out->nulls = 0;
+  if (ix.len == 0) return Status::OK();
   int64_t nulls = 0, bad = 0;
   AHC_RETURN_NOT_OK(s->FromStatus(ah_take_primitive(
       s->ctx(), w, values.buffers[1].buf ? Values(values) : nullptr, values.MayHaveNulls() ? values.buffers[0].buf : nullptr, values.offset,
-      values.len, iw, IsSignedInteger(indices.type->id) ? 1 : 0, Values(indices), indices.MayHaveNulls() ? indices.buffers[0].buf : nullptr,
-      indices.offset, indices.len, opts ? (int)opts->BoundsCheck : 1, db->dptr, allocate_validity ? (uint8_t*)vb->dptr : nullptr, &nulls, &bad)));
+      values.len, ix.width, ix.is_signed ? 1 : 0, ix.data, ix.valid, ix.offset, ix.len, bounds_check, db->dptr,
+      allocate_validity ? (uint8_t*)vb->dptr : nullptr, &nulls, &bad)));
   out->nulls = allocate_validity ? nulls : 0;
   return Status::OK();
+}
+static Status ExecTake(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  ArraySpan values = b.values[0].array, indices = b.values[1].array;
+  const TakeOptions* opts = static_cast<const TakeOptions*>(k->state);
+  AHC_RETURN_NOT_OK(values.UpdateNullCount(k->session));
+  AHC_RETURN_NOT_OK(indices.UpdateNullCount(k->session));
+  if (values.type->bit_width == 1)
+    return Status::Make(StatusCode::NotImplemented, "boolean-valued take is outside the accelerated path");
+  return TakeFixedCommon(k, values, IndexOperandOf(indices), values.nulls != 0 || indices.nulls != 0 /* :1176 */, opts ? (int)opts->BoundsCheck : 1, out);
 }
 
 // FSBImpl (vector_selection.go:1997-2031; registered for FIXED_SIZE_BINARY, DECIMAL128 and DECIMAL256 at :2344-2346 / :2354-2356):
@@ -639,38 +682,15 @@ static Status ExecTakeFixed(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
 // the filter of wide slots goes through GetTakeIndices (vector_selection.go:102-236) and the take, like the binary and boolean
 // filters here: ah_filter_primitive's compaction is built for slots of at most 8 bytes
 static Status ExecFilterFixed(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
-  Session* s = k->session;
   ArraySpan values = b.values[0].array, filter = b.values[1].array;
   AHC_RETURN_NOT_OK(CheckSlotWidth(values));
   const int w = values.type->bit_width / 8;
   if (w == 1 || w == 2 || w == 4 || w == 8) return ExecFilter(k, b, out);
-  const FilterOptions* opts = static_cast<const FilterOptions*>(k->state);
-  int null_sel = opts ? (int)opts->NullSelection : DropNulls;
-  AHC_RETURN_NOT_OK(values.UpdateNullCount(s));
-  AHC_RETURN_NOT_OK(filter.UpdateNullCount(s));
-  if (values.len >= ((int64_t)1 << 32)) return Status::Make(StatusCode::NotImplemented, "filter of a fixed-size binary column with 2^32 rows or more");
-  const uint8_t* fvalid = filter.MayHaveNulls() ? filter.buffers[0].buf : nullptr;
-  int64_t n_out = 0;
-  if (values.len > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_count(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, filter.len, null_sel, &n_out)));
-  const bool allocate_validity = values.nulls != 0 || filter.nulls != 0;
-  out->len = n_out;
-  BufferPtr ib, ivb, vb, db;
-  AHC_RETURN_NOT_OK(k->Allocate(n_out * 4, &ib));
-  AHC_RETURN_NOT_OK(k->AllocateBitmap(n_out, &ivb));
-  if (allocate_validity) { AHC_RETURN_NOT_OK(k->AllocateBitmap(n_out, &vb)); out->buffers[0].WrapBuffer(vb); }
-  AHC_RETURN_NOT_OK(k->Allocate(n_out * w, &db, /*zero_all=*/false));
-  out->buffers[1].WrapBuffer(db);
-  out->nulls = 0;
-  if (n_out == 0) return Status::OK();
-  int64_t idx_nulls = 0, nulls = 0, bad = 0;
-  AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_to_indices(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, values.len, null_sel, n_out,
-                                                       (uint32_t*)ib->dptr, (uint8_t*)ivb->dptr, &idx_nulls)));
-  AHC_RETURN_NOT_OK(s->FromStatus(ah_take_primitive(s->ctx(), w, Values(values), values.MayHaveNulls() ? values.buffers[0].buf : nullptr, values.offset, values.len,
-                                                    4, 0, ib->dptr, idx_nulls ? (const uint8_t*)ivb->dptr : nullptr, 0, n_out, /*bounds_check=*/0, db->dptr,
-                                                    allocate_validity ? (uint8_t*)vb->dptr : nullptr, &nulls, &bad)));
-  out->nulls = allocate_validity ? nulls : 0;
-  return Status::OK();
+  AHC_RETURN_NOT_OK(values.UpdateNullCount(k->session));
+  IndexOperand ix;
+  AHC_RETURN_NOT_OK(FilterToIndices(k->session, filter, values.len, static_cast<const FilterOptions*>(k->state), (int64_t)1 << 32,
+                                    "filter of a fixed-size binary column with 2^32 rows or more", &ix));
+  return TakeFixedCommon(k, values, ix, values.nulls != 0 || filter.nulls != 0, /*bounds_check=*/0, out);
 }
 
 // dictionaryTake / dictionaryFilter (compute/selection.go:497-586): select the INDICES (int32 on the device), keep a pointer
@@ -692,23 +712,22 @@ static Status ExecFilterDictionary(KernelCtx* k, const ExecSpan& b, ExecResult* 
 }
 
 // VarBinaryImpl (vector_selection.go:1925-1992) under takeExec: offsets + validity + byte count, then the bytes
-static Status TakeBinaryCommon(KernelCtx* k, const ArraySpan& values, int idx_width, bool idx_signed, const void* idx, const uint8_t* ivalid,
-                               int64_t ioff, int64_t n, bool allocate_validity, ExecResult* out) {
+static Status TakeBinaryCommon(KernelCtx* k, const ArraySpan& values, const IndexOperand& ix, bool allocate_validity, ExecResult* out) {
   Session* s = k->session;
   const int ow = values.type->bit_width / 8;
-  out->len = n;
+  out->len = ix.len;
   BufferPtr vb, ob, db;
-  if (allocate_validity) { AHC_RETURN_NOT_OK(k->AllocateBitmap(n, &vb)); out->buffers[0].WrapBuffer(vb); }
-  AHC_RETURN_NOT_OK(k->Allocate((n + 1) * ow, &ob));
+  if (allocate_validity) { AHC_RETURN_NOT_OK(k->AllocateBitmap(ix.len, &vb)); out->buffers[0].WrapBuffer(vb); }
+  AHC_RETURN_NOT_OK(k->Allocate((ix.len + 1) * ow, &ob));
   out->buffers[1].WrapBuffer(ob);
   int64_t nulls = 0, total = 0, bad = 0;
   AHC_RETURN_NOT_OK(s->FromStatus(ah_take_binary_offsets(s->ctx(), ow, values.buffers[1].buf, values.MayHaveNulls() ? values.buffers[0].buf : nullptr,
-                                                         values.offset, values.len, idx_width, idx_signed, idx, ivalid, ioff, n, 1, ob->dptr,
+                                                         values.offset, values.len, ix.width, ix.is_signed, ix.data, ix.valid, ix.offset, ix.len, 1, ob->dptr,
                                                          allocate_validity ? (uint8_t*)vb->dptr : nullptr, &nulls, &total, &bad)));
   AHC_RETURN_NOT_OK(k->Allocate(total, &db, /*zero_all=*/false));
   out->buffers[2].WrapBuffer(db);
-  if (n > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_take_binary_data(s->ctx(), ow, values.buffers[1].buf, values.buffers[2].buf, values.offset, idx_width, idx, n,
+  if (ix.len > 0)
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_take_binary_data(s->ctx(), ow, values.buffers[1].buf, values.buffers[2].buf, values.offset, ix.width, ix.data, ix.len,
                                                         ob->dptr, (uint8_t*)db->dptr)));
   out->nulls = allocate_validity ? nulls : 0;
   return Status::OK();
@@ -718,47 +737,30 @@ static Status ExecTakeBinary(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
   ArraySpan values = b.values[0].array, indices = b.values[1].array;
   AHC_RETURN_NOT_OK(values.UpdateNullCount(k->session));
   AHC_RETURN_NOT_OK(indices.UpdateNullCount(k->session));
-  return TakeBinaryCommon(k, values, indices.type->bit_width / 8, IsSignedInteger(indices.type->id), Values(indices),
-                          indices.MayHaveNulls() ? indices.buffers[0].buf : nullptr, indices.offset, indices.len,
-                          values.nulls != 0 || indices.nulls != 0, out);
+  return TakeBinaryCommon(k, values, IndexOperandOf(indices), values.nulls != 0 || indices.nulls != 0, out);
 }
 
 // binaryFilterImpl (vector_selection.go:1650-1815) = GetTakeIndices (:102-236) + the var-length take
 static Status ExecFilterBinary(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
-  Session* s = k->session;
   ArraySpan values = b.values[0].array, filter = b.values[1].array;
-  const FilterOptions* opts = static_cast<const FilterOptions*>(k->state);
-  int null_sel = opts ? (int)opts->NullSelection : DropNulls;
-  AHC_RETURN_NOT_OK(values.UpdateNullCount(s));
-  AHC_RETURN_NOT_OK(filter.UpdateNullCount(s));
-  if (values.len >= ((int64_t)1 << 32)) return Status::Make(StatusCode::NotImplemented, "filter of a binary column with 2^32 rows or more");  // :229-235
-  const uint8_t* fvalid = filter.MayHaveNulls() ? filter.buffers[0].buf : nullptr;
-  int64_t n_out = 0;
-  if (values.len > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_count(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, filter.len, null_sel, &n_out)));
-  BufferPtr ib, ivb;
-  AHC_RETURN_NOT_OK(k->Allocate(n_out * 4, &ib));
-  AHC_RETURN_NOT_OK(k->AllocateBitmap(n_out, &ivb));
-  int64_t idx_nulls = 0;
-  if (n_out > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_to_indices(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, values.len, null_sel, n_out,
-                                                         (uint32_t*)ib->dptr, (uint8_t*)ivb->dptr, &idx_nulls)));
-  bool allocate_validity = values.nulls != 0 || filter.nulls != 0;
-  return TakeBinaryCommon(k, values, 4, false, ib->dptr, idx_nulls ? (const uint8_t*)ivb->dptr : nullptr, 0, n_out, allocate_validity, out);
+  AHC_RETURN_NOT_OK(values.UpdateNullCount(k->session));
+  IndexOperand ix;
+  AHC_RETURN_NOT_OK(FilterToIndices(k->session, filter, values.len, static_cast<const FilterOptions*>(k->state), (int64_t)1 << 32,
+                                    "filter of a binary column with 2^32 rows or more", &ix));
+  return TakeBinaryCommon(k, values, ix, values.nulls != 0 || filter.nulls != 0, out);
 }
 
 // booleanTakeImpl (vector_selection.go:990-1074) and, for filter, GetTakeIndices in front of it
-static Status TakeBooleanCommon(KernelCtx* k, const ArraySpan& values, int idx_width, bool idx_signed, const void* idx, const uint8_t* ivalid,
-                                int64_t ioff, int64_t n, bool allocate_validity, ExecResult* out) {
+static Status TakeBooleanCommon(KernelCtx* k, const ArraySpan& values, const IndexOperand& ix, bool allocate_validity, ExecResult* out) {
   Session* s = k->session;
-  out->len = n;
+  out->len = ix.len;
   BufferPtr vb, db;
-  if (allocate_validity) { AHC_RETURN_NOT_OK(k->AllocateBitmap(n, &vb)); out->buffers[0].WrapBuffer(vb); }
-  AHC_RETURN_NOT_OK(k->AllocateBitmap(n, &db));
+  if (allocate_validity) { AHC_RETURN_NOT_OK(k->AllocateBitmap(ix.len, &vb)); out->buffers[0].WrapBuffer(vb); }
+  AHC_RETURN_NOT_OK(k->AllocateBitmap(ix.len, &db));
   out->buffers[1].WrapBuffer(db);
   int64_t nulls = 0, bad = 0;
   AHC_RETURN_NOT_OK(s->FromStatus(ah_take_boolean(s->ctx(), values.buffers[1].buf, values.MayHaveNulls() ? values.buffers[0].buf : nullptr, values.offset,
-                                                  values.len, idx_width, idx_signed, idx, ivalid, ioff, n, 1, (uint8_t*)db->dptr,
+                                                  values.len, ix.width, ix.is_signed, ix.data, ix.valid, ix.offset, ix.len, 1, (uint8_t*)db->dptr,
                                                   allocate_validity ? (uint8_t*)vb->dptr : nullptr, &nulls, &bad)));
   out->nulls = allocate_validity ? nulls : 0;
   return Status::OK();
@@ -768,32 +770,16 @@ static Status ExecTakeBoolean(KernelCtx* k, const ExecSpan& b, ExecResult* out) 
   ArraySpan values = b.values[0].array, indices = b.values[1].array;
   AHC_RETURN_NOT_OK(values.UpdateNullCount(k->session));
   AHC_RETURN_NOT_OK(indices.UpdateNullCount(k->session));
-  return TakeBooleanCommon(k, values, indices.type->bit_width / 8, IsSignedInteger(indices.type->id), Values(indices),
-                           indices.MayHaveNulls() ? indices.buffers[0].buf : nullptr, indices.offset, indices.len,
-                           values.nulls != 0 || indices.nulls != 0, out);
+  return TakeBooleanCommon(k, values, IndexOperandOf(indices), values.nulls != 0 || indices.nulls != 0, out);
 }
 
 static Status ExecFilterBoolean(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
-  Session* s = k->session;
   ArraySpan values = b.values[0].array, filter = b.values[1].array;
-  const FilterOptions* opts = static_cast<const FilterOptions*>(k->state);
-  int null_sel = opts ? (int)opts->NullSelection : DropNulls;
-  AHC_RETURN_NOT_OK(values.UpdateNullCount(s));
-  AHC_RETURN_NOT_OK(filter.UpdateNullCount(s));
-  if (values.len >= ((int64_t)1 << 32)) return Status::Make(StatusCode::NotImplemented, "filter of a boolean column with 2^32 rows or more");
-  const uint8_t* fvalid = filter.MayHaveNulls() ? filter.buffers[0].buf : nullptr;
-  int64_t n_out = 0;
-  if (values.len > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_count(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, filter.len, null_sel, &n_out)));
-  BufferPtr ib, ivb;
-  AHC_RETURN_NOT_OK(k->Allocate(n_out * 4, &ib));
-  AHC_RETURN_NOT_OK(k->AllocateBitmap(n_out, &ivb));
-  int64_t idx_nulls = 0;
-  if (n_out > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_to_indices(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, values.len, null_sel, n_out,
-                                                         (uint32_t*)ib->dptr, (uint8_t*)ivb->dptr, &idx_nulls)));
-  return TakeBooleanCommon(k, values, 4, false, ib->dptr, idx_nulls ? (const uint8_t*)ivb->dptr : nullptr, 0, n_out,
-                           values.nulls != 0 || filter.nulls != 0, out);
+  AHC_RETURN_NOT_OK(values.UpdateNullCount(k->session));
+  IndexOperand ix;
+  AHC_RETURN_NOT_OK(FilterToIndices(k->session, filter, values.len, static_cast<const FilterOptions*>(k->state), (int64_t)1 << 32,
+                                    "filter of a boolean column with 2^32 rows or more", &ix));
+  return TakeBooleanCommon(k, values, ix, values.nulls != 0 || filter.nulls != 0, out);
 }
 
 static const Type kBinaryTypes[] = {Type::STRING, Type::BINARY, Type::LARGE_STRING, Type::LARGE_BINARY};
@@ -807,28 +793,18 @@ static const DictionaryEncodeOptions kDefaultDictOptions;
 static Status FilterRecordBatch(ExecCtx* ctx, const Datum& batch, const ArrayData& filter_in, const FilterOptions* opts, Datum* out) {
   Session* s = ctx->session;
   if (batch.num_rows != filter_in.length) return Status::Make(StatusCode::Invalid, "filter inputs must all be the same length");
-  if (filter_in.length >= ((int64_t)1 << 32) - 1)
-    return Status::Make(StatusCode::NotImplemented, "filter length exceeds UINT32_MAX, consider a different strategy for selecting elements");  // :229-235
   exec::ArraySpan filter;
   filter.SetMembers(filter_in);
-  AHC_RETURN_NOT_OK(filter.UpdateNullCount(s));
-  const int null_sel = opts ? (int)opts->NullSelection : DropNulls;
-  const uint8_t* fvalid = filter.MayHaveNulls() ? filter.buffers[0].buf : nullptr;
-  int64_t n_out = 0;
-  if (filter.len > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_count(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, filter.len, null_sel, &n_out)));
+  IndexOperand ix;
+  AHC_RETURN_NOT_OK(FilterToIndices(s, filter, filter.len, opts, ((int64_t)1 << 32) - 1,
+                                    "filter length exceeds UINT32_MAX, consider a different strategy for selecting elements", &ix));
+  const int64_t n_out = ix.len;
   auto idx = std::make_shared<ArrayData>();
   idx->type = GetDataType(Type::UINT32);
   idx->length = n_out;
-  AHC_RETURN_NOT_OK(s->Allocate(n_out * 4, &idx->buffers[1]));
-  BufferPtr ivb;
-  AHC_RETURN_NOT_OK(s->AllocateBitmap(n_out, &ivb));
-  int64_t idx_nulls = 0;
-  if (n_out > 0)
-    AHC_RETURN_NOT_OK(s->FromStatus(ah_filter_to_indices(s->ctx(), filter.buffers[1].buf, fvalid, filter.offset, filter.len, null_sel, n_out,
-                                                         (uint32_t*)idx->buffers[1]->dptr, (uint8_t*)ivb->dptr, &idx_nulls)));
-  idx->null_count = idx_nulls;
-  if (idx_nulls) idx->buffers[0] = ivb;
+  idx->buffers[1] = ix.data_buf;
+  idx->null_count = ix.nulls;
+  if (ix.nulls) idx->buffers[0] = ix.valid_buf;
   static const TakeOptions kNoBoundsCheck = [] { TakeOptions t; t.BoundsCheck = false; return t; }();
   std::vector<ArrayDataPtr> cols;
   for (auto& c : batch.chunks) {
@@ -841,79 +817,36 @@ static Status FilterRecordBatch(ExecCtx* ctx, const Datum& batch, const ArrayDat
 }
 
 void RegisterVectorSelection(FunctionRegistry* reg) {
+  static const Type kIndexTypes[] = {Type::INT8, Type::UINT8, Type::INT16, Type::UINT16, Type::INT32, Type::UINT32, Type::INT64, Type::UINT64};
+  static const Type kBool[] = {Type::BOOL}, kDictionary[] = {Type::DICTIONARY};
+  static const Type kFixedSlotTypes[] = {Type::FIXED_SIZE_BINARY, Type::DECIMAL128, Type::DECIMAL256};
+  // one kernel per (value type, second type) pair, value-major
+  auto add = [](VectorFunction* fn, const auto& values, const auto& seconds, exec::ArrayKernelExec exec_fn, bool chunkwise) {
+    for (Type t : values)
+      for (Type t2 : seconds) {
+        exec::VectorKernel k;
+        k.sig.in_types = {t, t2};
+        k.exec_fn = exec_fn;
+        k.can_execute_chunkwise = chunkwise;
+        fn->AddKernel(std::move(k));
+      }
+  };
   auto af = std::make_shared<VectorFunction>("array_filter", Arity{2, false}, &kDefaultFilterOptions);
   af->chunked = VectorFunction::Chunked::Filter;
-  for (Type t : kNumericTypes) {
-    exec::VectorKernel k;
-    k.sig.in_types = {t, Type::BOOL};
-    k.exec_fn = ExecFilter;
-    af->AddKernel(std::move(k));
-  }
-  {
-    exec::VectorKernel k;
-    k.sig.in_types = {Type::DICTIONARY, Type::BOOL};
-    k.exec_fn = ExecFilterDictionary;
-    af->AddKernel(std::move(k));
-  }
-  for (Type t : kBinaryTypes) {
-    exec::VectorKernel k;
-    k.sig.in_types = {t, Type::BOOL};
-    k.exec_fn = ExecFilterBinary;
-    af->AddKernel(std::move(k));
-  }
-  {
-    exec::VectorKernel k;
-    k.sig.in_types = {Type::BOOL, Type::BOOL};
-    k.exec_fn = ExecFilterBoolean;
-    af->AddKernel(std::move(k));
-  }
-  for (Type t : {Type::FIXED_SIZE_BINARY, Type::DECIMAL128, Type::DECIMAL256}) {   // vector_selection.go:2344-2346
-    exec::VectorKernel k;
-    k.sig.in_types = {t, Type::BOOL};
-    k.exec_fn = ExecFilterFixed;
-    af->AddKernel(std::move(k));
-  }
+  add(af.get(), kNumericTypes, kBool, ExecFilter, true);
+  add(af.get(), kDictionary, kBool, ExecFilterDictionary, true);
+  add(af.get(), kBinaryTypes, kBool, ExecFilterBinary, true);
+  add(af.get(), kBool, kBool, ExecFilterBoolean, true);
+  add(af.get(), kFixedSlotTypes, kBool, ExecFilterFixed, true);   // vector_selection.go:2344-2346
   reg->AddFunction(af, false);
   auto at = std::make_shared<VectorFunction>("array_take", Arity{2, false}, &kDefaultTakeOptions);
   at->chunked = VectorFunction::Chunked::Take;
-  for (Type t : kNumericTypes)
-    for (Type it : {Type::INT8, Type::UINT8, Type::INT16, Type::UINT16, Type::INT32, Type::UINT32, Type::INT64, Type::UINT64}) {
-      exec::VectorKernel k;
-      k.sig.in_types = {t, it};
-      k.exec_fn = ExecTake;
-      k.can_execute_chunkwise = false;  // selection.go:639
-      at->AddKernel(std::move(k));
-    }
-  for (Type it : {Type::INT8, Type::UINT8, Type::INT16, Type::UINT16, Type::INT32, Type::UINT32, Type::INT64, Type::UINT64}) {
-    exec::VectorKernel k;
-    k.sig.in_types = {Type::DICTIONARY, it};
-    k.exec_fn = ExecTakeDictionary;
-    k.can_execute_chunkwise = false;
-    at->AddKernel(std::move(k));
-  }
-  for (Type it : {Type::INT8, Type::UINT8, Type::INT16, Type::UINT16, Type::INT32, Type::UINT32, Type::INT64, Type::UINT64}) {
-    exec::VectorKernel k;
-    k.sig.in_types = {Type::BOOL, it};
-    k.exec_fn = ExecTakeBoolean;
-    k.can_execute_chunkwise = false;
-    at->AddKernel(std::move(k));
-  }
-  for (Type t : {Type::FIXED_SIZE_BINARY, Type::DECIMAL128, Type::DECIMAL256})   // vector_selection.go:2354-2356
-    for (Type it : {Type::INT8, Type::UINT8, Type::INT16, Type::UINT16, Type::INT32, Type::UINT32, Type::INT64, Type::UINT64}) {
-      exec::VectorKernel k;
-      k.sig.in_types = {t, it};
-      k.exec_fn = ExecTakeFixed;
-      k.can_execute_chunkwise = false;
-      at->AddKernel(std::move(k));
-    }
-  for (Type t : kBinaryTypes)
-    for (Type it : {Type::INT8, Type::UINT8, Type::INT16, Type::UINT16, Type::INT32, Type::UINT32, Type::INT64, Type::UINT64}) {
-      exec::VectorKernel k;
-      k.sig.in_types = {t, it};
-      k.exec_fn = ExecTakeBinary;
-      k.can_execute_chunkwise = false;
-      at->AddKernel(std::move(k));
-    }
+  // (not chunkwise: selection.go:639)
+  add(at.get(), kNumericTypes, kIndexTypes, ExecTake, false);
+  add(at.get(), kDictionary, kIndexTypes, ExecTakeDictionary, false);
+  add(at.get(), kBool, kIndexTypes, ExecTakeBoolean, false);
+  add(at.get(), kFixedSlotTypes, kIndexTypes, ExecTakeFixed, false);   // vector_selection.go:2354-2356
+  add(at.get(), kBinaryTypes, kIndexTypes, ExecTakeBinary, false);
   reg->AddFunction(at, false);
   // filterMetaFunc (selection.go:42-85): validates, then dispatches on the values kind
   reg->AddFunction(std::make_shared<MetaFunction>("filter", Arity{2, false}, &kDefaultFilterOptions,
@@ -1069,7 +1002,9 @@ static Status ExecHashBinary(KernelCtx* k, const ExecSpan& b, ExecResult* out, b
   // GetDictArrayData (arrow/array/util.go:341-366): offsets + values in memo order, a null entry has no bytes
   ExecResult dres;
   dres.type = keys.type;
-  AHC_RETURN_NOT_OK(TakeBinaryCommon(k, keys, 8, true, first_rows->dptr, nullptr, 0, ndict, false, &dres));
+  IndexOperand rows;   // int64 first-occurrence rows, no nulls
+  rows.width = 8; rows.is_signed = true; rows.data = first_rows->dptr; rows.len = ndict;
+  AHC_RETURN_NOT_OK(TakeBinaryCommon(k, keys, rows, false, &dres));
   auto d = std::make_shared<ArrayData>();
   d->type = keys.type;
   d->length = ndict;

@@ -261,6 +261,23 @@ def test_filter_random_vs_arrow_cpp(sess):
 
 # ---- take ------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
+@pytest.mark.parametrize("values", [pa.array([7, 8, 9], type=pa.int64()), pa.array([True, False, None]), pa.array(["a", None, "ccc"]),
+                                    pa.array([b"abc", b"def", b"ghi"], type=pa.binary(3))], ids=lambda v: str(v.type))
+def test_take_unsigned_64_bit_index_above_2_63_is_reported_as_unsigned(sess, values):
+    """One host function turns the first offending position into "%d out of bounds" (helpers.go:950) for the primitive, boolean,
+    var-length and arbitrary-width Takes: an unsigned 64-bit index ≥ 2^63 prints as the unsigned number it is, never as a negative
+    one; a null slot holding the same bits is not checked."""
+    from arrow_go_amd import compute as ac
+    big = 2**63 + 5
+    with pytest.raises(ac.ErrIndex, match=rf"(?<![-\d]){big} out of bounds"):
+        sess.call_function("take", [values, pa.array([0, big, 1], type=pa.uint64())])
+    with pytest.raises(ac.ErrIndex, match=r"(?<![-\d])18446744073709551615 out of bounds"):
+        sess.call_function("take", [values, pa.array([2, None, 2**64 - 1, big], type=pa.uint64())])
+    got = sess.call_function("take", [values, pa.array([2, None, 0], type=pa.uint64())])
+    assert got.equals(pc.take(values, pa.array([2, None, 0], type=pa.uint64())))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("typ", NUMERIC, ids=str)
 @pytest.mark.parametrize("ityp", [pa.int8(), pa.uint32(), pa.int64()], ids=str)
 def test_take(sess, typ, ityp):

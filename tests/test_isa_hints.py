@@ -59,6 +59,9 @@ RESOURCES = {
         (r"enc_table_kernelILi8192ELb1E", 128, 0),
     ],
     "ah_take.hip": [(r"take_vec_kernelILi8EiLb[01]ELi7E", 64, 0)],
+    # the binned Take's hot kernels at the figures they had before the index rule moved into ah_index.h: the scatter
+    # (53 VGPRs; 45 for uint32 indices), the LDS-bitmap gather of 8-byte values (58) and their un-permute (42), none with scratch
+    "ah_take_binned.hip": [(r"bin_scatter_kernelI", 53, 0), (r"bin_gather_lds_kernelILi8E", 58, 0), (r"unpermute_kernelILi8ELb1E", 42, 0)],
     # the one-pass cumulative_sum: a workgroup of 1024 lanes per CU = 128 registers, and nothing of the tile in scratch (a CSE of the
     # sixteen null masks across the look-back once spilled 21 … 49 registers and every parity test stayed green: DESIGN.md §3.4)
     "ah_scan.hip": [(r"scan_onepass_kernelI[jyt]Lb", 128, 16), (r"scan_onepass_f64_kernel", 128, 0)],
