@@ -347,6 +347,9 @@ class Session:
                 tid = _TYPE_IDS["int32" if arr.type.bit_width == 32 else "int64"]
             elif tname in _TYPE_IDS:
                 tid = _TYPE_IDS[tname]
+            elif (pa.types.is_decimal(arr.type) or pa.types.is_fixed_size_binary(arr.type)) and arr.num_chunks:
+                # parametric types: the id here, precision / scale / width from the chunks themselves
+                tid = 23 if pa.types.is_decimal128(arr.type) else 24 if pa.types.is_decimal256(arr.type) else 15
             else:
                 raise ErrNotImplemented(f"unsupported chunked type {tname}")
             parts = [self._import(c) for c in arr.chunks]

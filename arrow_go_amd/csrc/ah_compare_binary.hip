@@ -20,6 +20,7 @@
 // table of 64-bit powers of ten) and compared as signed two's complement: top word signed, lower words unsigned.
 #include "ah_common.h"
 #include "ah_bytes.h"
+#include "ah_decimal.h"
 
 namespace {
 
@@ -100,63 +101,7 @@ __global__ __launch_bounds__(kBlock) void compare_bytes_kernel(ByteRows L, ByteR
 }
 
 // ---- decimals ---------------------------------------------------------------------------------------------------------------
-struct I256 { unsigned long long w[4]; };
-
-__constant__ unsigned long long kPow10[20] = {1ull,
-                                              10ull,
-                                              100ull,
-                                              1000ull,
-                                              10000ull,
-                                              100000ull,
-                                              1000000ull,
-                                              10000000ull,
-                                              100000000ull,
-                                              1000000000ull,
-                                              10000000000ull,
-                                              100000000000ull,
-                                              1000000000000ull,
-                                              10000000000000ull,
-                                              100000000000000ull,
-                                              1000000000000000ull,
-                                              10000000000000000ull,
-                                              100000000000000000ull,
-                                              1000000000000000000ull,
-                                              10000000000000000000ull};
-
-using V2u64 = unsigned long long __attribute__((ext_vector_type(2)));
-struct V2u64u { V2u64 v; } __attribute__((packed, aligned(1)));
-
-template <int W>
-__device__ __forceinline__ I256 load_dec(const uint8_t* p) {
-  I256 x;
-  const V2u64 lo = reinterpret_cast<const V2u64u*>(p)->v;
-  x.w[0] = lo.x;
-  x.w[1] = lo.y;
-  if constexpr (W == 32) {
-    const V2u64 hi = reinterpret_cast<const V2u64u*>(p + 16)->v;
-    x.w[2] = hi.x;
-    x.w[3] = hi.y;
-  } else {
-    x.w[2] = x.w[3] = (unsigned long long)((long long)x.w[1] >> 63);  // sign extension
-  }
-  return x;
-}
-
-// x · 10^k mod 2^256: exact whenever the product fits, which the promoted precision (≤ 76 digits) guarantees
-__device__ __forceinline__ void scale_up(I256& x, int k) {
-  while (k > 0) {
-    const unsigned long long m = kPow10[k < 19 ? k : 19];
-    k -= 19;
-    unsigned long long carry = 0;
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-      const unsigned __int128 p = (unsigned __int128)x.w[t] * m + carry;
-      x.w[t] = (unsigned long long)p;
-      carry = (unsigned long long)(p >> 64);
-    }
-  }
-}
-
+// I256, kPow10, load_dec and scale_up: ah_decimal.h
 __device__ __forceinline__ int order_i256(const I256& a, const I256& b) {
   if (a.w[3] != b.w[3]) return (long long)a.w[3] < (long long)b.w[3] ? -1 : 1;
 #pragma unroll

@@ -503,6 +503,22 @@ class Context:
         check(self.handle, lib.ah_cast_numeric(self.handle, in_type, out_type, _ptr(values), _ptr(valid), off, n,
                                                int(allow_int_overflow), int(allow_float_truncate), _ptr(out_values)))
 
+    def cast_decimal_rescale(self, in_width: int, out_width: int, scale_delta: int, out_precision: int, allow_truncate: bool, values, valid,
+                             off: int, n: int, out_values) -> None:
+        """CastDecimalToDecimal (numeric_cast.go:377-429); widths in bytes (16 | 32), scale_delta = out scale − in scale"""
+        check(self.handle, lib.ah_cast_decimal_rescale(self.handle, in_width, out_width, scale_delta, out_precision, int(allow_truncate),
+                                                       _ptr(values), _ptr(valid), off, n, _ptr(out_values)))
+
+    def cast_int_to_decimal(self, in_type: int, out_width: int, scale: int, values, valid, off: int, n: int, out_values) -> None:
+        """CastIntegerToDecimal (numeric_cast.go:173-239): value · 10^scale"""
+        check(self.handle, lib.ah_cast_int_to_decimal(self.handle, in_type, out_width, scale, _ptr(values), _ptr(valid), off, n, _ptr(out_values)))
+
+    def cast_decimal_to_int(self, in_width: int, in_scale: int, out_type: int, allow_truncate: bool, allow_overflow: bool, values, valid,
+                            off: int, n: int, out_values) -> None:
+        """CastDecimal128ToInteger / CastDecimal256ToInteger (numeric_cast.go:79-171)"""
+        check(self.handle, lib.ah_cast_decimal_to_int(self.handle, in_width, in_scale, out_type, int(allow_truncate), int(allow_overflow),
+                                                      _ptr(values), _ptr(valid), off, n, _ptr(out_values)))
+
     def shift_time(self, in_bits: int, out_bits: int, op: int, factor: int, checked: bool, values, valid, off: int, n: int, out_values) -> None:
         """ShiftTime (cast_temporal.go:35-104); op 0 multiply, 1 divide.  A failed check raises ErrInvalid carrying .bad_value"""
         bad = C.c_int64(0)

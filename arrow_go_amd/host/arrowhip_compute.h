@@ -231,6 +231,8 @@ struct KernelSignature {
   std::vector<Type> in_types;
   bool out_is_first_input = true;
   Type out_type = Type::NA;
+  // OutputType resolved from the call's CastOptions.ToType (resolveOutputFromOptions, compute/cast.go): the parametric cast targets
+  bool out_from_options = false;
   bool MatchesInputs(const std::vector<const DataType*>& types) const;
 };
 
@@ -409,6 +411,11 @@ class ScalarFunction : public Function {  // functions.go:239-290
  public:
   ScalarFunction(std::string name, Arity arity) : Function(std::move(name), arity, FuncKind::Scalar) {}
   Status AddKernel(exec::ScalarKernel k);
+  // Kernels for PARAMETRIC input types (Decimal128 / Decimal256, matched by id) that a later layer adds to a function whose own
+  // kernel table is fixed: DispatchExact tries them after the function's own kernels.  NumKernels() and Kernels() keep reporting the
+  // function's own table (the numeric casts' "9 other numeric types + bool"), which callers and tests count on.
+  Status AddParametricKernel(exec::ScalarKernel k);
+  int NumParametricKernels() const { return (int)parametric_kernels_.size(); }
   int NumKernels() const override;   // a flipped comparison counts the kernels it shares with its base (scalar_compare.go:73-99)
   // funcImpl.Kernels() (functions.go:220-226): live pointers — the in-place swap route
   std::vector<exec::ScalarKernel*> Kernels();
@@ -427,6 +434,7 @@ class ScalarFunction : public Function {  // functions.go:239-290
   Status DispatchBest(std::vector<const DataType*>* types, const exec::ScalarKernel** out) const;
  private:
   std::vector<exec::ScalarKernel> kernels_;
+  std::vector<exec::ScalarKernel> parametric_kernels_;
 };
 
 class VectorFunction : public Function {  // functions.go:290-360

@@ -310,7 +310,8 @@ AHC_EXPORT int ahc_datum_info(ahc_datum* d, int* kind, int* type_id, int64_t* le
 
 // options: "key=value;key=value"; keys follow the Go struct tags
 //   null_selection_behavior=drop|emit_null   bounds_check=0|1   null_encoding_behavior=mask|encode
-//   to_type=<type>   safe=0|1   allow_int_overflow=0|1   allow_float_truncate=0|1       (CastOptions)
+//   to_type=<type>|d:<precision>,<scale>[,256]   safe=0|1   allow_int_overflow=0|1   allow_float_truncate=0|1
+//   allow_decimal_truncate=0|1                                                                    (CastOptions)
 //   value_set=@<ahc_datum* in hex>   null_matching_behavior=match|skip|emit_null|inconclusive      (SetOptions)
 //   order=ascending|descending   null_placement=at_end|at_start                                   (SortOptions, one key)
 //   sort_keys=<col>:<asc|desc>:<at_end|at_start>,…                                                (SortOptions, several keys)
@@ -373,6 +374,7 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
       if (k == "to_type") {
         p->cast.ToType = v == "bool" ? GetDataType(Type::BOOL) : nullptr;
         for (auto& tn : kTypeNames) if (v == tn.name) p->cast.ToType = GetDataType(tn.id);
+        if (v.size() > 2 && v[0] == 'd' && v[1] == ':') p->cast.ToType = FixedWidthBinaryFromFormat(v);   // "d:22,2" / "d:22,2,256"
         p->pick = &p->cast;
       }
       if (k == "to_logical") { p->cast.ToLogical = v; p->pick = &p->cast; }
@@ -380,6 +382,7 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
       if (k == "allow_int_overflow") { p->cast.AllowIntOverflow = v != "0"; p->pick = &p->cast; }
       if (k == "allow_time_truncate") { p->cast.AllowTimeTruncate = v != "0"; p->pick = &p->cast; }
       if (k == "allow_time_overflow") { p->cast.AllowTimeOverflow = v != "0"; p->pick = &p->cast; }
+      if (k == "allow_decimal_truncate") { p->cast.AllowDecimalTruncate = v != "0"; p->pick = &p->cast; }
       if (k == "allow_float_truncate") { p->cast.AllowFloatTruncate = v != "0"; p->pick = &p->cast; }
       if (k == "value_set" && v.size() > 1 && v[0] == '@') {
         ahc_datum* d = (ahc_datum*)(uintptr_t)strtoull(v.c_str() + 1, nullptr, 16);
@@ -981,6 +984,12 @@ AHC_EXPORT int ahc_chunked_from_arrays(ahc_session* s, int type_id, int n, ahc_d
     if (!chunks.empty() && arrays[i]->d.array->logical != chunks[0]->logical)
       return Fail(s, Status::Make(StatusCode::Invalid, "arrow/array: mismatch data type " + arrays[i]->d.array->logical + " vs " + chunks[0]->logical));
     chunks.push_back(arrays[i]->d.array);
+  }
+  if (IsFixedWidthBinary(t->id) && !chunks.empty()) {  // parametric types: the column's type is its chunks' (interned: one pointer per type)
+    for (auto& c : chunks)
+      if (c->type != chunks[0]->type)
+        return Fail(s, Status::Make(StatusCode::Invalid, std::string("arrow/array: mismatch data type ") + c->type->format + " vs " + chunks[0]->type->format));
+    t = chunks[0]->type;
   }
   *out = new ahc_datum{Datum::OfChunks(t, std::move(chunks))};
   return 0;

@@ -302,6 +302,12 @@ Status ScalarFunction::AddKernel(exec::ScalarKernel k) {
   kernels_.push_back(std::move(k));
   return Status::OK();
 }
+Status ScalarFunction::AddParametricKernel(exec::ScalarKernel k) {
+  if ((int)k.sig.in_types.size() != arity_.NArgs)
+    return Status::Make(StatusCode::Invalid, "kernel signature does not match the arity of function '" + name_ + "'");
+  parametric_kernels_.push_back(std::move(k));
+  return Status::OK();
+}
 std::vector<exec::ScalarKernel*> ScalarFunction::Kernels() {
   std::vector<exec::ScalarKernel*> out;
   for (auto& k : kernels_) out.push_back(&k);
@@ -309,6 +315,8 @@ std::vector<exec::ScalarKernel*> ScalarFunction::Kernels() {
 }
 Status ScalarFunction::DispatchExact(const std::vector<const DataType*>& types, const exec::ScalarKernel** out) const {
   for (auto& k : kernels_)  // first matching signature wins (functions.go:209-213)
+    if (k.sig.MatchesInputs(types)) { *out = &k; return Status::OK(); }
+  for (auto& k : parametric_kernels_)
     if (k.sig.MatchesInputs(types)) { *out = &k; return Status::OK(); }
   return Status::Make(StatusCode::NotImplemented, "function '" + name_ + "' has no kernel matching input types " + TypesToString(types));
 }
@@ -392,11 +400,14 @@ static Status ArrayToScalar(Session* s, const ArrayData& a, ScalarPtr* out) {
   sc->type = a.type;
   uint8_t tmp[8] = {0};
   int w = a.type->bit_width == 1 ? 1 : a.type->bit_width / 8;
-  AHC_RETURN_NOT_OK(s->FromStatus(ah_download_async(s->ctx(), tmp, a.buffers[1]->dptr, (size_t)w)));
+  const bool wide = IsFixedWidthBinary(a.type->id);  // a decimal result: the payload travels in Scalar::bytes
+  if (wide) sc->bytes.assign((size_t)w, 0);
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_download_async(s->ctx(), wide ? sc->bytes.data() : tmp, a.buffers[1]->dptr, (size_t)w)));
   uint8_t vbyte = 1;
   if (a.buffers[0]) AHC_RETURN_NOT_OK(s->FromStatus(ah_download_async(s->ctx(), &vbyte, a.buffers[0]->dptr, 1)));
   AHC_RETURN_NOT_OK(s->FromStatus(ah_sync(s->ctx())));
   sc->valid = (vbyte & 1) != 0 && a.null_count != 1;
+  if (wide && !sc->valid) sc->bytes.clear();
   if (a.type->id == Type::BOOL) tmp[0] &= 1;
   memcpy(sc->value, tmp, 8);
   *out = sc;
@@ -454,6 +465,11 @@ Status ScalarFunction::Execute(ExecCtx* ctx, const FunctionOptions* opts, const 
 
   exec::ExecResult res;
   res.type = kernel->sig.out_is_first_input ? types[0] : GetDataType(kernel->sig.out_type);
+  if (kernel->sig.out_from_options) {
+    const CastOptions* co = dynamic_cast<const CastOptions*>(opts ? opts : default_opts_);
+    if (!co || !co->ToType) return Status::Make(StatusCode::Invalid, "cast requires that options be passed with a ToType");
+    res.type = co->ToType;
+  }
   res.len = length;
   res.offset = 0;
   // setupPrealloc (executor.go:658-702)

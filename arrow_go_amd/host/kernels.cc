@@ -1107,7 +1107,7 @@ void RegisterVectorHash(FunctionRegistry* reg) {
   reg->AddFunction(de, false);
 }
 
-// ---- cast (numeric ↔ numeric, bool ↔ numeric) -------------------------------------------------------
+// ---- cast (numeric ↔ numeric, bool ↔ numeric, decimal ↔ decimal, integer ↔ decimal) -----------------
 // CastIntToInt / CastFloatingToInteger / CastIntegerToFloating / CastFloatingToFloating
 // (kernels/numeric_cast.go:37-71): conversion and safe-cast check in one pass on the device
 static Status ExecCastNumeric(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
@@ -1135,8 +1135,72 @@ static Status ExecCastNumericToBool(KernelCtx* k, const ExecSpan& b, ExecResult*
                                      out->len, (int)(out->offset % 8)));
 }
 
+// ---- decimal casts (kernels/numeric_cast.go:79-429) ------------------------------------------------------------------------
+// precision and scale of a decimal cast target, checked against the width
+static Status CastTargetDecimal(const DataType* t, int* precision, int* scale) {
+  if (!DecimalParams(t, precision, scale)) return Status::Make(StatusCode::Invalid, std::string("cast: not a decimal type: ") + t->name);
+  const int max_p = t->id == Type::DECIMAL128 ? 38 : 76;
+  if (*precision < 1 || *precision > max_p)
+    return Status::Make(StatusCode::Invalid, "Decimal precision out of range [1, " + std::to_string(max_p) + "]: " + std::to_string(*precision));
+  return Status::OK();
+}
+
+// CastDecimalToDecimal (numeric_cast.go:377-429): rescale by the difference of the scales, then the precision check — or, with
+// AllowDecimalTruncate, truncate / wrap and check nothing.  Negative scales: refused, as in CastBinaryDecimalArgs.
+static Status ExecCastDecimalToDecimal(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  Session* s = k->session;
+  const CastOptions* opts = static_cast<const CastOptions*>(k->state);
+  const ArraySpan& in = b.values[0].array;
+  int in_p = 0, in_s = 0, out_p = 0, out_s = 0;
+  if (!DecimalParams(in.type, &in_p, &in_s)) return Status::Make(StatusCode::Invalid, "cast: decimal input without precision and scale");
+  AHC_RETURN_NOT_OK(CastTargetDecimal(out->type, &out_p, &out_s));
+  if (in_s < 0 || out_s < 0) return Status::Make(StatusCode::NotImplemented, "decimals with negative scales not supported");
+  if (out->len == 0) return Status::OK();
+  return s->FromStatus(ah_cast_decimal_rescale(s->ctx(), in.type->bit_width / 8, out->type->bit_width / 8, out_s - in_s, out_p,
+                                               opts && opts->AllowDecimalTruncate, Values(in), in.MayHaveNulls() ? in.buffers[0].buf : nullptr, in.offset,
+                                               in.len, Values(out)));
+}
+
+// CastIntegerToDecimal (numeric_cast.go:207-239): the scale and precision checks are made from the types, before any row is read
+static Status ExecCastIntegerToDecimal(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  Session* s = k->session;
+  const ArraySpan& in = b.values[0].array;
+  int out_p = 0, out_s = 0;
+  AHC_RETURN_NOT_OK(CastTargetDecimal(out->type, &out_p, &out_s));
+  if (out_s < 0) return Status::Make(StatusCode::Invalid, "scale must be non-negative");
+  const int min_precision = MaxDecimalDigitsForInt(in.type->id) + out_s;
+  if (out_p < min_precision)
+    return Status::Make(StatusCode::Invalid, "precision is not great enough for result. It should be at least " + std::to_string(min_precision));
+  if (out->len == 0) return Status::OK();
+  return s->FromStatus(ah_cast_int_to_decimal(s->ctx(), (int)in.type->id, out->type->bit_width / 8, out_s, Values(in),
+                                              in.MayHaveNulls() ? in.buffers[0].buf : nullptr, in.offset, in.len, Values(out)));
+}
+
+// CastDecimal128ToInteger / CastDecimal256ToInteger (numeric_cast.go:91-171)
+static Status ExecCastDecimalToInteger(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  Session* s = k->session;
+  const CastOptions* opts = static_cast<const CastOptions*>(k->state);
+  const ArraySpan& in = b.values[0].array;
+  int in_p = 0, in_s = 0;
+  if (!DecimalParams(in.type, &in_p, &in_s)) return Status::Make(StatusCode::Invalid, "cast: decimal input without precision and scale");
+  if (out->len == 0) return Status::OK();
+  return s->FromStatus(ah_cast_decimal_to_int(s->ctx(), in.type->bit_width / 8, in_s, (int)out->type->id, opts && opts->AllowDecimalTruncate,
+                                              opts && opts->AllowIntOverflow, Values(in), in.MayHaveNulls() ? in.buffers[0].buf : nullptr, in.offset,
+                                              in.len, Values(out)));
+}
+
+// arrow.TypeEqual for the cast meta function's shortcut: decimals by precision and scale (interned: usually the same pointer), every
+// other type by its id
+static bool CastIsIdentity(const DataType* from, const DataType* to) {
+  if (from->id != to->id) return false;
+  if (!IsDecimal(from->id) || from == to) return true;
+  int fp = 0, fs = 0, tp = 0, ts = 0;
+  return DecimalParams(from, &fp, &fs) && DecimalParams(to, &tp, &ts) && fp == tp && fs == ts;
+}
+
 static const char* CastFunctionName(Type t) {
   switch (t) {
+    case Type::DECIMAL128: return "cast_decimal"; case Type::DECIMAL256: return "cast_decimal256";   // cast.go:883-885
     case Type::BOOL: return "cast_boolean";
     case Type::UINT8: return "cast_uint8"; case Type::INT8: return "cast_int8"; case Type::UINT16: return "cast_uint16";
     case Type::INT16: return "cast_int16"; case Type::UINT32: return "cast_uint32"; case Type::INT32: return "cast_int32";
@@ -1147,7 +1211,7 @@ static const char* CastFunctionName(Type t) {
 }
 
 // RegisterScalarCast (compute/cast.go:83-85) + the per-target cast functions getCastFunction resolves
-// (cast.go:190-260: "cast_int32" …), numeric and boolean targets
+// (cast.go:190-260: "cast_int32" …), numeric, boolean and decimal targets
 void RegisterScalarCast(FunctionRegistry* reg) {
   for (Type to : kNumericTypes) {
     auto fn = std::make_shared<ScalarFunction>(CastFunctionName(to), Arity{1, false});
@@ -1166,6 +1230,42 @@ void RegisterScalarCast(FunctionRegistry* reg) {
     kb.sig.out_type = to;
     kb.exec_fn = ExecCastBoolToNumeric;
     fn->AddKernel(std::move(kb));
+    // the decimal kernels of every cast_<integer> function (numeric_cast.go:852-857), matched by type id: held beside the
+    // function's numeric table (ScalarFunction::AddParametricKernel), whose size of ten is what NumKernels() goes on reporting
+    if (IsInteger(to))
+      for (Type from : {Type::DECIMAL128, Type::DECIMAL256}) {
+        exec::ScalarKernel kd;
+        kd.sig.in_types = {from};
+        kd.sig.out_is_first_input = false;
+        kd.sig.out_type = to;
+        kd.exec_fn = ExecCastDecimalToInteger;
+        fn->AddParametricKernel(std::move(kd));
+      }
+    reg->AddFunction(fn, false);
+  }
+  // cast_decimal / cast_decimal256 (cast.go:883-885; getDecimalCastKernels numeric_cast.go:912-970): the eight integer inputs by exact
+  // type, Decimal128 / Decimal256 by id; the output type is the options' ToType (resolveOutputFromOptions)
+  for (Type to : {Type::DECIMAL128, Type::DECIMAL256}) {
+    auto fn = std::make_shared<ScalarFunction>(CastFunctionName(to), Arity{1, false});
+    for (Type from : kNumericTypes) {
+      if (!IsInteger(from)) continue;
+      exec::ScalarKernel k;
+      k.sig.in_types = {from};
+      k.sig.out_is_first_input = false;
+      k.sig.out_type = to;
+      k.sig.out_from_options = true;
+      k.exec_fn = ExecCastIntegerToDecimal;
+      fn->AddKernel(std::move(k));
+    }
+    for (Type from : {Type::DECIMAL128, Type::DECIMAL256}) {
+      exec::ScalarKernel k;
+      k.sig.in_types = {from};
+      k.sig.out_is_first_input = false;
+      k.sig.out_type = to;
+      k.sig.out_from_options = true;
+      k.exec_fn = ExecCastDecimalToDecimal;
+      fn->AddKernel(std::move(k));
+    }
     reg->AddFunction(fn, false);
   }
   auto fb = std::make_shared<ScalarFunction>(CastFunctionName(Type::BOOL), Arity{1, false});
@@ -1184,12 +1284,12 @@ void RegisterScalarCast(FunctionRegistry* reg) {
         const CastOptions* opts = dynamic_cast<const CastOptions*>(o);
         if (!opts || !opts->ToType)
           return Status::Make(StatusCode::Invalid, "cast requires that options be passed with a ToType");
-        if (args[0].type()->id == opts->ToType->id) { *out = args[0]; return Status::OK(); }  // TypeEqual → the input itself
+        if (CastIsIdentity(args[0].type(), opts->ToType)) { *out = args[0]; return Status::OK(); }  // TypeEqual → the input itself
         const char* name = CastFunctionName(opts->ToType->id);
         if (!name)
           return Status::Make(StatusCode::NotImplemented, std::string("unsupported cast to ") + opts->ToType->name + " from " + args[0].type()->name);
         Status st = CallFunction(ctx, name, o, args, out);
-        if (!st.ok() && st.code == StatusCode::NotImplemented)
+        if (!st.ok() && st.code == StatusCode::NotImplemented && st.msg.find("has no kernel matching") != std::string::npos)
           return Status::Make(StatusCode::NotImplemented, std::string("unsupported cast to ") + opts->ToType->name + " from " + args[0].type()->name);
         return st;
       }), false);

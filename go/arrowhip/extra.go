@@ -385,3 +385,26 @@ func (x *Context) CompareDecimal(cmpOp int, lWidth int, l unsafe.Pointer, lOff i
 	return x.err(C.ah_compare_decimal(x.c, C.int(cmpOp), C.int(lWidth), (*C.uint8_t)(l), C.int64_t(lOff), C.int(lBroadcast), C.int(lScaleUp),
 		C.int(rWidth), (*C.uint8_t)(r), C.int64_t(rOff), C.int(rBroadcast), C.int(rScaleUp), C.int64_t(n), (*C.uint8_t)(outBits), C.int64_t(outBitOffset)))
 }
+
+// CastDecimalRescale mirrors CastDecimalToDecimal (kernels/numeric_cast.go:377-429): inWidth / outWidth 16 or 32 bytes, scaleDelta the
+// output's scale minus the input's.  allowTruncate false: data loss and a value beyond outPrecision are arrow.ErrInvalid for the first
+// offending valid row; true: truncate toward zero / wrap, no precision check.  values points at the first row, off is its bit in valid.
+func (x *Context) CastDecimalRescale(inWidth, outWidth, scaleDelta, outPrecision int, allowTruncate bool, values, valid unsafe.Pointer,
+	off, n int64, dst unsafe.Pointer) error {
+	return x.err(C.ah_cast_decimal_rescale(x.c, C.int(inWidth), C.int(outWidth), C.int(scaleDelta), C.int(outPrecision), boolInt(allowTruncate),
+		values, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), dst))
+}
+
+// CastIntToDecimal mirrors CastIntegerToDecimal (kernels/numeric_cast.go:173-239): value · 10^scale into 16- or 32-byte slots; the
+// precision check against MaxDecimalDigitsForInt is the caller's.
+func (x *Context) CastIntToDecimal(in arrow.Type, outWidth, scale int, values, valid unsafe.Pointer, off, n int64, dst unsafe.Pointer) error {
+	return x.err(C.ah_cast_int_to_decimal(x.c, C.int(in), C.int(outWidth), C.int(scale), values, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), dst))
+}
+
+// CastDecimalToInt mirrors CastDecimal128ToInteger / CastDecimal256ToInteger (kernels/numeric_cast.go:79-171); allowTruncate is
+// CastOptions.AllowDecimalTruncate (round half away from zero instead of the data-loss error), allowOverflow is AllowIntOverflow.
+func (x *Context) CastDecimalToInt(inWidth, inScale int, out arrow.Type, allowTruncate, allowOverflow bool, values, valid unsafe.Pointer, off, n int64,
+	dst unsafe.Pointer) error {
+	return x.err(C.ah_cast_decimal_to_int(x.c, C.int(inWidth), C.int(inScale), C.int(out), boolInt(allowTruncate), boolInt(allowOverflow),
+		values, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), dst))
+}

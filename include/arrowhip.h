@@ -596,6 +596,33 @@ int ah_comm_merge_groups(ah_comm* comm, int is_f64, const uint64_t* keys, const 
  * Synchronises only when a check is active.  in_type == out_type is a device copy. */
 int ah_cast_numeric(ah_ctx* ctx, int in_type, int out_type, const void* values, const uint8_t* valid, int64_t off, int64_t n,
                     int allow_int_overflow, int allow_float_truncate, void* out_values);
+/* ---- decimal casts (row §8(f)-2) ------------------------------------------------------------------------
+ * The decimal kernels behind compute's "cast": all arithmetic on the unscaled integer (16 bytes: Decimal128, 32 bytes: Decimal256,
+ * little-endian two's complement).  `values` points at the first row; `off` is the bit offset of that row in `valid` (NULL: all
+ * valid).  ScalarUnaryNotNull: a null slot is not looked at and its output is zero bytes; only VALID rows can fail, and the error is
+ * that of the FIRST offending row.  One pass; synchronises only when a check is active.
+ *
+ * ah_cast_decimal_rescale replaces CastDecimalToDecimal (kernels/numeric_cast.go:377-429).  scale_delta = out_scale − in_scale,
+ * −76 … 76.  allow_truncate == 0 (safeRescaleDecimal128Out / 256Out, :310-375): × 10^k, or ÷ 10^k where a non-zero remainder is
+ * AH_EINVALID "rescale data loss"; then |v| < 10^out_precision, else AH_EINVALID "decimal value does not fit in precision" (also
+ * when the product leaves the width); a 32 → 16 byte cast narrows after the check.  allow_truncate != 0 (unsafeUpscale* /
+ * unsafeDownscale*, :264-308): × 10^k modulo 2^128 / 2^256, or ÷ 10^k truncated toward zero; no precision check; 32 → 16 keeps
+ * the low 16 bytes. */
+int ah_cast_decimal_rescale(ah_ctx* ctx, int in_width, int out_width, int scale_delta, int out_precision, int allow_truncate,
+                            const void* values, const uint8_t* valid, int64_t off, int64_t n, void* out_values);
+/* replaces CastIntegerToDecimal → integerToDecimal128 / 256 (kernels/numeric_cast.go:173-239): value · 10^scale, sign- or
+ * zero-extended by in_type (AH_UINT8 … AH_INT64).  scale < 0 → AH_EINVALID "scale must be non-negative".  The precision check is
+ * the caller's, from the types (precision ≥ MaxDecimalDigitsForInt(in_type) + scale); this entry refuses a scale with which that
+ * bound exceeds the width's 38 / 76 digits, so the product never leaves the width.  Never synchronises. */
+int ah_cast_int_to_decimal(ah_ctx* ctx, int in_type, int out_width, int scale, const void* values, const uint8_t* valid, int64_t off,
+                           int64_t n, void* out_values);
+/* replaces CastDecimal128ToInteger / CastDecimal256ToInteger → decimalToIntImpl (kernels/numeric_cast.go:79-171).
+ * allow_truncate == 0: Rescale(in_scale, 0) — a non-zero remainder is AH_EINVALID "rescale data loss"; != 0:
+ * ReduceScaleBy(in_scale, round = true), half away from zero.  A negative in_scale multiplies by 10^−in_scale.  allow_overflow == 0: a
+ * value outside out_type's inclusive range is AH_EINVALID "integer value out of bounds".  The result is the low 64 bits narrowed to
+ * out_type (AH_UINT8 … AH_INT64). */
+int ah_cast_decimal_to_int(ah_ctx* ctx, int in_width, int in_scale, int out_type, int allow_truncate, int allow_overflow,
+                           const void* values, const uint8_t* valid, int64_t off, int64_t n, void* out_values);
 /* ---- temporal unit change (the casts either side of the temporal kernels) ----------------------------
  * replaces ShiftTime[InT, OutT](ctx, op, factor, input, output) (kernels/cast_temporal.go:35-104), the leaf of the
  * timestamp / duration / time32↔time64 / date32↔date64 casts (cast_temporal.go:240-420) and of the implicit unit
