@@ -1,7 +1,15 @@
-// ah_bins.h — the tile / bin bookkeeping shared by the two "partition through LDS" pipelines: the binned Take
-// (ah_take_binned.hip: bin = window of the values column) and the partition-first group-by (ah_groupby.hip: bin =
-// hash partition of the keys).  Both cut the input into tiles, count per (tile, bin), turn the count table into the
-// global position of every tile's first record of every bin, and then stage each tile in bin order in LDS.
+// ah_bins.h — the tile / bin layer of the "partition through LDS" pipelines: the binned Take (ah_take_binned.hip: bin = window
+// of the values column), the partition-first group-by (ah_groupby.hip: bin = hash partition of the keys), the partition-first
+// encode (ah_hash_part.hip) and level 1 of the two-level pipelines of ah_msd.h.  All of them cut the input into tiles, count per
+// (tile, bin), turn the count table into the global position of every tile's first record of every bin, stage each tile in bin
+// order in LDS, and later send results home tile by tile the same way.  Here, each stated once:
+//   xcd_contiguous_tile   which tile a workgroup takes
+//   block_excl_scan       exclusive scan over ≤ 1024 bin counts;  digit_excl_scan: over more, 1024 at a time with a carry
+//   colsum / bin_prefix / tile_offs kernels + launch_tile_offsets   count table → offsets table, bin starts
+//   tile_bin_offsets      a tile's (or a group of tiles') counts and offsets → where each bin starts in the staged tile (s_start)
+//                         and in the global arrays (s_goff)
+//   bin_of_staged         staged position → bin: what an un-permute kernel needs to find a record it did not place itself
+//   store_staged          the staged output leaves coalesced
 #pragma once
 #include "ah_common.h"
 
@@ -35,6 +43,69 @@ __device__ __forceinline__ void block_excl_scan(const unsigned* s_cnt, unsigned*
   for (int w = 0; w < kThreads / 64; w++) if (w < wave) base += s_wsum[w];
   if (t < nb) s_start[t] = base + inc - a;
   __syncthreads();
+}
+
+// exclusive scan over nb > kThreads digit counts (nb ≤ 2048 in ah_msd.h), kThreads at a time with a carry.  each(d, start) runs
+// once per digit d, in the thread that owns it.  s_a, s_b: kThreads words each; all threads call.
+template <typename F>
+__device__ __forceinline__ void digit_excl_scan(const unsigned* s_cnt, int nb, unsigned* s_a, unsigned* s_b, unsigned* s_wsum, unsigned* s_carry, F&& each) {
+  const int t = threadIdx.x;
+  unsigned carry = 0;
+  for (int h = 0; h * kThreads < nb; h++) {
+    const int d = t + h * kThreads;
+    s_a[t] = d < nb ? s_cnt[d] : 0u;
+    __syncthreads();
+    block_excl_scan(s_a, s_b, s_wsum, kThreads);
+    if (d < nb) each(d, carry + s_b[t]);
+    if (t == kThreads - 1) *s_carry = s_b[t] + s_a[t];
+    __syncthreads();
+    carry += *s_carry;
+    __syncthreads();
+  }
+}
+
+// ---- a staged tile read back (the un-permute kernels).  Thread t owns bin t (nb ≤ kMaxBins): cnt = the bin's records in the tile —
+// or in a group of consecutive tiles, whose runs lie one after the other inside a bin: the caller sums — and toff = the global
+// position of the first of them.  Afterwards s_start[b] = staged position of bin b's first record and s_goff[b] + staged position
+// = global position.  All threads call; LDS written before the call is visible after it.
+__device__ __forceinline__ void tile_bin_offsets(unsigned cnt, unsigned toff, int nb, unsigned* s_cnt, unsigned* s_start, unsigned* s_goff, unsigned* s_wsum) {
+  const int t = threadIdx.x;
+  s_cnt[t] = t < nb ? cnt : 0u;
+  __syncthreads();
+  block_excl_scan(s_cnt, s_start, s_wsum, nb);
+  if (t < nb) s_goff[t] = toff - s_start[t];
+  __syncthreads();
+}
+// The bins of the thread's ROWS staged positions first_pos + k · kThreads + threadIdx.x → lo[k].  A position's bin is the LAST b
+// with s_start[b] ≤ position: empty bins share their start with the next one, and the last of them is the one that has records.
+// 2^STEPS ≥ nb.  The ROWS searches are independent, so their LDS reads overlap (the step loop stays rolled, the rows unrolled).
+template <int ROWS, int STEPS>
+__device__ __forceinline__ void bin_of_staged(const unsigned* s_start, int nb, int first_pos, int (&bin)[ROWS]) {
+  int lo[ROWS], hi[ROWS];
+#pragma unroll
+  for (int k = 0; k < ROWS; k++) { lo[k] = 0; hi[k] = nb - 1; }
+#pragma unroll 1
+  for (int step = 0; step < STEPS; step++) {
+#pragma unroll
+    for (int k = 0; k < ROWS; k++) {
+      const int mid = (lo[k] + hi[k] + 1) >> 1;
+      const bool le = s_start[mid] <= (unsigned)(first_pos + k * kThreads + threadIdx.x);
+      lo[k] = le ? mid : lo[k];
+      hi[k] = le ? hi[k] : mid - 1;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < ROWS; k++) bin[k] = lo[k];
+}
+constexpr int kMaxBinSteps = 10;   // 2^10 = kMaxBins
+// s_out[0 .. count) → out[base .. base + count), ROWS per thread, coalesced
+template <int ROWS, typename T>
+__device__ __forceinline__ void store_staged(const T* s_out, int count, T* __restrict__ out, int64_t base) {
+#pragma unroll
+  for (int k = 0; k < ROWS; k++) {
+    const int i = k * kThreads + threadIdx.x;
+    if (i < count) __builtin_nontemporal_store(s_out[i], &out[base + i]);
+  }
 }
 
 // ---- the offsets table.  toffs[tile][bin] = global position of the tile's first record of that bin = (records of
@@ -109,6 +180,19 @@ __global__ __launch_bounds__(kMaxBins) void tile_offs_kernel(const unsigned* __r
     toffs[t * nb + b] = run;
     run += cnt_tm[t * nb + b];
   }
+}
+
+// count table → offsets table and bin starts: (a), (b), (c) on the context's stream.  gsum: ceil(ntiles / kGroupTiles) · nb words.
+inline int launch_tile_offsets(ah_ctx* c, const unsigned* cnt_tm, int nb, int64_t ntiles, int64_t n, unsigned* gsum, unsigned* toffs, unsigned* binstart,
+                               unsigned long long* mb = nullptr, unsigned long long seq = 0) {
+  const int64_t ngroups = ah_ceil_div(ntiles, kGroupTiles);
+  colsum_kernel<<<(unsigned)ngroups, kMaxBins, 0, c->stream>>>(cnt_tm, nb, ntiles, gsum);
+  AH_LAUNCH_CHECK(c);
+  bin_prefix_kernel<<<1, kMaxBins, 0, c->stream>>>(gsum, nb, ngroups, n, binstart, mb, seq);
+  AH_LAUNCH_CHECK(c);
+  tile_offs_kernel<<<(unsigned)ngroups, kMaxBins, 0, c->stream>>>(cnt_tm, gsum, nb, ntiles, toffs);
+  AH_LAUNCH_CHECK(c);
+  return AH_OK;
 }
 
 }  // namespace

@@ -231,6 +231,14 @@ int ah_scratch_reserve(ah_ctx* ctx, size_t nbytes, void** out);
 // live: sort, group-by, var-length take.  One reservation per top-level call, carved by the caller; the block is
 // reused by the next call in stream order (no hipMalloc / hipFree — each maps and unmaps the whole range — per call).
 int ah_temp_reserve(ah_ctx* ctx, size_t nbytes, void** out);
+// The carving of such a block: every piece starts on a 256-byte boundary.  A caller sums ah_pad(bytes) of its pieces into the
+// size it reserves and then takes them in the same order.
+static inline constexpr size_t ah_pad(size_t b) { return (b + 255) & ~(size_t)255; }
+struct TempCarver {
+  uint8_t* base = nullptr;
+  size_t used = 0;
+  uint8_t* take(size_t b) { uint8_t* q = base + used; used += ah_pad(b); return q; }
+};
 // internal (ah_bitmap.hip): popcount of bits [off, off+nbits) into *total_dev (8 bytes,
 // device), enqueued on the compute stream; uses dscalars[16..] as partials — no scratch.
 int ah_popcount_async(ah_ctx* ctx, const uint8_t* bits, int64_t off, int64_t nbits, unsigned long long* total_dev);

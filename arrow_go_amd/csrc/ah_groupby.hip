@@ -807,27 +807,15 @@ struct GsRecords {   // level 2 reads level 1's output
 };
 
 template <typename SRC>
-__global__ __launch_bounds__(kThreads) void gs_hist_kernel(SRC src, int64_t n, const unsigned* __restrict__ pstart, int nparents, int lb, int shift,
-                                                            unsigned mask, int nb, unsigned* __restrict__ cnt) {
-  __shared__ unsigned s_h[kMaxNb2];
-  __shared__ unsigned s_cnt[kThreads], s_start[kThreads], s_wsum[kThreads / 64];
-  __shared__ int s_pick;
-  const TileRange r = ms_tile(pstart, nparents, n, s_cnt, s_start, s_wsum, &s_pick);
-  if (r.parent < 0) return;
-  for (int b = threadIdx.x; b < nb; b += kThreads) s_h[b] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < kMsRows; u++) {
-    const int64_t i = r.lo + u * kThreads + threadIdx.x;
-    if (i < r.hi) {
-      unsigned long long k, v; unsigned rw;
-      src.load(i, &k, &v, &rw);
-      atomicAdd(&s_h[(gs_bucket(k, rw & kKeyNull, lb) >> shift) & mask], 1u);
-    }
+struct GsDigit {   // tile_hist_kernel's view of either level (ah_msd.h)
+  static constexpr int kMaxDigits = kMaxNb2;
+  SRC src; int lb, shift; unsigned mask;
+  __device__ __forceinline__ unsigned digit(int64_t i, int) const {
+    unsigned long long k, v; unsigned rw;
+    src.load(i, &k, &v, &rw);
+    return (gs_bucket(k, rw & kKeyNull, lb) >> shift) & mask;
   }
-  __syncthreads();
-  for (int b = threadIdx.x; b < nb; b += kThreads) cnt[r.id * nb + b] = s_h[b];
-}
+};
 
 // RES (level 2 of the two-level cut, no histogram pass in front of it): child partition c = parent · nb + digit owns the FIXED region
 // [c · cap, (c + 1) · cap) of the record arrays; a tile reserves its run of every digit with one returning atomicAdd on the child's
@@ -889,35 +877,23 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8, 8))
     if ((t & 63) == 0) { s_max[t >> 6] = vmax; s_imin[t >> 6] = vimin; }
   }
   __syncthreads();
-  unsigned carry = 0;
-  for (int h = 0; h * kThreads < nb; h++) {   // exclusive scan over nb ≤ 2048 digit counts, 1024 at a time
-    s_a[t] = t + h * kThreads < nb ? s_cnt[t + h * kThreads] : 0u;
-    __syncthreads();
-    block_excl_scan(s_a, s_b, s_wsum, kThreads);
-    if (t + h * kThreads < nb) {
-      const int d = t + h * kThreads;
-      const unsigned st = carry + s_b[t];
-      s_start[d] = st;
-      if (RES) {
-        const unsigned cn = s_cnt[d];
-        unsigned go = trash_base;
-        if (cn) {
-          const unsigned parent = sub8 ? (((unsigned)r.parent >> 6) << 3) | ((unsigned)r.parent & 7u) : (unsigned)r.parent;
-          const unsigned child = parent * (unsigned)nb + (unsigned)d;
-          const unsigned at = atomicAdd(&cursor[child], cn);
-          if (at + cn <= cap) go = child * cap + at - st;   // (mod 2^32: a region may start below the tile's own prefix)
-          else atomicOr(redo, 4u);
-        }
-        s_goff[d] = go;
-      } else {
-        s_goff[d] = toffs[r.id * nb + d] - st;
+  digit_excl_scan(s_cnt, nb, s_a, s_b, s_wsum, &s_carry, [&](int d, unsigned st) {
+    s_start[d] = st;
+    if (RES) {
+      const unsigned cn = s_cnt[d];
+      unsigned go = trash_base;
+      if (cn) {
+        const unsigned parent = sub8 ? (((unsigned)r.parent >> 6) << 3) | ((unsigned)r.parent & 7u) : (unsigned)r.parent;
+        const unsigned child = parent * (unsigned)nb + (unsigned)d;
+        const unsigned at = atomicAdd(&cursor[child], cn);
+        if (at + cn <= cap) go = child * cap + at - st;   // (mod 2^32: a region may start below the tile's own prefix)
+        else atomicOr(redo, 4u);
       }
+      s_goff[d] = go;
+    } else {
+      s_goff[d] = toffs[r.id * nb + d] - st;
     }
-    if (t == kThreads - 1) s_carry = s_b[t] + s_a[t];
-    __syncthreads();
-    carry += s_carry;
-    __syncthreads();
-  }
+  });
   if (RANGE && tile_max && t == 0) {
     unsigned long long x = s_max[0];
     unsigned xi = s_imin[0];
@@ -1152,7 +1128,6 @@ static int gs_groupby(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t
                       int32_t* out_null_group, int* used) {
   *used = 0;
   if (n < ((int64_t)1 << 22) || n > ((int64_t)1 << 27)) return AH_OK;   // 2^27 rows = 2^21 buckets of 64 = 1024 parents × 2048
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   int lb = 0;
   while (((int64_t)64 << lb) < n) lb++;
   const int lb2 = lb >= 20 ? lb - 10 : lb - lb / 2;
@@ -1161,33 +1136,31 @@ static int gs_groupby(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t
   const int64_t ntiles = ah_ceil_div(n, kMsTile), ngrp = ah_ceil_div(ntiles, kGroupTiles), nvt = ((ntiles + nb1 + 7) / 8) * 8;
   const unsigned grid1 = (unsigned)(((ntiles + 7) / 8) * 8);
   const int64_t nwords = ah_ceil_div(n, 64), nrt = rank_tiles(nwords);
-  const size_t need = pad((size_t)n * 8) * 4 + pad((size_t)n * 4) * 3 + pad((size_t)ntiles * nb1 * 4) * 2 + pad((size_t)ngrp * nb1 * 4) + pad((size_t)(nb1 + 1) * 4) +
-                      pad((size_t)nvt * nb2 * 4) * 2 + pad(((size_t)nbuckets + 1) * 4) + pad((size_t)ntiles * 16) + pad((size_t)nwords * 8) + pad((size_t)nwords * 4) +
-                      pad((size_t)nrt * 4) + pad((size_t)nrt * 8);
-  uint8_t* base;
-  int rc = ah_temp_reserve(c, need, (void**)&base);
+  const size_t need = ah_pad((size_t)n * 8) * 4 + ah_pad((size_t)n * 4) * 3 + ah_pad((size_t)ntiles * nb1 * 4) * 2 + ah_pad((size_t)ngrp * nb1 * 4) + ah_pad((size_t)(nb1 + 1) * 4) +
+                      ah_pad((size_t)nvt * nb2 * 4) * 2 + ah_pad(((size_t)nbuckets + 1) * 4) + ah_pad((size_t)ntiles * 16) + ah_pad((size_t)nwords * 8) + ah_pad((size_t)nwords * 4) +
+                      ah_pad((size_t)nrt * 4) + ah_pad((size_t)nrt * 8);
+  TempCarver tc;
+  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
   if (rc != AH_OK) { c->err[0] = 0; return AH_OK; }   // these temporaries do not fit: *used stays 0 and the caller's id-based path (a fraction of them) answers
-  size_t off = 0;
-  auto take = [&](size_t b) { uint8_t* q = base + off; off += pad(b); return q; };
-  unsigned long long* pkeys = (unsigned long long*)take((size_t)n * 8);
-  unsigned long long* pvals = (unsigned long long*)take((size_t)n * 8);
-  unsigned long long* qkeys = (unsigned long long*)take((size_t)n * 8);
-  unsigned long long* qvals = (unsigned long long*)take((size_t)n * 8);
-  unsigned* prows = (unsigned*)take((size_t)n * 4);
-  unsigned* qrows = (unsigned*)take((size_t)n * 4);
-  unsigned* g_cnt = (unsigned*)take((size_t)n * 4);
-  unsigned* cnt1 = (unsigned*)take((size_t)ntiles * nb1 * 4);
-  unsigned* toffs1 = (unsigned*)take((size_t)ntiles * nb1 * 4);
-  unsigned* gsum = (unsigned*)take((size_t)ngrp * nb1 * 4);
-  unsigned* pstart = (unsigned*)take((size_t)(nb1 + 1) * 4);
-  unsigned* cnt2 = (unsigned*)take((size_t)nvt * nb2 * 4);
-  unsigned* toffs2 = (unsigned*)take((size_t)nvt * nb2 * 4);
-  unsigned* bstart = (unsigned*)take(((size_t)nbuckets + 1) * 4);
-  unsigned long long* tile_max = (unsigned long long*)take((size_t)ntiles * 16);
-  unsigned long long* firsts = (unsigned long long*)take((size_t)nwords * 8);
-  unsigned* wordprefix = (unsigned*)take((size_t)nwords * 4);
-  int* tilecnt = (int*)take((size_t)nrt * 4);
-  int64_t* tileoff = (int64_t*)take((size_t)nrt * 8);
+  unsigned long long* pkeys = (unsigned long long*)tc.take((size_t)n * 8);
+  unsigned long long* pvals = (unsigned long long*)tc.take((size_t)n * 8);
+  unsigned long long* qkeys = (unsigned long long*)tc.take((size_t)n * 8);
+  unsigned long long* qvals = (unsigned long long*)tc.take((size_t)n * 8);
+  unsigned* prows = (unsigned*)tc.take((size_t)n * 4);
+  unsigned* qrows = (unsigned*)tc.take((size_t)n * 4);
+  unsigned* g_cnt = (unsigned*)tc.take((size_t)n * 4);
+  unsigned* cnt1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
+  unsigned* toffs1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
+  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * nb1 * 4);
+  unsigned* pstart = (unsigned*)tc.take((size_t)(nb1 + 1) * 4);
+  unsigned* cnt2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
+  unsigned* toffs2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
+  unsigned* bstart = (unsigned*)tc.take(((size_t)nbuckets + 1) * 4);
+  unsigned long long* tile_max = (unsigned long long*)tc.take((size_t)ntiles * 16);
+  unsigned long long* firsts = (unsigned long long*)tc.take((size_t)nwords * 8);
+  unsigned* wordprefix = (unsigned*)tc.take((size_t)nwords * 4);
+  int* tilecnt = (int*)tc.take((size_t)nrt * 4);
+  int64_t* tileoff = (int64_t*)tc.take((size_t)nrt * 8);
   unsigned long long* absmax = (unsigned long long*)&c->dscalars[28];   // [28], [29]: the value range (ah_hashing.h)
   unsigned* oversize = (unsigned*)&c->dscalars[21];
   unsigned long long* total = (unsigned long long*)&c->dscalars[22];
@@ -1198,14 +1171,9 @@ static int gs_groupby(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t
   AH_HIP(c, hipMemsetAsync(firsts, 0, (size_t)nwords * 8, c->stream));
   GsColumns col{(const unsigned long long*)keys, kvalid, koff, (const unsigned long long*)vals, vvalid, voff};
   // level 1
-  gs_hist_kernel<GsColumns><<<grid1, kThreads, 0, c->stream>>>(col, n, nullptr, 1, lb, lb2, (unsigned)(nb1 - 1), nb1, cnt1);
+  tile_hist_kernel<GsDigit<GsColumns>><<<grid1, kThreads, 0, c->stream>>>(GsDigit<GsColumns>{col, lb, lb2, (unsigned)(nb1 - 1)}, n, nullptr, 1, nb1, cnt1);
   AH_LAUNCH_CHECK(c);
-  colsum_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt1, nb1, ntiles, gsum);
-  AH_LAUNCH_CHECK(c);
-  bin_prefix_kernel<<<1, kMaxBins, 0, c->stream>>>(gsum, nb1, ngrp, n, pstart);
-  AH_LAUNCH_CHECK(c);
-  tile_offs_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt1, gsum, nb1, ntiles, toffs1);
-  AH_LAUNCH_CHECK(c);
+  if ((rc = launch_tile_offsets(c, cnt1, nb1, ntiles, n, gsum, toffs1, pstart)) != AH_OK) return rc;
   gs_scatter_kernel<GsColumns><<<grid1, kThreads, 0, c->stream>>>(col, n, nullptr, 1, lb, lb2, (unsigned)(nb1 - 1), nb1, toffs1, pkeys, pvals, prows,
                                                                   is_f64 ? tile_max : nullptr);
   AH_LAUNCH_CHECK(c);
@@ -1217,7 +1185,7 @@ static int gs_groupby(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t
   }
   // level 2, parent by parent
   GsRecords rec{pkeys, pvals, prows};
-  gs_hist_kernel<GsRecords><<<(unsigned)nvt, kThreads, 0, c->stream>>>(rec, n, pstart, nb1, lb, 0, (unsigned)(nb2 - 1), nb2, cnt2);
+  tile_hist_kernel<GsDigit<GsRecords>><<<(unsigned)nvt, kThreads, 0, c->stream>>>(GsDigit<GsRecords>{rec, lb, 0, (unsigned)(nb2 - 1)}, n, pstart, nb1, nb2, cnt2);
   AH_LAUNCH_CHECK(c);
   ms_offs2_kernel<<<(unsigned)nb1, kThreads, 0, c->stream>>>(cnt2, pstart, nb1, nb2, toffs2, bstart, n);
   AH_LAUNCH_CHECK(c);
@@ -1265,7 +1233,6 @@ static int gb2_groupby(ah_ctx* c, int is_f64, int lp, const uint64_t* keys, cons
   // level-1 kernel takes 0.64–0.72) and the second level tiles those regions
   const bool xreg = reserve2 && hist != nullptr;
   *used = 0;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const int lb2 = lp - lp / 2;
   const int nb2 = 1 << lb2, nb1 = 1 << (lp - lb2);
   const int64_t P = (int64_t)1 << lp;
@@ -1286,50 +1253,48 @@ static int gb2_groupby(ah_ctx* c, int is_f64, int lp, const uint64_t* keys, cons
   const unsigned cap1 = (unsigned)((((n / nb1) * 9 / 8 + kMsTile) + 15) & ~(int64_t)15);
   const int64_t xcap_rows = n + n / 2 + (int64_t)nb1 * kGbRegions * 96;   // gb_layout_kernel's regions (as in gb_cut_aggregate)
   const int64_t prows_n = xreg ? xcap_rows + kGbTile : (reserve2 ? nb1 * (int64_t)cap1 + kMsTile : n);
-  const size_t plevel = pad((size_t)prows_n * 8) * 2 + pad((size_t)prows_n * 4);
-  const size_t level = plevel > pad(nrec * sizeof(GbRec)) ? plevel : pad(nrec * sizeof(GbRec));   // … and the coarse records lie over them
+  const size_t plevel = ah_pad((size_t)prows_n * 8) * 2 + ah_pad((size_t)prows_n * 4);
+  const size_t level = plevel > ah_pad(nrec * sizeof(GbRec)) ? plevel : ah_pad(nrec * sizeof(GbRec));   // … and the coarse records lie over them
   const size_t extra = 0;
   // second level's record arrays: dense (n rows) behind the offsets table; P regions of cap2 rows (1.25 × the even share) + kMsTile spare rows otherwise
   const unsigned cap2 = (unsigned)((((n / P) * 5 / 4 + 64) + 15) & ~(int64_t)15);
   const int64_t qrows_n = reserve2 ? P * (int64_t)cap2 + kMsTile : n;
-  const size_t qlevel = pad((size_t)qrows_n * 8) * 2 + pad((size_t)qrows_n * 4);
+  const size_t qlevel = ah_pad((size_t)qrows_n * 8) * 2 + ah_pad((size_t)qrows_n * 4);
   const size_t qblock = qlevel > level + extra ? qlevel : level + extra;
-  const size_t need = (level + extra) + qblock + pad((size_t)ntiles * nb1 * 4) * 2 + pad((size_t)ngrp * nb1 * 4) + pad((size_t)(nb1 + 1) * 4) +
-                      pad((size_t)nvt * nb2 * 4) * 2 + pad(((size_t)P + 1) * 4) + pad((size_t)ntiles * 16) + pad((size_t)kRecMaxBins * 4) + pad((size_t)nfine * 4) +
-                      pad((size_t)nfine * 8) + pad(((size_t)P + 1) * 4) + pad((size_t)(nb1 * kGbRegions + 1) * 4) * 5;
-  uint8_t* base;
-  int rc = ah_temp_reserve(c, need, (void**)&base);
+  const size_t need = (level + extra) + qblock + ah_pad((size_t)ntiles * nb1 * 4) * 2 + ah_pad((size_t)ngrp * nb1 * 4) + ah_pad((size_t)(nb1 + 1) * 4) +
+                      ah_pad((size_t)nvt * nb2 * 4) * 2 + ah_pad(((size_t)P + 1) * 4) + ah_pad((size_t)ntiles * 16) + ah_pad((size_t)kRecMaxBins * 4) + ah_pad((size_t)nfine * 4) +
+                      ah_pad((size_t)nfine * 8) + ah_pad(((size_t)P + 1) * 4) + ah_pad((size_t)(nb1 * kGbRegions + 1) * 4) * 5;
+  TempCarver tc;
+  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
   if (rc != AH_OK) { c->err[0] = 0; return AH_OK; }   // these temporaries do not fit: *used stays 0 and the caller's id-based path (a fraction of them) answers
-  size_t off = 0;
-  auto take = [&](size_t b) { uint8_t* q = base + off; off += pad(b); return q; };
-  uint8_t* pbase = take(level);
+  uint8_t* pbase = tc.take(level);
   unsigned long long* pkeys = (unsigned long long*)pbase;
-  unsigned long long* pvals = (unsigned long long*)(pbase + pad((size_t)prows_n * 8));
-  unsigned* prows = (unsigned*)(pbase + pad((size_t)prows_n * 8) * 2);
-  uint8_t* qbase = take(qblock);
+  unsigned long long* pvals = (unsigned long long*)(pbase + ah_pad((size_t)prows_n * 8));
+  unsigned* prows = (unsigned*)(pbase + ah_pad((size_t)prows_n * 8) * 2);
+  uint8_t* qbase = tc.take(qblock);
   unsigned long long* qkeys = (unsigned long long*)qbase;
-  unsigned long long* qvals = (unsigned long long*)(qbase + pad((size_t)qrows_n * 8));
-  unsigned* qrows = (unsigned*)(qbase + pad((size_t)qrows_n * 8) * 2);
+  unsigned long long* qvals = (unsigned long long*)(qbase + ah_pad((size_t)qrows_n * 8));
+  unsigned* qrows = (unsigned*)(qbase + ah_pad((size_t)qrows_n * 8) * 2);
   GbRec* recs1 = (GbRec*)pkeys;
   GbRec* recs2 = (GbRec*)qkeys;
-  unsigned* cnt1 = (unsigned*)take((size_t)ntiles * nb1 * 4);
-  unsigned* toffs1 = (unsigned*)take((size_t)ntiles * nb1 * 4);
-  unsigned* gsum = (unsigned*)take((size_t)ngrp * nb1 * 4);
-  unsigned* pstart = (unsigned*)take((size_t)(nb1 + 1) * 4);
-  unsigned* cnt2 = (unsigned*)take((size_t)nvt * nb2 * 4);
-  unsigned* toffs2 = (unsigned*)take((size_t)nvt * nb2 * 4);
-  unsigned* bstart = (unsigned*)take(((size_t)P + 1) * 4);
-  unsigned long long* tile_max = (unsigned long long*)take((size_t)ntiles * 16);
-  unsigned* ccursor = (unsigned*)take((size_t)kRecMaxBins * 4);
-  unsigned* fcursor = (unsigned*)take((size_t)nfine * 4);
-  int64_t* fprefix = (int64_t*)take((size_t)nfine * 8);
-  unsigned* cursor2 = (unsigned*)take(((size_t)P + 1) * 4);
+  unsigned* cnt1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
+  unsigned* toffs1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
+  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * nb1 * 4);
+  unsigned* pstart = (unsigned*)tc.take((size_t)(nb1 + 1) * 4);
+  unsigned* cnt2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
+  unsigned* toffs2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
+  unsigned* bstart = (unsigned*)tc.take(((size_t)P + 1) * 4);
+  unsigned long long* tile_max = (unsigned long long*)tc.take((size_t)ntiles * 16);
+  unsigned* ccursor = (unsigned*)tc.take((size_t)kRecMaxBins * 4);
+  unsigned* fcursor = (unsigned*)tc.take((size_t)nfine * 4);
+  int64_t* fprefix = (int64_t*)tc.take((size_t)nfine * 8);
+  unsigned* cursor2 = (unsigned*)tc.take(((size_t)P + 1) * 4);
   const int nsub = nb1 * kGbRegions;   // ≤ 512
-  unsigned* cursor1 = (unsigned*)take((size_t)(nsub + 1) * 4);
-  unsigned* pend = (unsigned*)take((size_t)(nsub + 1) * 4);
-  unsigned* sstart = (unsigned*)take((size_t)(nsub + 1) * 4);
-  unsigned* rstart1 = (unsigned*)take((size_t)(nsub + 1) * 4);
-  unsigned* rcap1 = (unsigned*)take((size_t)(nsub + 1) * 4);
+  unsigned* cursor1 = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
+  unsigned* pend = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
+  unsigned* sstart = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
+  unsigned* rstart1 = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
+  unsigned* rcap1 = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
   GbTable gt{nullptr, nullptr, nullptr, nullptr, nullptr};   // no tables: the groups leave the aggregate pass as records
   unsigned long long* absmax = (unsigned long long*)&c->dscalars[28];   // [28], [29]: the value range (ah_hashing.h)
   unsigned* overflow = (unsigned*)&c->dscalars[21];
@@ -1340,8 +1305,8 @@ static int gb2_groupby(ah_ctx* c, int is_f64, int lp, const uint64_t* keys, cons
     f.njobs = 5;
     f.p[0] = (uint4*)&c->dscalars[20]; f.n16[0] = 1; f.v[0] = 0u;                 // [20] unused, [21] overflow
     f.p[1] = (uint4*)&c->dscalars[28]; f.n16[1] = 1; f.v[1] = 0u;                 // [28], [29] value range
-    f.p[2] = (uint4*)ccursor; f.n16[2] = (pad((size_t)kRecMaxBins * 4) + pad((size_t)nfine * 4)) / 16; f.v[2] = 0u;
-    f.p[3] = (uint4*)cursor2; f.n16[3] = (pad(((size_t)P + 1) * 4) + pad((size_t)(nsub + 1) * 4)) / 16; f.v[3] = 0u;   // the children's and the parents' cursors (adjacent)
+    f.p[2] = (uint4*)ccursor; f.n16[2] = (ah_pad((size_t)kRecMaxBins * 4) + ah_pad((size_t)nfine * 4)) / 16; f.v[2] = 0u;
+    f.p[3] = (uint4*)cursor2; f.n16[3] = (ah_pad(((size_t)P + 1) * 4) + ah_pad((size_t)(nsub + 1) * 4)) / 16; f.v[3] = 0u;   // the children's and the parents' cursors (adjacent)
     f.p[4] = (uint4*)&c->dscalars[22]; f.n16[4] = 1; f.v[4] = 0u;                 // [22] total, [23] …
     f.ones = (unsigned long long*)null_id;                                         // … null id: none (the last job's first word: the same thread)
     gb_fill_kernel<<<64, 256, 0, c->stream>>>(f);
@@ -1375,14 +1340,9 @@ static int gb2_groupby(ah_ctx* c, int is_f64, int lp, const uint64_t* keys, cons
     gs_regions_kernel<<<1, 64, 0, c->stream>>>(cursor1, nb1, cap1, pstart, pend, overflow, is_f64 ? absmax : nullptr);   // nb1 ≤ 64
     AH_LAUNCH_CHECK(c);
   } else {
-  gs_hist_kernel<GsColumns><<<grid1, kThreads, 0, c->stream>>>(col, n, nullptr, 1, lp, lb2, (unsigned)(nb1 - 1), nb1, cnt1);
+  tile_hist_kernel<GsDigit<GsColumns>><<<grid1, kThreads, 0, c->stream>>>(GsDigit<GsColumns>{col, lp, lb2, (unsigned)(nb1 - 1)}, n, nullptr, 1, nb1, cnt1);
   AH_LAUNCH_CHECK(c);
-  colsum_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt1, nb1, ntiles, gsum);
-  AH_LAUNCH_CHECK(c);
-  bin_prefix_kernel<<<1, kMaxBins, 0, c->stream>>>(gsum, nb1, ngrp, n, pstart);
-  AH_LAUNCH_CHECK(c);
-  tile_offs_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt1, gsum, nb1, ntiles, toffs1);
-  AH_LAUNCH_CHECK(c);
+  if ((rc = launch_tile_offsets(c, cnt1, nb1, ntiles, n, gsum, toffs1, pstart)) != AH_OK) return rc;
   gs_scatter_kernel<GsColumns><<<grid1, kThreads, 0, c->stream>>>(col, n, nullptr, 1, lp, lb2, (unsigned)(nb1 - 1), nb1, toffs1, pkeys, pvals, prows,
                                                                   is_f64 ? tile_max : nullptr);
   AH_LAUNCH_CHECK(c);
@@ -1400,7 +1360,7 @@ static int gb2_groupby(ah_ctx* c, int is_f64, int lp, const uint64_t* keys, cons
                                                                        cursor2, cap2, (unsigned)(P * (int64_t)cap2), overflow, pend, l2_sub8);
     AH_LAUNCH_CHECK(c);
   } else {
-    gs_hist_kernel<GsRecords><<<(unsigned)nvt, kThreads, 0, c->stream>>>(rec, n, pstart, nb1, lp, 0, (unsigned)(nb2 - 1), nb2, cnt2);
+    tile_hist_kernel<GsDigit<GsRecords>><<<(unsigned)nvt, kThreads, 0, c->stream>>>(GsDigit<GsRecords>{rec, lp, 0, (unsigned)(nb2 - 1)}, n, pstart, nb1, nb2, cnt2);
     AH_LAUNCH_CHECK(c);
     ms_offs2_kernel<<<(unsigned)nb1, kThreads, 0, c->stream>>>(cnt2, pstart, nb1, nb2, toffs2, bstart, n);
     AH_LAUNCH_CHECK(c);
@@ -1869,36 +1829,33 @@ static int gb_direct(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t*
   // a seed table at or beyond the admission limit must never reach gb_lds_slot, whose probe loop relies on empty slots being there
   // (the caller's "≤ 2800 distinct" gate already says so; this is the guard at the place that would hang)
   if (seed_keys && seed_used >= (unsigned)kSoftLimit) { seed_keys = nullptr; seed_used = 0; }
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const int64_t nslots = kGStride;
   const unsigned dgrid = (unsigned)ah_ceil_div(n, (int64_t)1 << kChunkLog2);
   const size_t stage_rows = seed_keys ? (size_t)dgrid * kLSlots : 0;
-  const size_t need = pad((size_t)nslots * 8) * 3 + pad((size_t)nslots * 4) * 2 + pad((size_t)dgrid * 8) + pad(stage_rows * 8) * 2 + pad(stage_rows * 4) * 2 +
-                      pad((size_t)kLSlots * 8) * 3 + pad((size_t)kLSlots * 4) * 2;
-  uint8_t* base;
-  int rc = ah_temp_reserve(c, need, (void**)&base);
+  const size_t need = ah_pad((size_t)nslots * 8) * 3 + ah_pad((size_t)nslots * 4) * 2 + ah_pad((size_t)dgrid * 8) + ah_pad(stage_rows * 8) * 2 + ah_pad(stage_rows * 4) * 2 +
+                      ah_pad((size_t)kLSlots * 8) * 3 + ah_pad((size_t)kLSlots * 4) * 2;
+  TempCarver tc;
+  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
   if (rc != AH_OK) { c->err[0] = 0; return AH_OK; }   // these temporaries do not fit: *used stays 0 and the caller's id-based path (a fraction of them) answers
-  size_t off = 0;
-  auto take = [&](size_t b) { uint8_t* q = base + off; off += pad(b); return q; };
   GbTable gt;
-  gt.key = (unsigned long long*)take((size_t)nslots * 8);
-  gt.lo = (unsigned long long*)take((size_t)nslots * 8);
-  gt.hi = (unsigned long long*)take((size_t)nslots * 8);
-  gt.cnt = (unsigned*)take((size_t)nslots * 4);
-  gt.first = (unsigned*)take((size_t)nslots * 4);
-  unsigned* tile_range = (unsigned*)take((size_t)dgrid * 8);
+  gt.key = (unsigned long long*)tc.take((size_t)nslots * 8);
+  gt.lo = (unsigned long long*)tc.take((size_t)nslots * 8);
+  gt.hi = (unsigned long long*)tc.take((size_t)nslots * 8);
+  gt.cnt = (unsigned*)tc.take((size_t)nslots * 4);
+  gt.first = (unsigned*)tc.take((size_t)nslots * 4);
+  unsigned* tile_range = (unsigned*)tc.take((size_t)dgrid * 8);
   GbStaging st{nullptr, nullptr, nullptr, nullptr};
   GbTable rt{nullptr, nullptr, nullptr, nullptr, nullptr};
   if (seed_keys) {
-    st.lo = (unsigned long long*)take(stage_rows * 8);
-    st.hi = (unsigned long long*)take(stage_rows * 8);
-    st.cnt = (unsigned*)take(stage_rows * 4);
-    st.first = (unsigned*)take(stage_rows * 4);
-    rt.key = (unsigned long long*)take((size_t)kLSlots * 8);
-    rt.lo = (unsigned long long*)take((size_t)kLSlots * 8);
-    rt.hi = (unsigned long long*)take((size_t)kLSlots * 8);
-    rt.cnt = (unsigned*)take((size_t)kLSlots * 4);
-    rt.first = (unsigned*)take((size_t)kLSlots * 4);
+    st.lo = (unsigned long long*)tc.take(stage_rows * 8);
+    st.hi = (unsigned long long*)tc.take(stage_rows * 8);
+    st.cnt = (unsigned*)tc.take(stage_rows * 4);
+    st.first = (unsigned*)tc.take(stage_rows * 4);
+    rt.key = (unsigned long long*)tc.take((size_t)kLSlots * 8);
+    rt.lo = (unsigned long long*)tc.take((size_t)kLSlots * 8);
+    rt.hi = (unsigned long long*)tc.take((size_t)kLSlots * 8);
+    rt.cnt = (unsigned*)tc.take((size_t)kLSlots * 4);
+    rt.first = (unsigned*)tc.take((size_t)kLSlots * 4);
   }
   unsigned long long* absmax = (unsigned long long*)&c->dscalars[28];   // [28], [29]: the value range (ah_hashing.h)
   unsigned* overflow = (unsigned*)&c->dscalars[21];
@@ -1959,7 +1916,6 @@ static int gb_cut_aggregate(ah_ctx* c, int is_f64, int lp, const unsigned* hist,
                             int64_t* out_first_rows, int64_t* out_ngroups, int32_t* out_null_group, int* used, unsigned* redo) {
   *used = 0;
   *redo = 0;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   unsigned long long* absmax = (unsigned long long*)&c->dscalars[28];   // [28], [29]: the value range (ah_hashing.h)
   unsigned* overflow = (unsigned*)&c->dscalars[21];
   unsigned long long* total = (unsigned long long*)&c->dscalars[22];
@@ -1976,11 +1932,11 @@ static int gb_cut_aggregate(ah_ctx* c, int is_f64, int lp, const unsigned* hist,
   const int nreg = P * kGbRegions;
   // ---- temporaries (one reservation)
   const size_t table = reserve ? 0 : (size_t)P * (size_t)ntiles * 4;
-  const size_t need = pad((size_t)nslots * 8) * 3 + pad((size_t)nslots * 4) * 2 + pad((size_t)nwords * 8) + pad((size_t)nwords * 4) +
-                      pad((size_t)nrt * 4) + pad((size_t)nrt * 8) + pad(table) * 2 + pad((size_t)ngrp * P * 4) + pad((size_t)(P + 1) * 4) +
-                      pad((size_t)rec_rows * 8) * 2 + pad((size_t)rec_rows * 4) + pad((size_t)ntiles * 16) + pad((size_t)(nreg + 1) * 4) * 5;
-  uint8_t* base;
-  int rc = ah_temp_reserve(c, need, (void**)&base);
+  const size_t need = ah_pad((size_t)nslots * 8) * 3 + ah_pad((size_t)nslots * 4) * 2 + ah_pad((size_t)nwords * 8) + ah_pad((size_t)nwords * 4) +
+                      ah_pad((size_t)nrt * 4) + ah_pad((size_t)nrt * 8) + ah_pad(table) * 2 + ah_pad((size_t)ngrp * P * 4) + ah_pad((size_t)(P + 1) * 4) +
+                      ah_pad((size_t)rec_rows * 8) * 2 + ah_pad((size_t)rec_rows * 4) + ah_pad((size_t)ntiles * 16) + ah_pad((size_t)(nreg + 1) * 4) * 5;
+  TempCarver tc;
+  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
   if (rc != AH_OK && reserve) {
     // the regions want 1.5 n rows of records (≈ 30 B/row) where the dense arrays behind a histogram want n (20 B/row): a call that does
     // not fit THAT way is tried once more the other way (redo = 4: the caller runs the call again without the sample's histogram)
@@ -1989,39 +1945,37 @@ static int gb_cut_aggregate(ah_ctx* c, int is_f64, int lp, const unsigned* hist,
     return AH_OK;
   }
   if (rc != AH_OK) return rc;
-  size_t used_b = 0;
-  auto take = [&](size_t b) { uint8_t* q = base + used_b; used_b += pad(b); return q; };
   GbTable gt;
-  gt.key = (unsigned long long*)take((size_t)nslots * 8);
-  gt.lo = (unsigned long long*)take((size_t)nslots * 8);
-  gt.hi = (unsigned long long*)take((size_t)nslots * 8);
-  gt.cnt = (unsigned*)take((size_t)nslots * 4);
-  gt.first = (unsigned*)take((size_t)nslots * 4);
-  unsigned long long* firsts = (unsigned long long*)take((size_t)nwords * 8);
-  unsigned* wordprefix = (unsigned*)take((size_t)nwords * 4);
-  int* tilecnt = (int*)take((size_t)nrt * 4);
-  int64_t* tileoff = (int64_t*)take((size_t)nrt * 8);
-  unsigned* cnt_tm = (unsigned*)take(table);
-  unsigned* toffs = (unsigned*)take(table);
-  unsigned* gsum = (unsigned*)take((size_t)ngrp * P * 4);
-  unsigned* binstart = (unsigned*)take((size_t)(P + 1) * 4);
-  unsigned long long* pkeys = (unsigned long long*)take((size_t)rec_rows * 8);
-  unsigned long long* pvals = (unsigned long long*)take((size_t)rec_rows * 8);
-  unsigned* prows = (unsigned*)take((size_t)rec_rows * 4);
-  unsigned long long* tile_max = (unsigned long long*)take((size_t)ntiles * 16);
-  unsigned* rstart = (unsigned*)take((size_t)(nreg + 1) * 4);
-  unsigned* rcap = (unsigned*)take((size_t)(nreg + 1) * 4);
-  unsigned* cursor = (unsigned*)take((size_t)(nreg + 1) * 4);
-  unsigned* vstart = (unsigned*)take((size_t)(nreg + 1) * 4);
-  unsigned* delta = (unsigned*)take((size_t)(nreg + 1) * 4);
+  gt.key = (unsigned long long*)tc.take((size_t)nslots * 8);
+  gt.lo = (unsigned long long*)tc.take((size_t)nslots * 8);
+  gt.hi = (unsigned long long*)tc.take((size_t)nslots * 8);
+  gt.cnt = (unsigned*)tc.take((size_t)nslots * 4);
+  gt.first = (unsigned*)tc.take((size_t)nslots * 4);
+  unsigned long long* firsts = (unsigned long long*)tc.take((size_t)nwords * 8);
+  unsigned* wordprefix = (unsigned*)tc.take((size_t)nwords * 4);
+  int* tilecnt = (int*)tc.take((size_t)nrt * 4);
+  int64_t* tileoff = (int64_t*)tc.take((size_t)nrt * 8);
+  unsigned* cnt_tm = (unsigned*)tc.take(table);
+  unsigned* toffs = (unsigned*)tc.take(table);
+  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * P * 4);
+  unsigned* binstart = (unsigned*)tc.take((size_t)(P + 1) * 4);
+  unsigned long long* pkeys = (unsigned long long*)tc.take((size_t)rec_rows * 8);
+  unsigned long long* pvals = (unsigned long long*)tc.take((size_t)rec_rows * 8);
+  unsigned* prows = (unsigned*)tc.take((size_t)rec_rows * 4);
+  unsigned long long* tile_max = (unsigned long long*)tc.take((size_t)ntiles * 16);
+  unsigned* rstart = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
+  unsigned* rcap = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
+  unsigned* cursor = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
+  unsigned* vstart = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
+  unsigned* delta = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
   {
     // everything the call starts from, one launch: empty tables (lo, hi, cnt are adjacent), no first rows, the call's scalars
     GbFill f;
     f.njobs = 7;
-    f.p[0] = (uint4*)gt.key; f.n16[0] = pad((size_t)nslots * 8) / 16; f.v[0] = 0xFFFFFFFFu;
-    f.p[1] = (uint4*)gt.lo; f.n16[1] = (pad((size_t)nslots * 8) * 2 + pad((size_t)nslots * 4)) / 16; f.v[1] = 0u;
-    f.p[2] = (uint4*)gt.first; f.n16[2] = pad((size_t)nslots * 4) / 16; f.v[2] = 0xFFFFFFFFu;
-    f.p[3] = (uint4*)firsts; f.n16[3] = pad((size_t)nwords * 8) / 16; f.v[3] = 0u;
+    f.p[0] = (uint4*)gt.key; f.n16[0] = ah_pad((size_t)nslots * 8) / 16; f.v[0] = 0xFFFFFFFFu;
+    f.p[1] = (uint4*)gt.lo; f.n16[1] = (ah_pad((size_t)nslots * 8) * 2 + ah_pad((size_t)nslots * 4)) / 16; f.v[1] = 0u;
+    f.p[2] = (uint4*)gt.first; f.n16[2] = ah_pad((size_t)nslots * 4) / 16; f.v[2] = 0xFFFFFFFFu;
+    f.p[3] = (uint4*)firsts; f.n16[3] = ah_pad((size_t)nwords * 8) / 16; f.v[3] = 0u;
     f.p[4] = (uint4*)&c->dscalars[20]; f.n16[4] = 1; f.v[4] = 0u;                 // [20] unused, [21] overflow / redo flags
     f.p[5] = (uint4*)&c->dscalars[28]; f.n16[5] = 1; f.v[5] = 0u;                 // [28], [29] value range
     f.p[6] = (uint4*)&c->dscalars[22]; f.n16[6] = 1; f.v[6] = 0u;                 // [22] total, [23] …
@@ -2045,12 +1999,7 @@ static int gb_cut_aggregate(ah_ctx* c, int is_f64, int lp, const unsigned* hist,
   } else {
   gb_hist_kernel<<<tgrid, kGbHistThreads, 0, c->stream>>>(k64, kvalid, koff, n, lp, P, ntiles, cnt_tm);
   AH_LAUNCH_CHECK(c);
-  colsum_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt_tm, P, ntiles, gsum);
-  AH_LAUNCH_CHECK(c);
-  bin_prefix_kernel<<<1, kMaxBins, 0, c->stream>>>(gsum, P, ngrp, n, binstart);
-  AH_LAUNCH_CHECK(c);
-  tile_offs_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt_tm, gsum, P, ntiles, toffs);
-  AH_LAUNCH_CHECK(c);
+  if ((rc = launch_tile_offsets(c, cnt_tm, P, ntiles, n, gsum, toffs, binstart)) != AH_OK) return rc;
   gb_scatter_kernel<true><<<tgrid, kThreads, 0, c->stream>>>(k64, kvalid, koff, v64, vvalid, voff, n, lp, P, ntiles, toffs, pkeys, pvals, prows,
                                                        is_f64 ? tile_max : nullptr);
   AH_LAUNCH_CHECK(c);

@@ -391,75 +391,18 @@ __global__ __launch_bounds__(kThreads) void enc_resolve_kernel(const unsigned sh
   }
 }
 
-// ---- 6: ids back to row order, tile by tile -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void enc_unpermute_kernel(const int* __restrict__ rec_id, const unsigned* __restrict__ prows,
-                                                                  const unsigned* __restrict__ cnt_tm, const unsigned* __restrict__ toffs, int nb,
-                                                                  int64_t ntiles, int64_t n, int32_t* __restrict__ out_ids) {
-  __shared__ unsigned s_cnt[kMaxBins], s_start[kMaxBins], s_goff[kMaxBins], s_wsum[kThreads / 64];
-  __shared__ int s_out[kGbTile];
-  const int64_t tile = xcd_contiguous_tile(ntiles);
-  if (tile < 0) return;
-  unsigned excl = 0;
-  s_cnt[threadIdx.x] = 0;
-  if ((int)threadIdx.x < nb) {
-    s_cnt[threadIdx.x] = cnt_tm[tile * nb + threadIdx.x];
-    excl = toffs[tile * nb + threadIdx.x];
-  }
-  __syncthreads();
-  block_excl_scan(s_cnt, s_start, s_wsum, nb);
-  if ((int)threadIdx.x < nb) s_goff[threadIdx.x] = excl - s_start[threadIdx.x];
-  __syncthreads();
-  const int64_t base = tile * kGbTile;
-  const int tile_n = n - base >= kGbTile ? kGbTile : (int)(n - base);
-  // staged position lp → its partition = the LAST b with s_start[b] ≤ lp (empty partitions share their start with the next one)
-  int lo[kGbRows], hi[kGbRows];
-#pragma unroll
-  for (int k = 0; k < kGbRows; k++) { lo[k] = 0; hi[k] = nb - 1; }
-#pragma unroll 1
-  for (int step = 0; step < 10; step++) {   // 2^10 = kMaxBins
-#pragma unroll
-    for (int k = 0; k < kGbRows; k++) {
-      const int mid = (lo[k] + hi[k] + 1) >> 1;
-      const bool le = s_start[mid] <= (unsigned)(k * kThreads + threadIdx.x);
-      lo[k] = le ? mid : lo[k];
-      hi[k] = le ? hi[k] : mid - 1;
-    }
-  }
-  int id[kGbRows];
-  unsigned rw[kGbRows];
-#pragma unroll
-  for (int k = 0; k < kGbRows; k++) {
-    const int lp = k * kThreads + threadIdx.x;
-    id[k] = 0; rw[k] = 0;
-    if (lp < tile_n) {
-      const int64_t e = (int64_t)s_goff[lo[k]] + lp;
-      id[k] = __builtin_nontemporal_load(&rec_id[e]);
-      rw[k] = __builtin_nontemporal_load(&prows[e]);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kGbRows; k++)
-    if (k * kThreads + (int)threadIdx.x < tile_n) s_out[(int64_t)(rw[k] & kRowMask) - base] = id[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kGbRows; k++) {
-    const int i = k * kThreads + threadIdx.x;
-    if (i < tile_n) __builtin_nontemporal_store(s_out[i], &out_ids[base + i]);
-  }
-}
-
-// The same for G CONSECUTIVE tiles per workgroup.  Inside a partition the runs of consecutive tiles lie one after the other, so the
-// group's records of a partition are ONE run G times as long (256 partitions: 16 records = 64 bytes per tile, 256 bytes per group
-// of four) — the per-tile kernel read 64-byte pieces at 2.3 TB/s.  The group's ids are staged in LDS (G · 16 KiB) and leave as whole
-// lines.
+// ---- 6: ids back to row order, G consecutive tiles per workgroup -------------------------------------------------------------------
+// The tile's (group's) runs are found again (tile_bin_offsets, bin_of_staged: ah_bins.h), every record's id is placed at its row in
+// LDS, and the ids leave as whole lines.  Inside a partition the runs of consecutive tiles lie one after the other, so a group's
+// records of a partition are ONE run G times as long (256 partitions: 16 records = 64 bytes per tile, 256 bytes per group of four —
+// with G = 1 the kernel reads 64-byte pieces at 2.3 TB/s).  LDS: G · 16 KiB of ids.
 template <int G>
 __global__ __launch_bounds__(kThreads) void enc_unpermute_group_kernel(const int* __restrict__ rec_id, const unsigned* __restrict__ prows,
                                                                        const unsigned* __restrict__ cnt_tm, const unsigned* __restrict__ toffs, int nb,
                                                                        int64_t ntiles, int64_t n, int32_t* __restrict__ out_ids) {
   __shared__ unsigned s_cnt[kMaxBins], s_start[kMaxBins], s_goff[kMaxBins], s_wsum[kThreads / 64];
   __shared__ int s_out[G * kGbTile];
-  const int64_t ngroups = (ntiles + G - 1) / G;
-  const int64_t grp = xcd_contiguous_tile(ngroups);
+  const int64_t grp = xcd_contiguous_tile((ntiles + G - 1) / G);
   if (grp < 0) return;
   const int64_t tile0 = grp * G;
   unsigned excl = 0, cnt = 0;
@@ -469,28 +412,13 @@ __global__ __launch_bounds__(kThreads) void enc_unpermute_group_kernel(const int
     for (int g = 0; g < G; g++)
       if (tile0 + g < ntiles) cnt += cnt_tm[(tile0 + g) * nb + threadIdx.x];
   }
-  s_cnt[threadIdx.x] = cnt;
-  __syncthreads();
-  block_excl_scan(s_cnt, s_start, s_wsum, nb);
-  if ((int)threadIdx.x < nb) s_goff[threadIdx.x] = excl - s_start[threadIdx.x];
-  __syncthreads();
+  tile_bin_offsets(cnt, excl, nb, s_cnt, s_start, s_goff, s_wsum);
   const int64_t base = tile0 * kGbTile;
   const int grp_n = n - base >= (int64_t)G * kGbTile ? G * kGbTile : (int)(n - base);
 #pragma unroll 1
   for (int c = 0; c < G; c++) {
-    int lo[kGbRows], hi[kGbRows];
-#pragma unroll
-    for (int k = 0; k < kGbRows; k++) { lo[k] = 0; hi[k] = nb - 1; }
-#pragma unroll 1
-    for (int step = 0; step < 10; step++) {   // 2^10 = kMaxBins
-#pragma unroll
-      for (int k = 0; k < kGbRows; k++) {
-        const int mid = (lo[k] + hi[k] + 1) >> 1;
-        const bool le = s_start[mid] <= (unsigned)(c * kGbTile + k * kThreads + threadIdx.x);
-        lo[k] = le ? mid : lo[k];
-        hi[k] = le ? hi[k] : mid - 1;
-      }
-    }
+    int lo[kGbRows];
+    bin_of_staged<kGbRows, kMaxBinSteps>(s_start, nb, c * kGbTile, lo);
     int id[kGbRows];
     unsigned rw[kGbRows];
 #pragma unroll
@@ -508,26 +436,18 @@ __global__ __launch_bounds__(kThreads) void enc_unpermute_group_kernel(const int
       if (c * kGbTile + k * kThreads + (int)threadIdx.x < grp_n) s_out[(int64_t)(rw[k] & kRowMask) - base] = id[k];
   }
   __syncthreads();
-#pragma unroll
-  for (int k = 0; k < G * kGbRows; k++) {
-    const int i = k * kThreads + threadIdx.x;
-    if (i < grp_n) __builtin_nontemporal_store(s_out[i], &out_ids[base + i]);
-  }
+  store_staged<G * kGbRows>(s_out, grp_n, out_ids, base);
 }
 
 void launch_enc_unpermute(ah_ctx* c, const int* rec_id, const unsigned* prows, const unsigned* cnt_tm, const unsigned* toffs, int nb, int64_t ntiles,
                           int64_t n, int32_t* out_ids) {
   const int G = c->opt_encode_unperm_group;
-  if (G > 1) {
-    const int g = G >= 8 ? 8 : (G >= 4 ? 4 : 2);
-    const int64_t ngroups = (ntiles + g - 1) / g;
-    const unsigned grid = (unsigned)(((ngroups + 7) / 8) * 8);
-    if (g == 8) enc_unpermute_group_kernel<8><<<grid, kThreads, 0, c->stream>>>(rec_id, prows, cnt_tm, toffs, nb, ntiles, n, out_ids);
-    else if (g == 4) enc_unpermute_group_kernel<4><<<grid, kThreads, 0, c->stream>>>(rec_id, prows, cnt_tm, toffs, nb, ntiles, n, out_ids);
-    else enc_unpermute_group_kernel<2><<<grid, kThreads, 0, c->stream>>>(rec_id, prows, cnt_tm, toffs, nb, ntiles, n, out_ids);
-  } else {
-    enc_unpermute_kernel<<<(unsigned)(((ntiles + 7) / 8) * 8), kThreads, 0, c->stream>>>(rec_id, prows, cnt_tm, toffs, nb, ntiles, n, out_ids);
-  }
+  const int g = G >= 8 ? 8 : (G >= 4 ? 4 : (G >= 2 ? 2 : 1));
+  const unsigned grid = (unsigned)(((ah_ceil_div(ntiles, g) + 7) / 8) * 8);
+  if (g == 8) enc_unpermute_group_kernel<8><<<grid, kThreads, 0, c->stream>>>(rec_id, prows, cnt_tm, toffs, nb, ntiles, n, out_ids);
+  else if (g == 4) enc_unpermute_group_kernel<4><<<grid, kThreads, 0, c->stream>>>(rec_id, prows, cnt_tm, toffs, nb, ntiles, n, out_ids);
+  else if (g == 2) enc_unpermute_group_kernel<2><<<grid, kThreads, 0, c->stream>>>(rec_id, prows, cnt_tm, toffs, nb, ntiles, n, out_ids);
+  else enc_unpermute_group_kernel<1><<<grid, kThreads, 0, c->stream>>>(rec_id, prows, cnt_tm, toffs, nb, ntiles, n, out_ids);
 }
 
 
@@ -540,82 +460,14 @@ void launch_enc_unpermute(ah_ctx* c, const int* rec_id, const unsigned* prows, c
 __device__ __forceinline__ unsigned e2_digit(unsigned long long key, unsigned rw, int lp, unsigned mask) {
   return (rw & kKeyNull) ? 0u : ((unsigned)(gb_mix(key) >> (64 - lp)) & mask);   // level 1 took the top 6 of these lp bits (null keys: partition 0 of parent 0)
 }
-
-__global__ __launch_bounds__(kThreads) void e2_hist_kernel(const unsigned long long* __restrict__ pkeys, const unsigned* __restrict__ prows, int64_t n,
-                                                            const unsigned* __restrict__ pstart, int nparents, int lp, unsigned mask, int nb,
-                                                            unsigned* __restrict__ cnt, const TileRange* __restrict__ tile_table = nullptr) {
-  __shared__ unsigned s_h[kThreads];
-  __shared__ unsigned s_cnt[kThreads], s_start[kThreads], s_wsum[kThreads / 64];
-  __shared__ int s_pick;
-  // (tile_table: this launch's tiles precomputed — a histogram's workgroup lives ≈ 5 µs, ms_tile's loads, scan and barriers were 2 of them)
-  const TileRange r = tile_table ? tile_table[blockIdx.x] : ms_tile(pstart, nparents, n, s_cnt, s_start, s_wsum, &s_pick);
-  if (r.parent < 0) return;
-  for (int b = threadIdx.x; b < nb; b += kThreads) s_h[b] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < kMsRows; u++) {
-    const int64_t i = r.lo + u * kThreads + threadIdx.x;
-    // (null keys all sit in parent 0: the other 63 parents' histograms read the keys alone, 8 instead of 12 bytes per record)
-    if (i < r.hi) atomicAdd(&s_h[e2_digit(__builtin_nontemporal_load(&pkeys[i]), r.parent == 0 ? __builtin_nontemporal_load(&prows[i]) : 0u, lp, mask)], 1u);
+struct E2Digit {   // tile_hist_kernel's view of the level-1 records (ah_msd.h)
+  static constexpr int kMaxDigits = kThreads;
+  const unsigned long long* pkeys; const unsigned* prows; int lp; unsigned mask;
+  // (null keys all sit in parent 0: the other 63 parents' histograms read the keys alone, 8 instead of 12 bytes per record)
+  __device__ __forceinline__ unsigned digit(int64_t i, int parent) const {
+    return e2_digit(__builtin_nontemporal_load(&pkeys[i]), parent == 0 ? __builtin_nontemporal_load(&prows[i]) : 0u, lp, mask);
   }
-  __syncthreads();
-  for (int b = threadIdx.x; b < nb; b += kThreads) cnt[r.id * nb + b] = s_h[b];
-}
-
-// level-2 offsets for FEW digits (nb ≤ 128): ms_offs2_kernel (ah_msd.h) gives every digit one thread that walks all of the parent's
-// virtual tiles — right for the sort's 2048 digits, but here 64 of 1024 threads would walk ≈ 260 tiles twice, one dependent load
-// after the other (343 µs at 2^26 rows).  Here thread (slice s, digit d) takes a contiguous slice of the parent's tiles,
-// S = 1024 / nb slices per digit; slice totals meet in LDS, one scan, then every thread walks its own slice once more.
-__global__ __launch_bounds__(kThreads) void e2_offs2_kernel(const unsigned* __restrict__ cnt, const unsigned* __restrict__ pstart, int nparents, int nb,
-                                                             unsigned* __restrict__ toffs, unsigned* __restrict__ bstart, int64_t n,
-                                                             unsigned* __restrict__ largest, unsigned* __restrict__ done, unsigned long long* mb, unsigned long long seq) {
-  // largest / done: two device words, zero on entry and left zero — the largest final partition's size goes to the host's mailbox
-  // from the last workgroup to finish (the host looks at the partitions' balance while the scatter behind this kernel already runs)
-  __shared__ unsigned s_cnt[kThreads], s_start[kThreads], s_wsum[kThreads / 64];
-  __shared__ unsigned s_part[kThreads];   // [slice][digit] totals
-  __shared__ unsigned s_largest;
-  const int t = threadIdx.x, p = blockIdx.x;
-  if (t == 0) s_largest = 0;
-  unsigned tiles = 0;
-  if (t < nparents) { const int q = ms_parent_of(t, nparents); tiles = (pstart[q + 1] - pstart[q] + kMsTile - 1) / kMsTile; }
-  s_cnt[t] = tiles;
-  __syncthreads();
-  block_excl_scan(s_cnt, s_start, s_wsum, nparents);
-  const int j = (p & 7) * (nparents >> 3) + (p >> 3);   // this parent's place in the class-major tile numbering (ms_tile)
-  const int64_t vt0 = s_start[j], nvt = s_cnt[j];
-  __syncthreads();
-  const int S = kThreads / nb, d = t % nb, sl = t / nb;
-  const int64_t per = (nvt + S - 1) / S, a = vt0 + sl * per, b = a + per < vt0 + nvt ? a + per : vt0 + nvt;
-  unsigned tot = 0;
-  for (int64_t vt = a; vt < b; vt++) tot += cnt[vt * nb + d];
-  s_part[sl * nb + d] = sl < S ? tot : 0u;
-  __syncthreads();
-  // digit totals → exclusive scan over the digits
-  unsigned dtot = 0;
-  if (t < nb) for (int q = 0; q < S; q++) dtot += s_part[q * nb + t];
-  s_cnt[t] = t < nb ? dtot : 0u;
-  if (t < nb && dtot) atomicMax(&s_largest, dtot);
-  __syncthreads();
-  block_excl_scan(s_cnt, s_start, s_wsum, nb);
-  if (t == 0) {
-    atomicMax(largest, s_largest);
-    __threadfence();
-    if (atomicAdd(done, 1u) == gridDim.x - 1u) {
-      __threadfence();
-      const unsigned long long w = __hip_atomic_exchange(largest, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ah_mailbox_post(mb, seq, &w, 1);
-    }
-  }
-  const unsigned base = pstart[p];
-  if (t < nb) bstart[(int64_t)p * nb + t] = base + s_start[t];
-  // this thread's running offset = parent start + smaller digits + this digit in earlier slices
-  unsigned run = base + s_start[d];
-  for (int q = 0; q < sl; q++) run += s_part[q * nb + d];
-  if (sl < S)
-    for (int64_t vt = a; vt < b; vt++) { toffs[vt * nb + d] = run; run += cnt[vt * nb + d]; }
-  if (p == nparents - 1 && t == 0) bstart[(int64_t)nparents * nb] = (unsigned)n;
-}
+};
 
 __global__ __launch_bounds__(kThreads) void e2_scatter_kernel(const unsigned long long* __restrict__ pkeys, const unsigned* __restrict__ prows, int64_t n,
                                                                const unsigned* __restrict__ pstart, int nparents, int lp, unsigned mask, int nb,
@@ -678,7 +530,64 @@ __global__ __launch_bounds__(kThreads) void e2_scatter_kernel(const unsigned lon
     }
 }
 
-// ids of a virtual tile's records (scattered over the parent's partitions) → back at their level-1 positions
+// ---- ids of the level-2 records → back at their level-1 positions, G consecutive virtual tiles of a parent per workgroup ---------------
+// As enc_unpermute_group_kernel does for level 1 (353 → 205 µs there): inside a digit the runs of consecutive virtual tiles lie one
+// after the other (ms_offs2_kernel walks the tiles in order), so the group reads ONE run per digit, G times as long (nb2 = 128 digits:
+// 32 records per tile).  A record's tile inside the group follows from its offset in the group's run of its digit (s_cum: cumulative
+// counts per digit after each of the group's tiles but the last); its 2-byte position is relative to that tile.
+// vt0, gt: the group's first virtual tile and how many it has; [lo, lo + group_n): its level-1 positions.  nb ≤ 128.
+template <int G>
+__device__ __forceinline__ void e2_unpermute_body(const int* __restrict__ rec_id, const unsigned short* __restrict__ rec_j, const unsigned* __restrict__ cnt,
+                                                  const unsigned* __restrict__ toffs, int nb, int64_t vt0, int gt, int64_t lo, int group_n, unsigned* s_cnt,
+                                                  unsigned* s_start, unsigned* s_goff, unsigned* s_wsum, unsigned (*s_cum)[128], int* s_out,
+                                                  int* __restrict__ rec_id1) {
+  const int t = threadIdx.x;
+  unsigned excl = 0, c = 0;
+  if (t < nb) {
+    excl = toffs[vt0 * nb + t];
+#pragma unroll
+    for (int q = 0; q < G; q++) {
+      if (q < gt) c += cnt[(vt0 + q) * nb + t];
+      if (q < G - 1) s_cum[q][t] = c;
+    }
+  }
+  tile_bin_offsets(c, excl, nb, s_cnt, s_start, s_goff, s_wsum);
+#pragma unroll 1
+  for (int ch = 0; ch < G; ch++) {
+    int dlo[kMsRows];
+    bin_of_staged<kMsRows, 8>(s_start, nb, ch * kMsTile, dlo);   // 2^8 ≥ nb
+    int id[kMsRows];
+    unsigned short jp[kMsRows];
+#pragma unroll
+    for (int k = 0; k < kMsRows; k++) {
+      const int lp = ch * kMsTile + k * kThreads + t;
+      id[k] = 0; jp[k] = 0;
+      if (lp < group_n) {
+        const int64_t e = (int64_t)s_goff[dlo[k]] + lp;
+        id[k] = __builtin_nontemporal_load(&rec_id[e]);
+        jp[k] = __builtin_nontemporal_load(&rec_j[e]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kMsRows; k++) {
+      const int lp = ch * kMsTile + k * kThreads + t;
+      if (lp < group_n) {
+        int tile = 0;
+        if (G > 1) {
+          const unsigned q = (unsigned)lp - s_start[dlo[k]];   // offset in the group's run of this digit
+#pragma unroll
+          for (int w = 0; w < G - 1; w++) tile += q >= s_cum[w][dlo[k]] ? 1 : 0;
+        }
+        s_out[tile * kMsTile + jp[k]] = id[k];
+      }
+    }
+  }
+  __syncthreads();
+  store_staged<G * kMsRows>(s_out, group_n, rec_id1, lo);
+}
+
+// one virtual tile per workgroup (option encode_unperm2_group = 0), picked as the level-2 scatter picks it.  This one keeps the skeleton
+// spelled out: over tile_bin_offsets / bin_of_staged (ah_bins.h) it took 27 registers where it has a budget of 25 (tests/test_isa_hints.py)
 __global__ __launch_bounds__(kThreads) void e2_unpermute_kernel(const int* __restrict__ rec_id, const unsigned short* __restrict__ rec_j,
                                                                  const unsigned* __restrict__ cnt, const unsigned* __restrict__ toffs, int64_t n,
                                                                  const unsigned* __restrict__ pstart, int nparents, int nb, int* __restrict__ rec_id1) {
@@ -701,7 +610,7 @@ __global__ __launch_bounds__(kThreads) void e2_unpermute_kernel(const int* __res
 #pragma unroll
   for (int k = 0; k < kMsRows; k++) { lo[k] = 0; hi[k] = nb - 1; }
 #pragma unroll 1
-  for (int step = 0; step < 8; step++) {   // 2^7 ≥ nb
+  for (int step = 0; step < 8; step++) {   // bin_of_staged<kMsRows, 8>, spelled out
 #pragma unroll
     for (int k = 0; k < kMsRows; k++) {
       const int mid = (lo[k] + hi[k] + 1) >> 1;
@@ -726,20 +635,12 @@ __global__ __launch_bounds__(kThreads) void e2_unpermute_kernel(const int* __res
   for (int k = 0; k < kMsRows; k++)
     if (k * kThreads + t < tile_n) s_out[j[k]] = id[k];
   __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kMsRows; k++) {
-    const int i = k * kThreads + t;
-    if (i < tile_n) __builtin_nontemporal_store(s_out[i], &rec_id1[r.lo + i]);
-  }
+  store_staged<kMsRows>(s_out, tile_n, rec_id1, r.lo);
 }
 
-
-// (option encode_unperm2_group: 4 = default, 0 = one virtual tile per workgroup.  Built last in round 3: 2^24 keys 2.64 → 2.60 ms)
-// the level-2 un-permute over G consecutive virtual tiles of a parent per workgroup, as enc_unpermute_group_kernel does for level 1
-// (353 → 205 µs there).  Inside a digit the runs of consecutive virtual tiles lie one after the other (e2_offs2_kernel walks the tiles
-// in order), so the group reads ONE run per digit, G times as long (nb2 = 128 digits: 32 records per tile).  A record's tile inside
-// the group follows from its offset in the group's run of its digit (cumulative counts per digit in LDS); its 2-byte position is
-// relative to that tile.  Needs nparents ≤ 64 (the two-cut path always has 64).
+// (option encode_unperm2_group: 4 = default.  Built last in round 3: 2^24 keys 2.64 → 2.60 ms)  Block b serves the b-th GROUP in the
+// class-major parent order of the tile numbering; needs nparents ≤ 64 (the two-cut path always has 64): one wave scans the tiles and
+// the groups per parent side by side.
 template <int G>
 __global__ __launch_bounds__(kThreads) void e2_unpermute_group_kernel(const int* __restrict__ rec_id, const unsigned short* __restrict__ rec_j,
                                                                        const unsigned* __restrict__ cnt, const unsigned* __restrict__ toffs, int64_t n,
@@ -751,10 +652,8 @@ __global__ __launch_bounds__(kThreads) void e2_unpermute_group_kernel(const int*
   __shared__ int s_out[G * kMsTile];
   __shared__ int s_pick;
   const int t = threadIdx.x;
-  // tiles and groups per parent, in the class-major parent order the tile numbering of the count / offset tables uses (ms_tile)
   if (t < 64) {
-    unsigned tiles = 0;
-    if (t < nparents) { const int p = ms_parent_of(t, nparents); tiles = (pstart[p + 1] - pstart[p] + kMsTile - 1) / kMsTile; }
+    const unsigned tiles = t < nparents ? ms_tiles_of(pstart, nullptr, t, nparents) : 0u;
     const unsigned groups = (tiles + G - 1) / G;
     unsigned it = tiles, ig = groups;
 #pragma unroll
@@ -779,67 +678,7 @@ __global__ __launch_bounds__(kThreads) void e2_unpermute_group_kernel(const int*
   const int gt = (int)(s_tiles[j] - g * G < (unsigned)G ? s_tiles[j] - g * G : (unsigned)G);   // tiles in this group
   const int64_t lo = (int64_t)pstart[p] + (int64_t)g * G * kMsTile;
   const int64_t pend = (int64_t)pstart[p + 1], hi = lo + (int64_t)gt * kMsTile < pend ? lo + (int64_t)gt * kMsTile : pend;
-  // per digit: the group's record count, the cumulative counts after each of its tiles, where its run starts
-  unsigned excl = 0, c = 0;
-  if (t < nb) {
-    excl = toffs[vt0 * nb + t];
-#pragma unroll
-    for (int q = 0; q < G; q++) {
-      if (q < gt) c += cnt[(vt0 + q) * nb + t];
-      if (q < G - 1) s_cum[q][t] = c;
-    }
-  }
-  s_cnt[t] = t < nb ? c : 0u;
-  __syncthreads();
-  block_excl_scan(s_cnt, s_start, s_wsum, nb);
-  if (t < nb) s_goff[t] = excl - s_start[t];
-  __syncthreads();
-  const int group_n = (int)(hi - lo);
-#pragma unroll 1
-  for (int ch = 0; ch < G; ch++) {
-    int dlo[kMsRows], dhi[kMsRows];
-#pragma unroll
-    for (int k = 0; k < kMsRows; k++) { dlo[k] = 0; dhi[k] = nb - 1; }
-#pragma unroll 1
-    for (int step = 0; step < 8; step++) {   // 2^7 ≥ nb
-#pragma unroll
-      for (int k = 0; k < kMsRows; k++) {
-        const int mid = (dlo[k] + dhi[k] + 1) >> 1;
-        const bool le = s_start[mid] <= (unsigned)(ch * kMsTile + k * kThreads + t);
-        dlo[k] = le ? mid : dlo[k];
-        dhi[k] = le ? dhi[k] : mid - 1;
-      }
-    }
-    int id[kMsRows];
-    unsigned short jp[kMsRows];
-#pragma unroll
-    for (int k = 0; k < kMsRows; k++) {
-      const int lp = ch * kMsTile + k * kThreads + t;
-      id[k] = 0; jp[k] = 0;
-      if (lp < group_n) {
-        const int64_t e = (int64_t)s_goff[dlo[k]] + lp;
-        id[k] = __builtin_nontemporal_load(&rec_id[e]);
-        jp[k] = __builtin_nontemporal_load(&rec_j[e]);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kMsRows; k++) {
-      const int lp = ch * kMsTile + k * kThreads + t;
-      if (lp < group_n) {
-        const unsigned q = (unsigned)lp - s_start[dlo[k]];   // offset in the group's run of this digit
-        int tile = 0;
-#pragma unroll
-        for (int w = 0; w < G - 1; w++) tile += q >= s_cum[w][dlo[k]] ? 1 : 0;
-        s_out[tile * kMsTile + jp[k]] = id[k];
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < G * kMsRows; k++) {
-    const int i = k * kThreads + t;
-    if (i < group_n) __builtin_nontemporal_store(s_out[i], &rec_id1[lo + i]);
-  }
+  e2_unpermute_body<G>(rec_id, rec_j, cnt, toffs, nb, vt0, gt, lo, (int)(hi - lo), s_cnt, s_start, s_goff, s_wsum, s_cum, s_out, rec_id1);
 }
 
 }  // namespace
@@ -953,34 +792,31 @@ int ah_encode_partitioned_try(ah_ctx* c, const uint64_t* keys, const uint8_t* va
                               int32_t* out_ids, uint64_t* out_dict, int64_t* out_first_rows, int64_t* out_ndict, int32_t* out_null_id, int* used) {
   *used = 0;
   if (n < 1 || n >= kMaxRows || lp < 3 || lp > 10 || (slots != kESlots && slots != kESlots2)) return AH_OK;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const int P = 1 << lp;
   const int64_t ntiles = ah_ceil_div(n, kGbTile), ngrp = ah_ceil_div(ntiles, kGroupTiles);
   const int64_t nslots = (int64_t)P * (slots + 8);
   const int64_t nwords = ah_ceil_div(n, 64), nrt = rank_tiles(nwords);
   const size_t table = (size_t)P * (size_t)ntiles * 4;
-  const size_t need = pad(table) * 2 + pad((size_t)ngrp * P * 4) + pad((size_t)(P + 1) * 4) + pad((size_t)n * 8) + pad((size_t)n * 4) + pad((size_t)n * 2) +
-                      pad((size_t)nslots * 8) + pad((size_t)nslots * 4) + pad((size_t)nwords * 8) + pad((size_t)nwords * 4) + pad((size_t)nrt * 4) + pad((size_t)nrt * 8) + pad((size_t)nwords * 64);
-  uint8_t* base;
-  int rc = ah_temp_reserve(c, need, (void**)&base);
+  const size_t need = ah_pad(table) * 2 + ah_pad((size_t)ngrp * P * 4) + ah_pad((size_t)(P + 1) * 4) + ah_pad((size_t)n * 8) + ah_pad((size_t)n * 4) + ah_pad((size_t)n * 2) +
+                      ah_pad((size_t)nslots * 8) + ah_pad((size_t)nslots * 4) + ah_pad((size_t)nwords * 8) + ah_pad((size_t)nwords * 4) + ah_pad((size_t)nrt * 4) + ah_pad((size_t)nrt * 8) + ah_pad((size_t)nwords * 64);
+  TempCarver tc;
+  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
   if (rc != AH_OK) return rc;
-  size_t used_b = 0;
-  auto take = [&](size_t b) { uint8_t* q = base + used_b; used_b += pad(b); return q; };
-  unsigned* cnt_tm = (unsigned*)take(table);
-  unsigned* toffs = (unsigned*)take(table);
-  unsigned* gsum = (unsigned*)take((size_t)ngrp * P * 4);
-  unsigned* binstart = (unsigned*)take((size_t)(P + 1) * 4);
-  unsigned long long* pkeys = (unsigned long long*)take((size_t)n * 8);
-  unsigned* prows = (unsigned*)take((size_t)n * 4);
-  unsigned short* rec_slot = (unsigned short*)take((size_t)n * 2);
-  unsigned long long* tab_key = (unsigned long long*)take((size_t)nslots * 8);
-  unsigned* tab_first = (unsigned*)take((size_t)nslots * 4);
-  unsigned long long* firsts = (unsigned long long*)take((size_t)nwords * 8);
+  unsigned* cnt_tm = (unsigned*)tc.take(table);
+  unsigned* toffs = (unsigned*)tc.take(table);
+  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * P * 4);
+  unsigned* binstart = (unsigned*)tc.take((size_t)(P + 1) * 4);
+  unsigned long long* pkeys = (unsigned long long*)tc.take((size_t)n * 8);
+  unsigned* prows = (unsigned*)tc.take((size_t)n * 4);
+  unsigned short* rec_slot = (unsigned short*)tc.take((size_t)n * 2);
+  unsigned long long* tab_key = (unsigned long long*)tc.take((size_t)nslots * 8);
+  unsigned* tab_first = (unsigned*)tc.take((size_t)nslots * 4);
+  unsigned long long* firsts = (unsigned long long*)tc.take((size_t)nwords * 8);
   // (from 1024 partitions on — ≈ 4·10^6 keys: below, the map's fill and packing cost what the atomics cost)
-  uint8_t* fbytes = (c->opt_encode_byte_map == 2 || (c->opt_encode_byte_map == 1 && lp >= 10)) ? (uint8_t*)take((size_t)nwords * 64) : nullptr;
-  unsigned* wordprefix = (unsigned*)take((size_t)nwords * 4);
-  int* tilecnt = (int*)take((size_t)nrt * 4);
-  int64_t* tileoff = (int64_t*)take((size_t)nrt * 8);
+  uint8_t* fbytes = (c->opt_encode_byte_map == 2 || (c->opt_encode_byte_map == 1 && lp >= 10)) ? (uint8_t*)tc.take((size_t)nwords * 64) : nullptr;
+  unsigned* wordprefix = (unsigned*)tc.take((size_t)nwords * 4);
+  int* tilecnt = (int*)tc.take((size_t)nrt * 4);
+  int64_t* tileoff = (int64_t*)tc.take((size_t)nrt * 8);
   int* rec_id = (int*)pkeys;   // the keys are not needed once every record knows its slot
   unsigned* overflow = (unsigned*)&c->dscalars[30];
   unsigned long long* total = (unsigned long long*)&c->dscalars[31];
@@ -991,7 +827,7 @@ int ah_encode_partitioned_try(ah_ctx* c, const uint64_t* keys, const uint8_t* va
     f.p[0] = (uint4*)&c->dscalars[30]; f.n16[0] = 1; f.v[0] = 0u;                 // [30] overflow, [31] total
     f.ones = (unsigned long long*)null_id;                                         // [32] null id: none
     if (fbytes) { f.p[1] = (uint4*)fbytes; f.n16[1] = (size_t)nwords * 4; }   // the byte map (the bitmap is then written whole)
-    else { f.p[1] = (uint4*)firsts; f.n16[1] = pad((size_t)nwords * 8) / 16; }
+    else { f.p[1] = (uint4*)firsts; f.n16[1] = ah_pad((size_t)nwords * 8) / 16; }
     f.v[1] = 0u;
     gb_fill_kernel<<<(unsigned)(c->num_cu * 2), 256, 0, c->stream>>>(f);
     AH_LAUNCH_CHECK(c);
@@ -1001,18 +837,13 @@ int ah_encode_partitioned_try(ah_ctx* c, const uint64_t* keys, const uint8_t* va
   const unsigned tgrid = (unsigned)(((ntiles + 7) / 8) * 8);
   gb_hist_kernel<<<tgrid, kGbHistThreads, 0, c->stream>>>(k64, valid, off, n, lp, P, ntiles, cnt_tm);
   AH_LAUNCH_CHECK(c);
-  colsum_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt_tm, P, ntiles, gsum);
-  AH_LAUNCH_CHECK(c);
   // one workgroup per partition is only as fast as the largest partition: the sizes are looked at before the tables are built — through
   // the mailbox, posted by the prefix kernel itself and read while the offsets and the scatter are already running (a copy of
   // binstart + a stream synchronisation left the device idle for ≈ 15 µs on every call; a lopsided column now costs a scatter
   // that nobody reads, and such columns rarely get here: the first look sends them to the global table)
   unsigned long long *mb, seq, largest = 0;
   if ((rc = ah_mailbox_begin(c, &mb, &seq)) != AH_OK) return rc;
-  bin_prefix_kernel<<<1, kMaxBins, 0, c->stream>>>(gsum, P, ngrp, n, binstart, mb, seq);
-  AH_LAUNCH_CHECK(c);
-  tile_offs_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt_tm, gsum, P, ntiles, toffs);
-  AH_LAUNCH_CHECK(c);
+  if ((rc = launch_tile_offsets(c, cnt_tm, P, ntiles, n, gsum, toffs, binstart, mb, seq)) != AH_OK) return rc;
   gb_scatter_kernel<false><<<tgrid, kThreads, 0, c->stream>>>(k64, valid, off, nullptr, nullptr, 0, n, lp, P, ntiles, toffs, pkeys, nullptr, prows, nullptr);
   AH_LAUNCH_CHECK(c);
   if ((rc = ah_mailbox_wait(c, seq, 1, &largest)) != AH_OK) return rc;
@@ -1058,41 +889,38 @@ int ah_encode_partitioned2_try(ah_ctx* c, const uint64_t* keys, const uint8_t* v
                                int32_t* out_ids, uint64_t* out_dict, int64_t* out_first_rows, int64_t* out_ndict, int32_t* out_null_id, int* used) {
   *used = 0;
   if (n < ((int64_t)1 << 20) || n >= kMaxRows || lp < 7 || lp > 13 || (slots != kESlots && slots != kESlots2)) return AH_OK;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   constexpr int lb1 = 6, nb1 = 1 << lb1;
   const int lb2 = lp - lb1, nb2 = 1 << lb2;
   const int64_t P = (int64_t)1 << lp;
   const int64_t ntiles = ah_ceil_div(n, kGbTile), ngrp = ah_ceil_div(ntiles, kGroupTiles), nvt = ((ntiles + nb1 + 7) / 8) * 8;
   const int64_t nslots = P * (slots + 8);
   const int64_t nwords = ah_ceil_div(n, 64), nrt = rank_tiles(nwords);
-  const size_t need = pad((size_t)ntiles * nb1 * 4) * 2 + pad((size_t)ngrp * nb1 * 4) + pad((size_t)(nb1 + 1) * 4) + pad((size_t)nvt * nb2 * 4) * 2 + pad(((size_t)P + 1) * 4) +
-                      pad((size_t)n * 8) * 2 + pad((size_t)n * 4) * 2 + pad((size_t)n * 2) * 2 + pad((size_t)nslots * 8) + pad((size_t)nslots * 4) +
-                      pad((size_t)nwords * 8) + pad((size_t)nwords * 4) + pad((size_t)nrt * 4) + pad((size_t)nrt * 8) + pad((size_t)nwords * 64) + pad((size_t)nvt * sizeof(TileRange));
-  uint8_t* base;
-  int rc = ah_temp_reserve(c, need, (void**)&base);
+  const size_t need = ah_pad((size_t)ntiles * nb1 * 4) * 2 + ah_pad((size_t)ngrp * nb1 * 4) + ah_pad((size_t)(nb1 + 1) * 4) + ah_pad((size_t)nvt * nb2 * 4) * 2 + ah_pad(((size_t)P + 1) * 4) +
+                      ah_pad((size_t)n * 8) * 2 + ah_pad((size_t)n * 4) * 2 + ah_pad((size_t)n * 2) * 2 + ah_pad((size_t)nslots * 8) + ah_pad((size_t)nslots * 4) +
+                      ah_pad((size_t)nwords * 8) + ah_pad((size_t)nwords * 4) + ah_pad((size_t)nrt * 4) + ah_pad((size_t)nrt * 8) + ah_pad((size_t)nwords * 64) + ah_pad((size_t)nvt * sizeof(TileRange));
+  TempCarver tc;
+  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
   if (rc != AH_OK) return rc;
-  size_t used_b = 0;
-  auto take = [&](size_t b) { uint8_t* q = base + used_b; used_b += pad(b); return q; };
-  unsigned* cnt1 = (unsigned*)take((size_t)ntiles * nb1 * 4);
-  unsigned* toffs1 = (unsigned*)take((size_t)ntiles * nb1 * 4);
-  unsigned* gsum = (unsigned*)take((size_t)ngrp * nb1 * 4);
-  unsigned* pstart = (unsigned*)take((size_t)(nb1 + 1) * 4);
-  unsigned* cnt2 = (unsigned*)take((size_t)nvt * nb2 * 4);
-  unsigned* toffs2 = (unsigned*)take((size_t)nvt * nb2 * 4);
-  unsigned* bstart = (unsigned*)take(((size_t)P + 1) * 4);
-  unsigned long long* pkeys1 = (unsigned long long*)take((size_t)n * 8);
-  unsigned long long* pkeys2 = (unsigned long long*)take((size_t)n * 8);
-  unsigned* prows1 = (unsigned*)take((size_t)n * 4);
-  unsigned* prows2 = (unsigned*)take((size_t)n * 4);
-  unsigned short* pj2 = (unsigned short*)take((size_t)n * 2);
-  unsigned short* rec_slot = (unsigned short*)take((size_t)n * 2);
-  unsigned long long* tab_key = (unsigned long long*)take((size_t)nslots * 8);
-  unsigned* tab_first = (unsigned*)take((size_t)nslots * 4);
-  unsigned long long* firsts = (unsigned long long*)take((size_t)nwords * 8);
-  uint8_t* fbytes = c->opt_encode_byte_map ? (uint8_t*)take((size_t)nwords * 64) : nullptr;
-  unsigned* wordprefix = (unsigned*)take((size_t)nwords * 4);
-  int* tilecnt = (int*)take((size_t)nrt * 4);
-  int64_t* tileoff = (int64_t*)take((size_t)nrt * 8);
+  unsigned* cnt1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
+  unsigned* toffs1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
+  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * nb1 * 4);
+  unsigned* pstart = (unsigned*)tc.take((size_t)(nb1 + 1) * 4);
+  unsigned* cnt2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
+  unsigned* toffs2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
+  unsigned* bstart = (unsigned*)tc.take(((size_t)P + 1) * 4);
+  unsigned long long* pkeys1 = (unsigned long long*)tc.take((size_t)n * 8);
+  unsigned long long* pkeys2 = (unsigned long long*)tc.take((size_t)n * 8);
+  unsigned* prows1 = (unsigned*)tc.take((size_t)n * 4);
+  unsigned* prows2 = (unsigned*)tc.take((size_t)n * 4);
+  unsigned short* pj2 = (unsigned short*)tc.take((size_t)n * 2);
+  unsigned short* rec_slot = (unsigned short*)tc.take((size_t)n * 2);
+  unsigned long long* tab_key = (unsigned long long*)tc.take((size_t)nslots * 8);
+  unsigned* tab_first = (unsigned*)tc.take((size_t)nslots * 4);
+  unsigned long long* firsts = (unsigned long long*)tc.take((size_t)nwords * 8);
+  uint8_t* fbytes = c->opt_encode_byte_map ? (uint8_t*)tc.take((size_t)nwords * 64) : nullptr;
+  unsigned* wordprefix = (unsigned*)tc.take((size_t)nwords * 4);
+  int* tilecnt = (int*)tc.take((size_t)nrt * 4);
+  int64_t* tileoff = (int64_t*)tc.take((size_t)nrt * 8);
   int* rec_id2 = (int*)pkeys2;   // level-2 keys are dead once every record knows its slot
   int* rec_id1 = (int*)pkeys1;   // level-1 keys are dead after the level-2 scatter
   unsigned* overflow = (unsigned*)&c->dscalars[30];
@@ -1104,7 +932,7 @@ int ah_encode_partitioned2_try(ah_ctx* c, const uint64_t* keys, const uint8_t* v
     f.p[0] = (uint4*)&c->dscalars[30]; f.n16[0] = 1; f.v[0] = 0u;                 // [30] overflow, [31] total
     f.ones = (unsigned long long*)null_id;                                         // [32] null id: none
     if (fbytes) { f.p[1] = (uint4*)fbytes; f.n16[1] = (size_t)nwords * 4; }   // the byte map (the bitmap is then written whole)
-    else { f.p[1] = (uint4*)firsts; f.n16[1] = pad((size_t)nwords * 8) / 16; }
+    else { f.p[1] = (uint4*)firsts; f.n16[1] = ah_pad((size_t)nwords * 8) / 16; }
     f.v[1] = 0u;
     gb_fill_kernel<<<(unsigned)(c->num_cu * 2), 256, 0, c->stream>>>(f);
     AH_LAUNCH_CHECK(c);
@@ -1114,24 +942,19 @@ int ah_encode_partitioned2_try(ah_ctx* c, const uint64_t* keys, const uint8_t* v
   const unsigned tgrid = (unsigned)(((ntiles + 7) / 8) * 8);
   gb_hist_kernel<<<tgrid, kGbHistThreads, 0, c->stream>>>(k64, valid, off, n, lb1, nb1, ntiles, cnt1);
   AH_LAUNCH_CHECK(c);
-  colsum_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt1, nb1, ntiles, gsum);
-  AH_LAUNCH_CHECK(c);
-  bin_prefix_kernel<<<1, kMaxBins, 0, c->stream>>>(gsum, nb1, ngrp, n, pstart);
-  AH_LAUNCH_CHECK(c);
-  tile_offs_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt1, gsum, nb1, ntiles, toffs1);
-  AH_LAUNCH_CHECK(c);
+  if ((rc = launch_tile_offsets(c, cnt1, nb1, ntiles, n, gsum, toffs1, pstart)) != AH_OK) return rc;
   gb_scatter_kernel<false><<<tgrid, kThreads, 0, c->stream>>>(k64, valid, off, nullptr, nullptr, 0, n, lb1, nb1, ntiles, toffs1, pkeys1, nullptr, prows1, nullptr);
   AH_LAUNCH_CHECK(c);
   // ---- level 2: every parent into 2^lb2 partitions
-  TileRange* tile_table = (TileRange*)take((size_t)nvt * sizeof(TileRange));
+  TileRange* tile_table = (TileRange*)tc.take((size_t)nvt * sizeof(TileRange));
   ms_tile_table_kernel<<<(unsigned)ah_ceil_div(nvt, kThreads), kThreads, 0, c->stream>>>(pstart, nullptr, nb1, (unsigned)nvt, tile_table);
   AH_LAUNCH_CHECK(c);
-  e2_hist_kernel<<<(unsigned)nvt, kThreads, 0, c->stream>>>(pkeys1, prows1, n, pstart, nb1, lp, (unsigned)(nb2 - 1), nb2, cnt2, tile_table);
+  tile_hist_kernel<E2Digit><<<(unsigned)nvt, kThreads, 0, c->stream>>>(E2Digit{pkeys1, prows1, lp, (unsigned)(nb2 - 1)}, n, pstart, nb1, nb2, cnt2, tile_table);
   AH_LAUNCH_CHECK(c);
   // (the partitions' balance: posted by the offsets kernel, read while the scatter runs — see ah_encode_partitioned_try)
   unsigned long long *mb, seq, largest = 0;
   if ((rc = ah_mailbox_begin(c, &mb, &seq)) != AH_OK) return rc;
-  e2_offs2_kernel<<<(unsigned)nb1, kThreads, 0, c->stream>>>(cnt2, pstart, nb1, nb2, toffs2, bstart, n, (unsigned*)&c->dscalars[35], (unsigned*)&c->dscalars[36], mb, seq);
+  ms_offs2_kernel<<<(unsigned)nb1, kThreads, 0, c->stream>>>(cnt2, pstart, nb1, nb2, toffs2, bstart, n, (unsigned*)&c->dscalars[35], (unsigned*)&c->dscalars[36], mb, seq);
   AH_LAUNCH_CHECK(c);
   e2_scatter_kernel<<<(unsigned)nvt, kThreads, 0, c->stream>>>(pkeys1, prows1, n, pstart, nb1, lp, (unsigned)(nb2 - 1), nb2, toffs2, pkeys2, prows2, pj2);
   AH_LAUNCH_CHECK(c);

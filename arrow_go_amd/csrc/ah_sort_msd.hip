@@ -194,24 +194,12 @@ __global__ __launch_bounds__(kThreads) void ms_bucket_kernel(const unsigned long
   }
 }
 
-// ---- hist: per (tile, digit) counts.  digit = (bucket >> shift) & mask --------------------------------------------------
-__global__ __launch_bounds__(kThreads) void ms_hist_kernel(const unsigned* __restrict__ bucket, int64_t n, const unsigned* __restrict__ pstart, int nparents,
-                                                            int shift, unsigned mask, int nb, unsigned* __restrict__ cnt) {
-  __shared__ unsigned s_h[kMaxNb2];
-  __shared__ unsigned s_cnt[kThreads], s_start[kThreads], s_wsum[kThreads / 64];
-  __shared__ int s_pick;
-  const TileRange r = ms_tile(pstart, nparents, n, s_cnt, s_start, s_wsum, &s_pick);
-  if (r.parent < 0) return;
-  for (int b = threadIdx.x; b < nb; b += kThreads) s_h[b] = 0;
-  __syncthreads();
-  unsigned bk[kMsRows];
-#pragma unroll
-  for (int u = 0; u < kMsRows; u++) { const int64_t i = r.lo + u * kThreads + threadIdx.x; bk[u] = i < r.hi ? __builtin_nontemporal_load(&bucket[i]) : 0u; }
-#pragma unroll
-  for (int u = 0; u < kMsRows; u++) { const int64_t i = r.lo + u * kThreads + threadIdx.x; if (i < r.hi) atomicAdd(&s_h[(bk[u] >> shift) & mask], 1u); }
-  __syncthreads();
-  for (int b = threadIdx.x; b < nb; b += kThreads) cnt[r.id * nb + b] = s_h[b];
-}
+// ---- hist: per (tile, digit) counts (tile_hist_kernel, ah_msd.h).  digit = (bucket >> shift) & mask -----------------------------
+struct MsDigit {
+  static constexpr int kMaxDigits = kMaxNb2;
+  const unsigned* bucket; int shift; unsigned mask;
+  __device__ __forceinline__ unsigned digit(int64_t i, int) const { return (__builtin_nontemporal_load(&bucket[i]) >> shift) & mask; }
+};
 
 // ---- scatter: the tile staged in digit order in LDS, written as runs ----------------------------------------------------
 // WITH_BUCKET: the bucket ids travel with the pairs (level 1); level 2 drops them
@@ -249,22 +237,10 @@ __global__ __launch_bounds__(kThreads) void ms_scatter_kernel(const unsigned lon
     rank[u] = live[u] ? atomicAdd(&s_cnt[dg[u]], 1u) : 0u;
   }
   __syncthreads();
-  // exclusive scan over nb ≤ 2048 digit counts, 1024 at a time
-  unsigned carry = 0;
-  for (int h = 0; h * kThreads < nb; h++) {
-    s_a[t] = t + h * kThreads < nb ? s_cnt[t + h * kThreads] : 0u;
-    __syncthreads();
-    block_excl_scan(s_a, s_b, s_wsum, kThreads);
-    if (t + h * kThreads < nb) {
-      const unsigned st = carry + s_b[t];
-      s_start[t + h * kThreads] = st;
-      s_goff[t + h * kThreads] = toffs[r.id * nb + t + h * kThreads] - st;   // global position = s_goff[digit] + staged position
-    }
-    if (t == kThreads - 1) s_carry = s_b[t] + s_a[t];
-    __syncthreads();
-    carry += s_carry;
-    __syncthreads();
-  }
+  digit_excl_scan(s_cnt, nb, s_a, s_b, s_wsum, &s_carry, [&](int d, unsigned st) {
+    s_start[d] = st;
+    s_goff[d] = toffs[r.id * nb + d] - st;   // global position = s_goff[digit] + staged position
+  });
   const int tile_n = (int)(r.hi - r.lo);
 #pragma unroll
   for (int u = 0; u < kMsRows; u++)
@@ -452,7 +428,6 @@ static void ms_plan(int64_t n, int* lb_out, int* lb2_out) {
   *lb_out = lb;
   *lb2_out = lb >= 20 ? lb - 10 : lb - lb / 2;    // NB2 = 2^lb2 ≤ 2048, NB1 = 2^(lb − lb2) ≤ 1024
 }
-static size_t ms_pad(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // bytes of temporaries ah_sort_rest_msd wants for n pairs (0: it will not run).  2^27 rows = 2^21 buckets of 64: the largest table
 // the two partition levels address (1024 × 2048); below 2^22 rows the fixed costs (sorting the sample) eat the gain
@@ -462,9 +437,9 @@ size_t ah_sort_msd_temp_bytes(int64_t n) {
   ms_plan(n, &lb, &lb2);
   const int nb2 = 1 << lb2, nb1 = 1 << (lb - lb2);
   const int64_t ntiles = ah_ceil_div(n, kMsTile), ngrp = ah_ceil_div(ntiles, kGroupTiles), nvt = ((ntiles + nb1 + 7) / 8) * 8;
-  return ms_pad((size_t)n * 4) * 2 + ms_pad((size_t)kSample * 8) * 2 + ms_pad((size_t)kSample * 4) * 2 + ms_pad((size_t)(kSplit + 1) * 8) + ms_pad(kFlagWords * 4) + ms_pad(4097 * 2) +
-         ms_pad((size_t)ntiles * nb1 * 4) * 2 + ms_pad((size_t)ngrp * nb1 * 4) + ms_pad((size_t)(nb1 + 1) * 4) + ms_pad((size_t)nvt * nb2 * 4) * 2 +
-         ms_pad(((size_t)1 << lb) * 4 + 4) + ms_pad((size_t)kBigList * 4) + 256;
+  return ah_pad((size_t)n * 4) * 2 + ah_pad((size_t)kSample * 8) * 2 + ah_pad((size_t)kSample * 4) * 2 + ah_pad((size_t)(kSplit + 1) * 8) + ah_pad(kFlagWords * 4) + ah_pad(4097 * 2) +
+         ah_pad((size_t)ntiles * nb1 * 4) * 2 + ah_pad((size_t)ngrp * nb1 * 4) + ah_pad((size_t)(nb1 + 1) * 4) + ah_pad((size_t)nvt * nb2 * 4) * 2 +
+         ah_pad(((size_t)1 << lb) * 4 + 4) + ah_pad((size_t)kBigList * 4) + 256;
 }
 
 // keys / rows: the `rest` range (n pairs, row order).  alt_keys / alt_rows: same-sized scratch.  tmp: ah_sort_msd_temp_bytes(n) bytes.
@@ -476,7 +451,6 @@ int ah_sort_rest_msd(ah_ctx* c, unsigned long long* keys, unsigned* rows, unsign
   *used = -1;
   if (!tmp || varying == 0 || ah_sort_msd_temp_bytes(n) == 0) return AH_OK;
   unsigned* out_rows = rows;   // the last step rewrites every bucket in place
-  auto pad = ms_pad;
   int lb, lb2;
   ms_plan(n, &lb, &lb2);
   const int nb2 = 1 << lb2, nb1 = 1 << (lb - lb2);
@@ -486,27 +460,26 @@ int ah_sort_rest_msd(ah_ctx* c, unsigned long long* keys, unsigned* rows, unsign
   const int64_t ntiles = ah_ceil_div(n, kMsTile), ngrp = ah_ceil_div(ntiles, kGroupTiles), nvt = ((ntiles + nb1 + 7) / 8) * 8;
   const unsigned grid1 = (unsigned)(((ntiles + 7) / 8) * 8);
   const int64_t sample_n = n < kSample ? n : kSample;
-  uint8_t* base = (uint8_t*)tmp;
+  TempCarver tc;
+  tc.base = (uint8_t*)tmp;
   int rc;
-  size_t off = 0;
-  auto take = [&](size_t b) { uint8_t* q = base + off; off += pad(b); return q; };
-  unsigned* bucket = (unsigned*)take((size_t)n * 4);
-  unsigned* bucket2 = (unsigned*)take((size_t)n * 4);
-  unsigned long long* sample = (unsigned long long*)take((size_t)kSample * 8);
-  unsigned long long* sample_alt = (unsigned long long*)take((size_t)kSample * 8);
-  unsigned* sample_rows = (unsigned*)take((size_t)kSample * 4);
-  unsigned* sample_rows_alt = (unsigned*)take((size_t)kSample * 4);
-  unsigned long long* split = (unsigned long long*)take((size_t)(kSplit + 1) * 8);
-  unsigned* flags = (unsigned*)take(kFlagWords * 4);
-  unsigned short* guide = (unsigned short*)take(4097 * 2);
-  unsigned* cnt1 = (unsigned*)take((size_t)ntiles * nb1 * 4);
-  unsigned* toffs1 = (unsigned*)take((size_t)ntiles * nb1 * 4);
-  unsigned* gsum = (unsigned*)take((size_t)ngrp * nb1 * 4);
-  unsigned* pstart = (unsigned*)take((size_t)(nb1 + 1) * 4);
-  unsigned* cnt2 = (unsigned*)take((size_t)nvt * nb2 * 4);
-  unsigned* toffs2 = (unsigned*)take((size_t)nvt * nb2 * 4);
-  unsigned* bstart = (unsigned*)take(((size_t)nbuckets + 1) * 4);
-  unsigned* big_list = (unsigned*)take((size_t)kBigList * 4);
+  unsigned* bucket = (unsigned*)tc.take((size_t)n * 4);
+  unsigned* bucket2 = (unsigned*)tc.take((size_t)n * 4);
+  unsigned long long* sample = (unsigned long long*)tc.take((size_t)kSample * 8);
+  unsigned long long* sample_alt = (unsigned long long*)tc.take((size_t)kSample * 8);
+  unsigned* sample_rows = (unsigned*)tc.take((size_t)kSample * 4);
+  unsigned* sample_rows_alt = (unsigned*)tc.take((size_t)kSample * 4);
+  unsigned long long* split = (unsigned long long*)tc.take((size_t)(kSplit + 1) * 8);
+  unsigned* flags = (unsigned*)tc.take(kFlagWords * 4);
+  unsigned short* guide = (unsigned short*)tc.take(4097 * 2);
+  unsigned* cnt1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
+  unsigned* toffs1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
+  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * nb1 * 4);
+  unsigned* pstart = (unsigned*)tc.take((size_t)(nb1 + 1) * 4);
+  unsigned* cnt2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
+  unsigned* toffs2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
+  unsigned* bstart = (unsigned*)tc.take(((size_t)nbuckets + 1) * 4);
+  unsigned* big_list = (unsigned*)tc.take((size_t)kBigList * 4);
   unsigned* oversize = (unsigned*)&c->dscalars[26];   // [0] largest bucket nobody can sort, [1] buckets listed for ms_big_kernel
   AH_HIP(c, hipMemsetAsync(oversize, 0, 8, c->stream));
   // 0: the map
@@ -538,19 +511,14 @@ int ah_sort_rest_msd(ah_ctx* c, unsigned long long* keys, unsigned* rows, unsign
   ms_bucket_kernel<<<ah_stream_grid(c, ah_ceil_div(n, kThreads * 4), 2), kThreads, 0, c->stream>>>(keys, n, map, pts, split, flags, guide, nbuckets / kSplit, bucket);
   AH_LAUNCH_CHECK(c);
   // 2: level 1
-  ms_hist_kernel<<<grid1, kThreads, 0, c->stream>>>(bucket, n, nullptr, 1, lb2, (unsigned)(nb1 - 1), nb1, cnt1);
+  tile_hist_kernel<MsDigit><<<grid1, kThreads, 0, c->stream>>>(MsDigit{bucket, lb2, (unsigned)(nb1 - 1)}, n, nullptr, 1, nb1, cnt1);
   AH_LAUNCH_CHECK(c);
-  colsum_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt1, nb1, ntiles, gsum);
-  AH_LAUNCH_CHECK(c);
-  bin_prefix_kernel<<<1, kMaxBins, 0, c->stream>>>(gsum, nb1, ngrp, n, pstart);
-  AH_LAUNCH_CHECK(c);
-  tile_offs_kernel<<<(unsigned)ngrp, kMaxBins, 0, c->stream>>>(cnt1, gsum, nb1, ntiles, toffs1);
-  AH_LAUNCH_CHECK(c);
+  if ((rc = launch_tile_offsets(c, cnt1, nb1, ntiles, n, gsum, toffs1, pstart)) != AH_OK) return rc;
   ms_scatter_kernel<true><<<grid1, kThreads, 0, c->stream>>>(keys, rows, bucket, n, nullptr, 1, lb2, (unsigned)(nb1 - 1), nb1, toffs1, alt_keys,
                                                                         alt_rows, bucket2);
   AH_LAUNCH_CHECK(c);
   // 3: level 2, parent by parent
-  ms_hist_kernel<<<(unsigned)nvt, kThreads, 0, c->stream>>>(bucket2, n, pstart, nb1, 0, (unsigned)(nb2 - 1), nb2, cnt2);
+  tile_hist_kernel<MsDigit><<<(unsigned)nvt, kThreads, 0, c->stream>>>(MsDigit{bucket2, 0, (unsigned)(nb2 - 1)}, n, pstart, nb1, nb2, cnt2);
   AH_LAUNCH_CHECK(c);
   ms_offs2_kernel<<<(unsigned)nb1, kThreads, 0, c->stream>>>(cnt2, pstart, nb1, nb2, toffs2, bstart, n);
   AH_LAUNCH_CHECK(c);

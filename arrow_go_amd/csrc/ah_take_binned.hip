@@ -378,33 +378,18 @@ __global__ __launch_bounds__(kThreads) void unpermute_kernel(const void* __restr
   __shared__ unsigned s_ok[kTile / 32];
   const int64_t tile = xcd_contiguous_tile(ntiles);
   if (tile < 0) return;
-  unsigned excl = 0;
+  unsigned cnt = 0, excl = 0;
   if ((int)threadIdx.x < nb) {
-    s_cnt[threadIdx.x] = cnt_tm[tile * nb + threadIdx.x];
+    cnt = cnt_tm[tile * nb + threadIdx.x];
     excl = toffs[tile * nb + threadIdx.x];
   }
   if (HAS_VALID && threadIdx.x < kTile / 32) s_ok[threadIdx.x] = 0;
-  __syncthreads();
-  block_excl_scan(s_cnt, s_start, s_wsum, nb);
-  if ((int)threadIdx.x < nb) s_goff[threadIdx.x] = excl - s_start[threadIdx.x];
-  __syncthreads();
+  tile_bin_offsets(cnt, excl, nb, s_cnt, s_start, s_goff, s_wsum);
   const int64_t base = tile * kTile;
   const int tile_n = nidx - base >= kTile ? kTile : (int)(nidx - base);
-  // staged position lp → its bin = the LAST b with s_start[b] ≤ lp (empty bins share their start with the next one): the
-  // kRowsPerThread searches of a thread are independent, so their LDS reads overlap; then all loads go out together
-  int lo[kRowsPerThread], hi[kRowsPerThread];
-#pragma unroll
-  for (int k = 0; k < kRowsPerThread; k++) { lo[k] = 0; hi[k] = nb - 1; }
-#pragma unroll 1
-  for (int step = 0; step < 10; step++) {   // 2^10 = kMaxBins
-#pragma unroll
-    for (int k = 0; k < kRowsPerThread; k++) {
-      const int mid = (lo[k] + hi[k] + 1) >> 1;
-      const bool le = s_start[mid] <= (unsigned)(k * kThreads + threadIdx.x);
-      lo[k] = le ? mid : lo[k];
-      hi[k] = le ? hi[k] : mid - 1;
-    }
-  }
+  // the bin of every staged position of this thread (bin_of_staged, ah_bins.h); then all loads go out together
+  int lo[kRowsPerThread];
+  bin_of_staged<kRowsPerThread, kMaxBinSteps>(s_start, nb, 0, lo);
   unsigned r[kRowsPerThread];
   T v[kRowsPerThread];
   bool ok[kRowsPerThread];
@@ -466,15 +451,10 @@ template <typename IdxT>
 int run_front(ah_ctx* c, const Plan& p, const void* idx, const uint8_t* ivalid, int64_t ioff, int64_t nidx, int64_t nvalues, unsigned* cnt_tm,
               unsigned* toffs, unsigned* gsum, unsigned* binstart, unsigned* rec, unsigned long long* first_bad) {
   const unsigned grid = (unsigned)(((p.ntiles + 7) / 8) * 8);
-  const int64_t ngroups = ah_ceil_div(p.ntiles, kGroupTiles);
   bin_hist_kernel<IdxT><<<grid, kHistThreads, 0, c->stream>>>((const IdxT*)idx, ivalid, ioff, nidx, (uint64_t)nvalues, p.shift, p.nb, p.ntiles, cnt_tm, first_bad);
   AH_LAUNCH_CHECK(c);
-  colsum_kernel<<<(unsigned)ngroups, kMaxBins, 0, c->stream>>>(cnt_tm, p.nb, p.ntiles, gsum);
-  AH_LAUNCH_CHECK(c);
-  bin_prefix_kernel<<<1, kMaxBins, 0, c->stream>>>(gsum, p.nb, ngroups, nidx, binstart);
-  AH_LAUNCH_CHECK(c);
-  tile_offs_kernel<<<(unsigned)ngroups, kMaxBins, 0, c->stream>>>(cnt_tm, gsum, p.nb, p.ntiles, toffs);
-  AH_LAUNCH_CHECK(c);
+  const int rc = launch_tile_offsets(c, cnt_tm, p.nb, p.ntiles, nidx, gsum, toffs, binstart);
+  if (rc != AH_OK) return rc;
   bin_scatter_kernel<IdxT><<<grid, kThreads, 0, c->stream>>>((const IdxT*)idx, ivalid, ioff, nidx, (uint64_t)nvalues, p.shift, p.nb, p.ntiles, toffs, rec);
   AH_LAUNCH_CHECK(c);
   return AH_OK;
@@ -578,20 +558,17 @@ int ah_take_binned_try(ah_ctx* c, int byte_width, const void* values, const uint
   }
   // temporaries
   const size_t table = (size_t)p.nb * (size_t)p.ntiles * sizeof(unsigned);
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t need = pad(table) * 2 + pad((size_t)ah_ceil_div(p.ntiles, kGroupTiles) * p.nb * 4) + pad((size_t)(p.nb + 1) * 4) + pad((size_t)nidx * 4) + pad((size_t)nidx * byte_width) + pad((size_t)(nidx / 64 + 2) * 8);
-  uint8_t* base;
-  int rc = ah_temp_reserve(c, need, (void**)&base);
+  const size_t need = ah_pad(table) * 2 + ah_pad((size_t)ah_ceil_div(p.ntiles, kGroupTiles) * p.nb * 4) + ah_pad((size_t)(p.nb + 1) * 4) + ah_pad((size_t)nidx * 4) + ah_pad((size_t)nidx * byte_width) + ah_pad((size_t)(nidx / 64 + 2) * 8);
+  TempCarver tc;
+  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
   if (rc != AH_OK) return rc;
-  size_t used_b = 0;
-  auto take = [&](size_t b) { uint8_t* q = base + used_b; used_b += pad(b); return q; };
-  unsigned* cnt_tm = (unsigned*)take(table);
-  unsigned* toffs = (unsigned*)take(table);
-  unsigned* gsum = (unsigned*)take((size_t)ah_ceil_div(p.ntiles, kGroupTiles) * p.nb * 4);
-  unsigned* binstart = (unsigned*)take((size_t)(p.nb + 1) * 4);
-  unsigned* rec = (unsigned*)take((size_t)nidx * 4);
-  void* gval = take((size_t)nidx * byte_width);
-  unsigned long long* gvalid = (unsigned long long*)take((size_t)(nidx / 64 + 2) * 8);
+  unsigned* cnt_tm = (unsigned*)tc.take(table);
+  unsigned* toffs = (unsigned*)tc.take(table);
+  unsigned* gsum = (unsigned*)tc.take((size_t)ah_ceil_div(p.ntiles, kGroupTiles) * p.nb * 4);
+  unsigned* binstart = (unsigned*)tc.take((size_t)(p.nb + 1) * 4);
+  unsigned* rec = (unsigned*)tc.take((size_t)nidx * 4);
+  void* gval = tc.take((size_t)nidx * byte_width);
+  unsigned long long* gvalid = (unsigned long long*)tc.take((size_t)(nidx / 64 + 2) * 8);
   const bool known = with_index_type(iw, is_signed, [&](auto it) {
     rc = run_front<typename decltype(it)::type>(c, p, idx, ivalid, ioff, nidx, nvalues, cnt_tm, toffs, gsum, binstart, rec, first_bad);
   });

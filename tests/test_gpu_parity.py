@@ -977,6 +977,58 @@ def test_hash_encode_partitioned(hip, orc_be, ctx, lp):
         ctx.set_option("encode_partition", 1)
 
 
+def _assert_encode_equals_oracle(hip, orc_be, keys, valid, off, enc, what):
+    n = keys.size
+    g, e = hip.hash_encode(keys, valid, off, enc), orc_be.hash_encode(keys, valid, off, enc)
+    assert g[2].size == e[2].size and g[3] == e[3], (what, g[2].size, e[2].size, g[3], e[3])
+    bad = np.flatnonzero(g[0] != e[0])
+    assert bad.size == 0, (what, bad.size, bad[:5], g[0][bad[:5]], e[0][bad[:5]])
+    bits = lambda a: np.unpackbits(a, bitorder="little")[:n]
+    assert (bits(g[1]) == bits(e[1])).all() and g[2].tobytes() == e[2].tobytes(), what
+
+
+@pytest.mark.parametrize("group", [1, 2, 4, 8])
+def test_hash_encode_unpermute_group(hip, orc_be, ctx, group):
+    """the final un-permute of the partition-first encode over 1, 2, 4 or 8 consecutive tiles per workgroup (option encode_unperm_group;
+    enc_unpermute_group_kernel<G>): six tiles — for every G the last group is short of tiles and the last tile short of rows — and a
+    second tile of one row; the all-ones key, a validity bitmap at bit offset 5, nulls encoded and masked.  Byte-equal to the
+    sequential memo table."""
+    rng = np.random.default_rng(1300 + group)
+    try:
+        ctx.set_option("encode_partition", 8)
+        ctx.set_option("encode_unperm_group", group)
+        for n in (5 * 4096 + 3, 4096 + 1):
+            keys = rng.integers(0, 3000, n).astype(np.int64) * 1000003
+            keys[rng.integers(0, n, 3)] = -1          # the all-ones key
+            for valid, off in ((None, 0), (rand_bits(rng, n + 16, 0.9), 5)):
+                for enc in (False, True):
+                    _assert_encode_equals_oracle(hip, orc_be, keys, valid, off, enc, (group, n, valid is not None, enc))
+    finally:
+        ctx.set_option("encode_partition", 1)
+        ctx.set_option("encode_unperm_group", 4)
+
+
+@pytest.mark.parametrize("lp", [11, 13])
+@pytest.mark.parametrize("group2", [0, 4])
+def test_hash_encode_unpermute2_group(hip, orc_be, ctx, group2, lp):
+    """the level-2 un-permute of the two-cut encode, one virtual tile per workgroup (option encode_unperm2_group = 0:
+    e2_unpermute_kernel) or four (e2_unpermute_group_kernel<4>), at the smallest length the two-cut path accepts plus a tile and three
+    rows: every parent's last virtual tile is short.  Byte-equal to the sequential memo table."""
+    rng = np.random.default_rng(1400 + lp + group2)
+    n = (1 << 20) + 4096 + 3
+    try:
+        ctx.set_option("encode_partition", lp)
+        ctx.set_option("encode_unperm2_group", group2)
+        keys = rng.integers(0, 1 << 19, n).astype(np.int64) * 1000003
+        keys[rng.integers(0, n, 3)] = -1
+        for valid, off in ((None, 0), (rand_bits(rng, n + 16, 0.9), 5)):
+            for enc in (False, True):
+                _assert_encode_equals_oracle(hip, orc_be, keys, valid, off, enc, (group2, lp, valid is not None, enc))
+    finally:
+        ctx.set_option("encode_partition", 1)
+        ctx.set_option("encode_unperm2_group", 4)
+
+
 @pytest.mark.parametrize("lp,byte_map", [(8, 2), (8, 0), (11, 1), (11, 0)])
 def test_hash_encode_first_occurrence_marks(hip, orc_be, ctx, lp, byte_map):
     """the first-occurrence bitmap of the partition-first encode, both ways (option encode_byte_map): one device-scope atomicOr per key on
@@ -1750,8 +1802,13 @@ def test_sort_indices_msd_path(ctx, hip, orc_be):
         "int64 heavy duplicates (falls back)": rng.integers(0, 2**50, 3000, dtype=np.int64)[rng.integers(0, 3000, n)],
         "int64 one hot key (falls back)": np.where(rng.random(n) < 0.2, np.int64(123456789012345), rng.integers(-2**62, 2**62, n, dtype=np.int64)),
     }
+    # a second length, one row past a tile boundary (n itself ends 57 rows into a tile), with constant high bits: only the low 40 bits
+    # vary, so the bucket map works on shifted keys.  (The map is built from sample quantiles: it fills every level-1 parent
+    # whatever the keys are — a parent without rows is reached through the two-cut encode and group-by, whose parents are hash bits.)
+    cases["int64 constant high bits, a tile and one row more"] = (np.int64(0x5A) << 56) + rng.integers(0, 2**40, (1 << 22) + 4097, dtype=np.int64)
     for name, a in cases.items():
         a = np.ascontiguousarray(a)
+        n = a.size
         if a.dtype.kind == "f":
             a[rng.integers(0, n, 6)] = [np.nan, -np.nan, np.inf, -np.inf, -0.0, 0.0]
         valid = OL.pack_bits(list(rng.random(n + 9) >= 0.03))

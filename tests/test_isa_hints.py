@@ -51,11 +51,22 @@ RESOURCES = {
         # the two-level cut's scatter (round 6): at 68–71 registers one workgroup of 1024 per CU — level 2 ran at 3.5 TB/s, 772 µs; at 64: 660
         (r"gs_scatter_kernelINS_9GsRecordsE", 64, 16),
         (r"gbr_emit_kernel", 64, 0),
+        (r"tile_hist_kernelINS_7GsDigitINS_9GsColumnsE", 54, 0),   # was gs_hist_kernel<GsColumns>
+        (r"tile_hist_kernelINS_7GsDigitINS_9GsRecordsE", 54, 0),   # was gs_hist_kernel<GsRecords>
+    ],
+    "ah_sort_msd.hip": [
+        (r"tile_hist_kernelINS_7MsDigitE", 54, 0),                 # was ms_hist_kernel
+        (r"ms_scatter_kernelILb1E", 63, 0),
+        (r"ms_scatter_kernelILb0E", 60, 0),
     ],
     "ah_hash_part.hip": [
         (r"gb_scatter_kernelILb0E", 64, 0),
         (r"enc_unpermute_group_kernelILi4E", 64, 0),
         (r"e2_unpermute_group_kernelILi4E", 64, 0),
+        # the kernels rewritten over the tile / bin layer of ah_bins.h and ah_msd.h, at the figures they had before
+        (r"enc_unpermute_group_kernelILi1E", 25, 0),   # was enc_unpermute_kernel
+        (r"e2_unpermute_kernel", 25, 0),
+        (r"tile_hist_kernelINS_7E2DigitE", 54, 0),     # was e2_hist_kernel
         (r"enc_table_kernelILi8192ELb1E", 128, 0),
     ],
     "ah_take.hip": [(r"take_vec_kernelILi8EiLb[01]ELi7E", 64, 0)],
