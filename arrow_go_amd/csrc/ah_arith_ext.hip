@@ -1,7 +1,10 @@
-// ah_arith_ext.hip — the exact part of the arithmetic registry beyond + − ×: divide, abs / negate with
-// overflow check, bit-wise and / or / xor / not, shifts, sqrt.
+// ah_arith_ext.hip — the part of the arithmetic registry that knows validity or can fail: checked add / subtract / multiply,
+// divide, abs / negate with overflow check, bit-wise and / or / xor / not, shifts, power, sqrt, floor / ceil / trunc, round.
 //
 // Reference (arrow/compute/internal/kernels):
+//   add, subtract              base_arithmetic.go:249-286: the carry test, through ScalarBinaryNotNull (helpers.go:284-380)
+//   multiply                   :84-106 mulWithOverflow in EVERY slot (ScalarBinary, helpers.go:193-236), null payloads included;
+//                              floats under the three checked names take the unchecked kernels (base_arithmetic_amd64.go:109-117)
 //   divide, divide_unchecked   base_arithmetic.go:154-160, 287-294 (integers: BOTH names refuse a zero divisor in
 //                              a valid slot, "divide by zero"; Go's truncated quotient, MinInt / −1 wraps);
 //                              :386-396 (floats: unchecked = IEEE a / b, checked refuses b == 0)
@@ -21,144 +24,13 @@
 //
 // One kernel shape for all of them: 16 bytes per lane per operand, validity as V bits per lane, one flag word
 // of error bits, 16-byte stores.  HBM-bound like ah_arith.hip except 64-bit integer division (≈ 100 VALU
-// instructions per element).
-#include <type_traits>
-
+// instructions per element).  What an element computes, and which ops skip null slots: ah_elementwise.h.
 #include "ah_common.h"
+#include "ah_elementwise.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-
-template <typename T>
-using Vec16 = T __attribute__((ext_vector_type(16 / sizeof(T))));
-
-// 16-byte aligned operands stream through nontemporal vector accesses (+10–15 % on this chip);
-// element-aligned Arrow slices fall back to the 16-byte struct access.  `aligned` is wave-uniform.
-template <typename ST>
-__device__ __forceinline__ ah_vec16<ST> load16(const ST* base, int64_t i, bool aligned) {
-  ah_vec16<ST> v;
-  if (aligned) {
-    const Vec16<ST> t = __builtin_nontemporal_load((const Vec16<ST>*)base + i);
-    __builtin_memcpy(&v, &t, 16);
-  } else {
-    v = ah_ld16<ST>(base + i * (int64_t)(16 / sizeof(ST)));
-  }
-  return v;
-}
-template <typename ST>
-__device__ __forceinline__ void store16(ST* base, int64_t i, const ah_vec16<ST>& v, bool aligned) {
-  if (aligned) {
-    Vec16<ST> t;
-    __builtin_memcpy(&t, &v, 16);
-    __builtin_nontemporal_store(t, (Vec16<ST>*)base + i);
-  } else {
-    ah_st16<ST>(base + i * (int64_t)(16 / sizeof(ST)), v);
-  }
-}
-
-enum { ERR_OVERFLOW = 1, ERR_DIV_ZERO = 2, ERR_SHIFT = 4, ERR_NEG_SQRT = 8, ERR_NEG_POWER = 16 };
-enum { X_DIV, X_DIV_CHECKED, X_SHL, X_SHL_CHECKED, X_SHR, X_SHR_CHECKED, X_POW_CHECKED, X_BIT_NOT, X_SQRT_CHECKED,  // NotNull
-       X_ABS_CHECKED, X_NEG_CHECKED, X_BIT_AND, X_BIT_OR, X_BIT_XOR, X_POW, X_SQRT, X_FLOOR, X_CEIL, X_TRUNC };  // every slot
-
-constexpr bool NotNull(int x) { return x <= X_SQRT_CHECKED; }
-constexpr bool Unary(int x) { return x == X_BIT_NOT || x == X_SQRT_CHECKED || x == X_ABS_CHECKED || x == X_NEG_CHECKED || x >= X_SQRT; }
-
-template <typename ST, int X>
-__device__ __forceinline__ ST apply(ST a, ST b, unsigned& err) {
-  constexpr bool kFloat = std::is_floating_point<ST>::value;
-  constexpr bool kSigned = !kFloat && ((ST)-1 < (ST)0);
-  constexpr int bits = sizeof(ST) * 8;
-  if constexpr (X == X_DIV || X == X_DIV_CHECKED) {
-    if constexpr (kFloat) {
-      if (X == X_DIV_CHECKED && b == 0) { err |= ERR_DIV_ZERO; return (ST)0; }
-      return a / b;
-    } else {
-      using U = typename std::make_unsigned<ST>::type;
-      if (b == 0) { err |= ERR_DIV_ZERO; return (ST)0; }
-      if constexpr (kSigned) { if (b == (ST)-1) return (ST)((U)0 - (U)a); }  // MinInt / −1 wraps (Go spec, "Integer overflow")
-      return (ST)(a / b);
-    }
-  } else if constexpr (X == X_SHL || X == X_SHL_CHECKED || X == X_SHR || X == X_SHR_CHECKED) {
-    using U = typename std::make_unsigned<ST>::type;
-    constexpr ST maxshift = kSigned ? (ST)(bits - 1) : (ST)bits;  // unsigned 8-bit: bits = 8 fits
-    const bool bad = kSigned ? (b < 0 || b >= maxshift) : ((unsigned long long)b >= (unsigned long long)bits);
-    if (bad) { if (X == X_SHL_CHECKED || X == X_SHR_CHECKED) err |= ERR_SHIFT; return a; }
-    if (X == X_SHL || X == X_SHL_CHECKED) return (ST)((U)a << (int)b);
-    return (ST)(a >> (int)b);  // arithmetic for signed, logical for unsigned
-  } else if constexpr (X == X_BIT_NOT) {
-    return (ST)~a;
-  } else if constexpr (X == X_BIT_AND) {
-    return (ST)(a & b);
-  } else if constexpr (X == X_BIT_OR) {
-    return (ST)(a | b);
-  } else if constexpr (X == X_BIT_XOR) {
-    return (ST)(a ^ b);
-  } else if constexpr (X == X_ABS_CHECKED || X == X_NEG_CHECKED) {
-    if constexpr (kFloat) {
-      return X == X_ABS_CHECKED ? (ST)__builtin_fabs(a) : -a;
-    } else if constexpr (!kSigned) {
-      return a;  // abs of an unsigned value; negate has no unsigned kernel
-    } else {
-      using U = typename std::make_unsigned<ST>::type;
-      constexpr ST tmin = (ST)((U)1 << (bits - 1));
-      if (a == tmin) { err |= ERR_OVERFLOW; return (ST)0; }
-      return X == X_ABS_CHECKED ? (ST)(a < 0 ? -a : a) : (ST)-a;
-    }
-  } else if constexpr (X == X_POW || X == X_POW_CHECKED) {
-    // power_unchecked / power (base_arithmetic.go:226-248, 342-373, 443-446)
-    if constexpr (kFloat) {
-      return (ST)::pow((double)a, (double)b);      // OutT(math.Pow(float64(a), float64(b))) under both names
-    } else {
-      if constexpr (kSigned) {
-        if (b < 0) { err |= ERR_NEG_POWER; return (ST)0; }
-      }
-      if constexpr (X == X_POW) {  // right to left in uint64, narrowed at the end: wraps
-        unsigned long long base = (unsigned long long)a, e = (unsigned long long)b, p = 1;
-        while (e != 0) {
-          if (e & 1) p *= base;
-          base *= base;
-          e >>= 1;
-        }
-        return (ST)p;
-      } else {  // left to right with mulWithOverflow (:84-108: an overflowing product is 0 and the flag sticks)
-        if (b == 0) return (ST)1;
-        const unsigned long long ue = (unsigned long long)b;
-        unsigned long long mask = 1ull << (63 - __builtin_clzll(ue));
-        ST p = (ST)1;
-        bool of = false;
-        while (mask != 0) {
-          ST t;
-          if (__builtin_mul_overflow(p, p, &t)) { of = true; t = (ST)0; }
-          p = t;
-          if (ue & mask) {
-            if (__builtin_mul_overflow(p, a, &t)) { of = true; t = (ST)0; }
-            p = t;
-          }
-          mask >>= 1;
-        }
-        if (of) err |= ERR_OVERFLOW;
-        return p;
-      }
-    }
-  } else if constexpr (X == X_FLOOR || X == X_CEIL || X == X_TRUNC) {
-    // getFloatRoundImpl (rounding.go:180-187): math.Floor / Ceil / Trunc of the value widened to float64 and narrowed
-    // back — exact in the narrow type as well
-    if constexpr (kFloat) {
-      const double v = (double)a;
-      return (ST)(X == X_FLOOR ? __builtin_floor(v) : X == X_CEIL ? __builtin_ceil(v) : __builtin_trunc(v));
-    } else {
-      return a;
-    }
-  } else {  // X_SQRT, X_SQRT_CHECKED
-    if constexpr (kFloat) {
-      if (X == X_SQRT_CHECKED && a < 0) { err |= ERR_NEG_SQRT; return (ST)__builtin_nan(""); }
-      return sizeof(ST) == 4 ? (ST)__builtin_sqrtf((float)a) : (ST)__builtin_sqrt((double)a);
-    } else {
-      return a;
-    }
-  }
-}
 
 // SHAPE: 0 = l[i] ∘ r[i], 1 = l[i] ∘ scalar (and all unary ops), 2 = scalar ∘ r[i]
 template <typename ST, int X, int SHAPE>
@@ -172,8 +44,8 @@ __global__ __launch_bounds__(kBlock) void ext_kernel(const ST* __restrict__ l, c
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nvec; i += stride) {
     VT a, b, o;
-    if (SHAPE != 2) a = load16<ST>(l, i, aligned);
-    if (SHAPE != 1) b = load16<ST>(r, i, aligned);
+    if (SHAPE != 2) a = ah_load16<ST>(l, i, aligned);
+    if (SHAPE != 1) b = ah_load16<ST>(r, i, aligned);
     unsigned vbits = (1u << V) - 1;
     if (NotNull(X)) {
       if (SHAPE != 2 && lv) vbits &= (unsigned)ah_load_bits64(lv, loff + i * V, V);
@@ -181,13 +53,19 @@ __global__ __launch_bounds__(kBlock) void ext_kernel(const ST* __restrict__ l, c
     }
 #pragma unroll
     for (int e = 0; e < V; e++) {
-      unsigned e1 = 0;
-      const ST v = apply<ST, X>(SHAPE == 2 ? scalar : a.v[e], SHAPE == 1 ? scalar : b.v[e], e1);
-      const bool valid = (vbits >> e) & 1;
-      o.v[e] = valid ? v : (ST)0;   // helpers.go:303-306: null slots hold the zero value
-      if (valid) err |= e1;
+      if constexpr (LiveSlotsOnly(X)) {
+        ST v = (ST)0;
+        if ((vbits >> e) & 1) v = apply<ST, X>(SHAPE == 2 ? scalar : a.v[e], SHAPE == 1 ? scalar : b.v[e], err);
+        o.v[e] = v;
+      } else {
+        unsigned e1 = 0;
+        const ST v = apply<ST, X>(SHAPE == 2 ? scalar : a.v[e], SHAPE == 1 ? scalar : b.v[e], e1);
+        const bool valid = (vbits >> e) & 1;
+        o.v[e] = valid ? v : (ST)0;   // helpers.go:303-306: null slots hold the zero value
+        if (valid) err |= e1;
+      }
     }
-    store16<ST>(out, i, o, aligned);
+    ah_store16<ST>(out, i, o, aligned);
   }
   if (blockIdx.x == 0) {  // < V trailing elements
     const int64_t j = nvec * V + threadIdx.x;
@@ -199,9 +77,7 @@ __global__ __launch_bounds__(kBlock) void ext_kernel(const ST* __restrict__ l, c
       if (valid) err |= e1;
     }
   }
-  // one atomic per wave that saw an error, none otherwise
-  for (unsigned bit = 1; bit <= ERR_NEG_POWER; bit <<= 1)
-    if (__any((err & bit) != 0) && (threadIdx.x & 63) == 0) atomicOr(flag, bit);
+  report_errors(err, flag);
 }
 
 template <typename ST, int X>
@@ -224,10 +100,11 @@ int launch(ah_ctx* c, int shape, const void* l, const uint8_t* lv, int64_t loff,
   return AH_OK;
 }
 
+#define AH_X(X) return launch<ST, X>(c, shape, l, lv, loff, r, rv, roff, out, len, flag)
+
 template <typename ST>
 int dispatch_int(ah_ctx* c, int op, int shape, const void* l, const uint8_t* lv, int64_t loff, const void* r, const uint8_t* rv, int64_t roff,
                  void* out, int64_t len, unsigned* flag) {
-#define AH_X(X) return launch<ST, X>(c, shape, l, lv, loff, r, rv, roff, out, len, flag)
   switch (op) {
     case AH_OP_DIV: AH_X(X_DIV);
     case AH_OP_DIV_CHECKED: AH_X(X_DIV_CHECKED);
@@ -249,6 +126,18 @@ int dispatch_int(ah_ctx* c, int op, int shape, const void* l, const uint8_t* lv,
   return ah_fail(c, AH_ENOTIMPL, "arithmetic: op %d is not defined for this integer type", op);
 }
 
+// the checked names of ah_arith.hip's three ops, integers only
+template <typename ST>
+int dispatch_checked(ah_ctx* c, int op, int shape, const void* l, const uint8_t* lv, int64_t loff, const void* r, const uint8_t* rv, int64_t roff,
+                     void* out, int64_t len, unsigned* flag) {
+  switch (op) {
+    case AH_OP_ADD_CHECKED: AH_X(X_ADD_CHECKED);
+    case AH_OP_SUB_CHECKED: AH_X(X_SUB_CHECKED);
+    case AH_OP_MUL_CHECKED: AH_X(X_MUL_CHECKED);
+  }
+  return ah_fail(c, AH_ENOTIMPL, "arithmetic_checked: unsupported op %d", op);
+}
+
 template <typename ST>
 int dispatch_float(ah_ctx* c, int op, int shape, const void* l, const uint8_t* lv, int64_t loff, const void* r, const uint8_t* rv, int64_t roff,
                    void* out, int64_t len, unsigned* flag) {
@@ -264,28 +153,15 @@ int dispatch_float(ah_ctx* c, int op, int shape, const void* l, const uint8_t* l
     case AH_OP_CEIL: AH_X(X_CEIL);
     case AH_OP_TRUNC: AH_X(X_TRUNC);
   }
-#undef AH_X
   return ah_fail(c, AH_ENOTIMPL, "arithmetic: op %d is not defined for floating point", op);
 }
+#undef AH_X
 
 // ---- round / round_to_multiple (kernels/rounding.go:321-370, 562-598) --------------------------------------------
 // MODE: RoundMode (rounding.go:40-59).  MULTIPLE: round_to_multiple (scale = the multiple: divide, round, multiply);
 // otherwise scale = 10^|ndigits| (multiply first when ndigits ≥ 0, divide first when negative).  Arithmetic in T, the
 // rounding primitives in double — as the Go code has it.  Inf / NaN and values that are integral after scaling pass
 // through; a non-finite result in a valid slot is "overflow".  ScalarUnaryNotNull: null slots hold 0.
-template <typename T>
-__device__ __forceinline__ T round_impl(T v, int mode) {
-  const double d = (double)v;
-  switch (mode) {
-    case 0: case 4: return (T)__builtin_floor(d);                                   // RoundDown, HalfDown (tie)
-    case 1: case 5: return (T)__builtin_ceil(d);                                    // RoundUp, HalfUp (tie)
-    case 2: case 6: return (T)__builtin_trunc(d);                                   // TowardsZero, HalfTowardsZero (tie)
-    case 3: case 7: return (T)(__builtin_signbit(d) ? __builtin_floor(d) : __builtin_ceil(d));  // AwayFromZero, HalfAwayFromZero (tie)
-    case 8: return (T)__builtin_rint(d);                                            // HalfToEven: math.RoundToEven
-    default: return (T)(__builtin_floor(d * 0.5) + __builtin_ceil(d * 0.5));        // HalfToOdd
-  }
-}
-
 template <typename T, bool MULTIPLE>
 __global__ __launch_bounds__(kBlock) void round_kernel(const T* __restrict__ in, const uint8_t* __restrict__ valid, int64_t off, int64_t n,
                                                         T scale, int ndigits_sign, int mode, T* __restrict__ out, unsigned* __restrict__ flag) {
@@ -311,7 +187,18 @@ __global__ __launch_bounds__(kBlock) void round_kernel(const T* __restrict__ in,
     }
     out[i] = res;
   }
-  if (__any(err != 0) && (threadIdx.x & 63) == 0) atomicOr(flag, (unsigned)ERR_OVERFLOW);
+  report_errors(err, flag);
+}
+
+// the flag word around a launch: cleared, `launch(flag)`, and — where the op can fail — read back and turned into the error
+template <class F>
+int run_flagged(ah_ctx* c, bool can_fail, F&& launch) {
+  unsigned* flag = (unsigned*)c->dscalars;
+  unsigned bits = 0;
+  int rc = ah_flag_clear(c, flag);
+  if (rc == AH_OK) rc = launch(flag);
+  if (rc == AH_OK && can_fail) rc = ah_flag_read(c, flag, &bits);
+  return rc == AH_OK ? ah_error_of_flag(c, bits) : rc;
 }
 
 bool is_unary_op(int op) {
@@ -320,6 +207,18 @@ bool is_unary_op(int op) {
 }
 
 }  // namespace
+
+int ah_error_of_flag(ah_ctx* c, unsigned bits) {   // first match in this order
+  static const struct { unsigned bit; int code; const char* text; } kErrors[] = {
+      {ERR_OVERFLOW, AH_EOVERFLOW, "overflow"},
+      {ERR_DIV_ZERO, AH_EINVALID, "divide by zero"},
+      {ERR_SHIFT, AH_EINVALID, "shift amount must be >= 0 and less than precision of type"},
+      {ERR_NEG_SQRT, AH_EINVALID, "square root of negative number"},
+      {ERR_NEG_POWER, AH_EINVALID, "integers to negative integer powers are not allowed"}};
+  for (const auto& e : kErrors)
+    if (bits & e.bit) return ah_fail(c, e.code, "%s", e.text);
+  return AH_OK;
+}
 
 AH_EXPORT int ah_arithmetic_ext(ah_ctx* c, int type, int op, int shape, const void* l, const uint8_t* lvalid, int64_t loff, const void* r,
                                 const uint8_t* rvalid, int64_t roff, int scalar_valid, void* out, int64_t len) {
@@ -343,36 +242,47 @@ AH_EXPORT int ah_arithmetic_ext(ah_ctx* c, int type, int op, int shape, const vo
     AH_HIP(c, hipMemsetAsync(out, 0, (size_t)len * w, c->stream));
     return AH_OK;
   }
-  unsigned* flag = (unsigned*)c->dscalars;
-  AH_HIP(c, hipMemsetAsync(flag, 0, sizeof(unsigned), c->stream));
-  int rc;
-  switch (type) {
-    case AH_UINT8: rc = dispatch_int<uint8_t>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    case AH_INT8: rc = dispatch_int<int8_t>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    case AH_UINT16: rc = dispatch_int<uint16_t>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    case AH_INT16: rc = dispatch_int<int16_t>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    case AH_UINT32: rc = dispatch_int<uint32_t>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    case AH_INT32: rc = dispatch_int<int32_t>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    case AH_UINT64: rc = dispatch_int<uint64_t>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    case AH_INT64: rc = dispatch_int<int64_t>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    case AH_FLOAT32: rc = dispatch_float<float>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    case AH_FLOAT64: rc = dispatch_float<double>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag); break;
-    default: return ah_fail(c, AH_ENOTIMPL, "arithmetic: unsupported type id %d", type);
-  }
-  if (rc != AH_OK) return rc;
-  if (op == AH_OP_DIV && (type == AH_FLOAT32 || type == AH_FLOAT64)) return AH_OK;  // cannot fail: no readback
-  if (op == AH_OP_BIT_AND || op == AH_OP_BIT_OR || op == AH_OP_BIT_XOR || op == AH_OP_BIT_NOT || op == AH_OP_SQRT || op == AH_OP_SHIFT_LEFT ||
-      op == AH_OP_SHIFT_RIGHT || op == AH_OP_FLOOR || op == AH_OP_CEIL || op == AH_OP_TRUNC)
+  const bool cannot_fail = (op == AH_OP_DIV && (type == AH_FLOAT32 || type == AH_FLOAT64)) || op == AH_OP_BIT_AND || op == AH_OP_BIT_OR ||
+                           op == AH_OP_BIT_XOR || op == AH_OP_BIT_NOT || op == AH_OP_SQRT || op == AH_OP_SHIFT_LEFT || op == AH_OP_SHIFT_RIGHT ||
+                           op == AH_OP_FLOOR || op == AH_OP_CEIL || op == AH_OP_TRUNC;   // no readback
+  return run_flagged(c, !cannot_fail, [&](unsigned* flag) {
+    int rc = AH_OK;
+    const bool known = with_numeric_type(type, [&](auto t) {
+      using T = typename decltype(t)::type;
+      if constexpr (__is_floating_point(T)) rc = dispatch_float<T>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag);
+      else rc = dispatch_int<T>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag);
+    });
+    return known ? rc : ah_fail(c, AH_ENOTIMPL, "arithmetic: unsupported type id %d", type);
+  });
+}
+
+AH_EXPORT int ah_arithmetic_checked(ah_ctx* c, int type, int8_t op, int shape,
+                                    const void* l, const uint8_t* lvalid, int64_t loff,
+                                    const void* r, const uint8_t* rvalid, int64_t roff,
+                                    int scalar_valid, void* out, int64_t len) {
+  AH_ENTER(c);
+  if (len < 0) return ah_fail(c, AH_EINVALID, "arithmetic_checked: negative length");
+  if (len == 0) return AH_OK;
+  if (shape < AH_SHAPE_AA || shape > AH_SHAPE_SA) return ah_fail(c, AH_EINVALID, "arithmetic_checked: bad shape %d", shape);
+  // floats: checked == unchecked SIMD kernels (base_arithmetic_amd64.go:109-117)
+  if (type == AH_FLOAT32 || type == AH_FLOAT64) return ah_arith_binary(c, type, op, shape, l, r, out, len);
+  if (op != AH_OP_ADD_CHECKED && op != AH_OP_SUB_CHECKED && op != AH_OP_MUL_CHECKED)
+    return ah_fail(c, AH_ENOTIMPL, "arithmetic_checked: unsupported op %d", op);
+  int w = ah_type_width(type);
+  if (!w) return ah_fail(c, AH_ENOTIMPL, "arithmetic_checked: unsupported type id %d", type);
+  if (op != AH_OP_MUL_CHECKED && shape != AH_SHAPE_AA && !scalar_valid) {
+    // null scalar: output stays as allocated = zero (helpers.go:312-314,341-343)
+    AH_HIP(c, hipMemsetAsync(out, 0, (size_t)len * w, c->stream));
     return AH_OK;
-  AH_HIP(c, hipMemcpyAsync(c->pinned, flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-  AH_HIP(c, hipStreamSynchronize(c->stream));
-  const unsigned f = *(volatile unsigned*)c->pinned;
-  if (f & ERR_OVERFLOW) return ah_fail(c, AH_EOVERFLOW, "overflow");
-  if (f & ERR_DIV_ZERO) return ah_fail(c, AH_EINVALID, "divide by zero");
-  if (f & ERR_SHIFT) return ah_fail(c, AH_EINVALID, "shift amount must be >= 0 and less than precision of type");
-  if (f & ERR_NEG_SQRT) return ah_fail(c, AH_EINVALID, "square root of negative number");
-  if (f & ERR_NEG_POWER) return ah_fail(c, AH_EINVALID, "integers to negative integer powers are not allowed");
-  return AH_OK;
+  }
+  return run_flagged(c, true, [&](unsigned* flag) {
+    int rc = AH_OK;
+    const bool known = with_numeric_type(type, [&](auto t) {
+      using T = typename decltype(t)::type;
+      if constexpr (!__is_floating_point(T)) rc = dispatch_checked<T>(c, op, shape, l, lvalid, loff, r, rvalid, roff, out, len, flag);
+    });
+    return known ? rc : ah_fail(c, AH_ENOTIMPL, "arithmetic_checked: unsupported type id %d", type);
+  });
 }
 
 AH_EXPORT int ah_round(ah_ctx* c, int type, const void* values, const uint8_t* valid, int64_t off, int64_t n, int64_t ndigits, int mode,
@@ -383,22 +293,19 @@ AH_EXPORT int ah_round(ah_ctx* c, int type, const void* values, const uint8_t* v
   if (type != AH_FLOAT32 && type != AH_FLOAT64) return ah_fail(c, AH_ENOTIMPL, "round: unsupported type id %d", type);
   if (n == 0) return AH_OK;
   if (!values || !out) return ah_fail(c, AH_EINVALID, "round: null buffer");
-  unsigned* flag = (unsigned*)c->dscalars;
-  AH_HIP(c, hipMemsetAsync(flag, 0, sizeof(unsigned), c->stream));
   const unsigned grid = ah_stream_grid(c, ah_ceil_div(n, kBlock), /*default_bpc=*/8);
   const int sgn = ndigits > 0 ? 1 : (ndigits < 0 ? -1 : 0);
-  if (type == AH_FLOAT32) {
-    float scale = (float)pow10;
-    if (multiple_host) { memcpy(&scale, multiple_host, 4); round_kernel<float, true><<<grid, kBlock, 0, c->stream>>>((const float*)values, valid, off, n, scale, 0, mode, (float*)out, flag); }
-    else round_kernel<float, false><<<grid, kBlock, 0, c->stream>>>((const float*)values, valid, off, n, scale, sgn, mode, (float*)out, flag);
-  } else {
-    double scale = pow10;
-    if (multiple_host) { memcpy(&scale, multiple_host, 8); round_kernel<double, true><<<grid, kBlock, 0, c->stream>>>((const double*)values, valid, off, n, scale, 0, mode, (double*)out, flag); }
-    else round_kernel<double, false><<<grid, kBlock, 0, c->stream>>>((const double*)values, valid, off, n, scale, sgn, mode, (double*)out, flag);
-  }
-  AH_LAUNCH_CHECK(c);
-  AH_HIP(c, hipMemcpyAsync(c->pinned, flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-  AH_HIP(c, hipStreamSynchronize(c->stream));
-  if (*(volatile unsigned*)c->pinned & ERR_OVERFLOW) return ah_fail(c, AH_EOVERFLOW, "overflow");
-  return AH_OK;
+  return run_flagged(c, true, [&](unsigned* flag) {
+    if (type == AH_FLOAT32) {
+      float scale = (float)pow10;
+      if (multiple_host) { memcpy(&scale, multiple_host, 4); round_kernel<float, true><<<grid, kBlock, 0, c->stream>>>((const float*)values, valid, off, n, scale, 0, mode, (float*)out, flag); }
+      else round_kernel<float, false><<<grid, kBlock, 0, c->stream>>>((const float*)values, valid, off, n, scale, sgn, mode, (float*)out, flag);
+    } else {
+      double scale = pow10;
+      if (multiple_host) { memcpy(&scale, multiple_host, 8); round_kernel<double, true><<<grid, kBlock, 0, c->stream>>>((const double*)values, valid, off, n, scale, 0, mode, (double*)out, flag); }
+      else round_kernel<double, false><<<grid, kBlock, 0, c->stream>>>((const double*)values, valid, off, n, scale, sgn, mode, (double*)out, flag);
+    }
+    AH_LAUNCH_CHECK(c);
+    return (int)AH_OK;
+  });
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <initializer_list>
+#include <type_traits>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stddef.h>
@@ -167,6 +168,8 @@ static inline bool ah_fcache_overlaps(const ah_ctx* c, const void* p, size_t nby
 #define AH_LAUNCH_CHECK(ctx) AH_HIP((ctx), hipGetLastError())
 
 void ah_expr_cache_free(ah_ctx* ctx);  // ah_expr.hip
+// internal (ah_arith.hip): the unchecked add / subtract / multiply of any shape — what the checked names are for floats
+int ah_arith_binary(ah_ctx* ctx, int type, int op, int shape, const void* l, const void* r, void* out, int64_t len);
 // internal (ah_sort.hip): stable radix partition of (value bits, group id) pairs for the group-by of
 // ah_hash.hip — by (id >> shift) & 255 (passes = 1) or by (id >> shift) & 65535 (passes = 2, LSD; alt_*
 // is the intermediate buffer).  A row whose value is null (vvalid bit clear) travels with bit 31 of
@@ -259,6 +262,48 @@ static inline int ah_type_width(int type) {
 
 static inline int64_t ah_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+template <typename T> struct TypeTag { using type = T; };
+// numeric type id → f(TypeTag<T>{}); false (and no call) for any other id — what that means is the call site's decision
+template <class F>
+inline bool with_numeric_type(int type, F&& f) {
+  switch (type) {
+    case AH_UINT8: f(TypeTag<uint8_t>{}); return true;
+    case AH_INT8: f(TypeTag<int8_t>{}); return true;
+    case AH_UINT16: f(TypeTag<uint16_t>{}); return true;
+    case AH_INT16: f(TypeTag<int16_t>{}); return true;
+    case AH_UINT32: f(TypeTag<uint32_t>{}); return true;
+    case AH_INT32: f(TypeTag<int32_t>{}); return true;
+    case AH_UINT64: f(TypeTag<uint64_t>{}); return true;
+    case AH_INT64: f(TypeTag<int64_t>{}); return true;
+    case AH_FLOAT32: f(TypeTag<float>{}); return true;
+    case AH_FLOAT64: f(TypeTag<double>{}); return true;
+  }
+  return false;
+}
+// … with a signed integer type as the unsigned type of its width: the carrier of the wrapping kernels
+template <class F>
+inline bool with_numeric_carrier(int type, F&& f) {
+  return with_numeric_type(type, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if constexpr (__is_floating_point(T)) f(t);
+    else f(TypeTag<typename std::make_unsigned<T>::type>{});
+  });
+}
+
+// The error flag word of a kernel that can fail (bits: ah_elementwise.h), a word of dscalars: cleared on the stream before the
+// launch, and brought home after it — a copy to pinned memory and a synchronisation of the stream.
+static inline int ah_flag_clear(ah_ctx* c, unsigned* flag) {
+  AH_HIP(c, hipMemsetAsync(flag, 0, sizeof(unsigned), c->stream));
+  return AH_OK;
+}
+static inline int ah_flag_read(ah_ctx* c, const unsigned* flag, unsigned* bits) {
+  AH_HIP(c, hipMemcpyAsync(c->pinned, flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  AH_HIP(c, hipStreamSynchronize(c->stream));
+  *bits = *(volatile unsigned*)c->pinned;
+  return AH_OK;
+}
+int ah_error_of_flag(ah_ctx* ctx, unsigned bits);   // ah_arith_ext.hip: those bits as the reference's error, AH_OK for none
+
 // ---- device helpers ------------------------------------------------------------
 #define AH_WAVE 64
 
@@ -308,6 +353,33 @@ __device__ __forceinline__ void ah_st16(T* p, const ah_vec16<T>& x) {
 #pragma unroll
   for (int j = 0; j < (int)(16 / sizeof(T)); j++) raw[j] = x.v[j];
   *reinterpret_cast<ah_raw16<T>*>(p) = raw;
+}
+
+// Vector i of a column as the validity-aware kernels take it (ah_arith_ext.hip): 16-byte aligned operands stream through
+// nontemporal vector accesses (+10–15 % on this chip); element-aligned Arrow slices fall back to the 16-byte
+// struct access.  `aligned` is wave-uniform.
+template <typename T>
+using ah_aligned16 = T __attribute__((ext_vector_type(16 / sizeof(T))));
+template <typename ST>
+__device__ __forceinline__ ah_vec16<ST> ah_load16(const ST* base, int64_t i, bool aligned) {
+  ah_vec16<ST> v;
+  if (aligned) {
+    const ah_aligned16<ST> t = __builtin_nontemporal_load((const ah_aligned16<ST>*)base + i);
+    __builtin_memcpy(&v, &t, 16);
+  } else {
+    v = ah_ld16<ST>(base + i * (int64_t)(16 / sizeof(ST)));
+  }
+  return v;
+}
+template <typename ST>
+__device__ __forceinline__ void ah_store16(ST* base, int64_t i, const ah_vec16<ST>& v, bool aligned) {
+  if (aligned) {
+    ah_aligned16<ST> t;
+    __builtin_memcpy(&t, &v, 16);
+    __builtin_nontemporal_store(t, (ah_aligned16<ST>*)base + i);
+  } else {
+    ah_st16<ST>(base + i * (int64_t)(16 / sizeof(ST)), v);
+  }
 }
 
 template <typename T>

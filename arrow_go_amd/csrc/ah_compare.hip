@@ -204,17 +204,7 @@ AH_EXPORT int ah_comparison(ah_ctx* c, int cmpop, int shape, int type, const voi
   const void* arr0 = shape == AH_SHAPE_SA ? r : l;
   if ((((uintptr_t)arr0 | (shape == AH_SHAPE_AA ? (uintptr_t)r : 0)) & (uintptr_t)(w - 1)) != 0)
     return ah_fail(c, AH_EINVALID, "comparison: buffer not element-aligned");
-  switch (type) {
-    case AH_UINT8: return dispatch_compare<uint8_t>(c, cmpop, shape, l, r, out_bits, length, prefix);
-    case AH_INT8: return dispatch_compare<int8_t>(c, cmpop, shape, l, r, out_bits, length, prefix);
-    case AH_UINT16: return dispatch_compare<uint16_t>(c, cmpop, shape, l, r, out_bits, length, prefix);
-    case AH_INT16: return dispatch_compare<int16_t>(c, cmpop, shape, l, r, out_bits, length, prefix);
-    case AH_UINT32: return dispatch_compare<uint32_t>(c, cmpop, shape, l, r, out_bits, length, prefix);
-    case AH_INT32: return dispatch_compare<int32_t>(c, cmpop, shape, l, r, out_bits, length, prefix);
-    case AH_UINT64: return dispatch_compare<uint64_t>(c, cmpop, shape, l, r, out_bits, length, prefix);
-    case AH_INT64: return dispatch_compare<int64_t>(c, cmpop, shape, l, r, out_bits, length, prefix);
-    case AH_FLOAT32: return dispatch_compare<float>(c, cmpop, shape, l, r, out_bits, length, prefix);
-    case AH_FLOAT64: return dispatch_compare<double>(c, cmpop, shape, l, r, out_bits, length, prefix);
-  }
+  int rc = AH_OK;
+  if (with_numeric_type(type, [&](auto t) { rc = dispatch_compare<typename decltype(t)::type>(c, cmpop, shape, l, r, out_bits, length, prefix); })) return rc;
   return ah_fail(c, AH_ENOTIMPL, "comparison: unsupported type id %d", type);
 }

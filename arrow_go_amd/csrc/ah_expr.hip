@@ -13,8 +13,11 @@
 // Semantics are those of the per-call execution, bit for bit: every call on this path has
 // NullHandling = NullIntersection (validity = AND of the operands' validity), unchecked
 // kernels compute every slot (null payloads included), checked integer kernels write 0 under
-// nulls and fail with "overflow" by the reference's carry test (see ah_arith.hip), compares
-// produce bits, and/or/xor/and_not/invert are the plain (non-Kleene) bitmap ops.  Float
+// nulls and fail with "overflow" by the reference's carry test, compares produce bits,
+// and/or/xor/and_not/invert are the plain (non-Kleene) bitmap ops.  What a call computes is
+// not restated here: the generated source includes ah_elementwise.h — the text the per-call
+// kernels are compiled from, handed to hiprtc as a named header — and calls apply_unary /
+// apply_binary / apply of it; only float + − × and the comparisons are infix.  Float
 // contraction is disabled (-ffp-contract=off): a*b+c rounds twice, like two kernels.
 // No implicit casts: the operands of a call must have the same type (→ AH_ENOTIMPL).
 #include <hip/hiprtc.h>
@@ -91,7 +94,13 @@ bool ValuePreserving(int from, int to) {
   return from == AH_FLOAT32 && to == AH_FLOAT64;
 }
 
+// the text of ah_elementwise.h, wrapped into a string literal by the Makefile
+const char kOpsText[] =
+#include "build/ah_elementwise_text.inc"
+    ;
+
 const char* kPrelude = R"SRC(
+#include "ah_elementwise.h"
 typedef unsigned long long u64;
 struct Params {
   const void* col[16]; const unsigned char* valid[16]; long long off[16];
@@ -120,28 +129,6 @@ __device__ __forceinline__ void store_word(unsigned char* out, long long row0, i
   int nb = (cnt + 7) >> 3;
   for (int b = 0; b < nb; b++) p[b] = (unsigned char)(w >> (8 * b));
 }
-// checked integer ops: the reference's carry test (kernels/base_arithmetic.go:249-286,84-106)
-template <typename T, typename U, bool SIGNED, int OP>
-__device__ __forceinline__ T chk(T a, T b, bool valid, bool& ovf) {
-  const int bits = sizeof(T) * 8;
-  if (OP == 2) {
-    const T tmin = SIGNED ? (T)((U)1 << (bits - 1)) : (T)0;
-    const T tmax = SIGNED ? (T)(~((U)1 << (bits - 1))) : (T)~(U)0;
-    bool o = false;
-    if (a > 0) { if (b > 0) { if (a > (T)(tmax / b)) o = true; } else { if (b < (T)(tmin / a)) o = true; } }
-    else if (b > 0) { if (a < (T)(tmin / b)) o = true; }
-    else { if (a != 0 && b < (T)(tmax / a)) o = true; }
-    ovf |= o;
-    return o ? (T)0 : (T)((U)a * (U)b);
-  }
-  if (!valid) return (T)0;
-  U ua = (U)a, ub = (U)b, o, cy;
-  if (OP == 0) { o = (U)(ua + ub); cy = (U)((ua & ub) | ((ua | ub) & (U)~o)); }
-  else { o = (U)(ua - ub); cy = (U)(((U)~ua & ub) | ((U) ~(ua ^ ub) & o)); }
-  bool top = (cy >> (bits - 1)) & 1, next = (cy >> (bits - 2)) & 1;
-  ovf |= SIGNED ? (!top && next) : top;
-  return (T)o;
-}
 )SRC";
 
 struct NodeVal { int type; std::string v, ok; };
@@ -153,7 +140,6 @@ int Generate(ah_ctx* c, const ah_expr_node* nodes, int n_nodes, const int* col_t
   std::vector<NodeVal> stack;
   std::vector<bool> col_used(n_cols, false);
   int tmp = 0;
-  char buf[512];
   auto push = [&](int type, const std::string& expr, const std::string& ok) {
     std::string v = "v" + std::to_string(tmp), k = "k" + std::to_string(tmp);
     tmp++;
@@ -175,17 +161,8 @@ int Generate(ah_ctx* c, const ah_expr_node* nodes, int n_nodes, const int* col_t
       if (stack.empty()) return ah_fail(c, AH_EINVALID, "expr: stack underflow");
       NodeVal a = stack.back(); stack.pop_back();
       if (!IsNum(a.type)) return ah_fail(c, AH_ENOTIMPL, "expr: unary arithmetic needs a numeric operand");
-      std::string T = CType(a.type), ex;
-      if (op == AH_X_NEGATE) ex = IsInt(a.type) ? "(" + T + ")((" + UType(a.type) + ")0 - (" + UType(a.type) + ")" + a.v + ")" : "-" + a.v;
-      else if (op == AH_X_ABS) {
-        if (IsFloat(a.type)) ex = "__builtin_fabs" + std::string(a.type == AH_FLOAT32 ? "f" : "") + "(" + a.v + ")";
-        else if (!IsSigned(a.type)) ex = a.v;
-        else ex = "(" + T + ")(((" + UType(a.type) + ")" + a.v + " + (" + a.v + " < 0 ? (" + UType(a.type) + ")~(" + UType(a.type) + ")0 : (" + UType(a.type) + ")0)) ^ (" + a.v + " < 0 ? (" + UType(a.type) + ")~(" + UType(a.type) + ")0 : (" + UType(a.type) + ")0))";
-      } else {
-        if (IsFloat(a.type)) ex = "(" + a.v + " != " + a.v + ") ? " + a.v + " : (" + a.v + " == 0 ? (" + T + ")0 : (__builtin_signbit(" + a.v + ") ? (" + T + ")-1 : (" + T + ")1))";
-        else if (!IsSigned(a.type)) ex = "(" + T + ")(" + a.v + " > 0 ? 1 : 0)";
-        else ex = "(" + T + ")(" + a.v + " > 0 ? 1 : (" + a.v + " ? -1 : 0))";
-      }
+      const char* opc = op == AH_X_NEGATE ? "OP_NEG" : op == AH_X_ABS ? "OP_ABS" : "OP_SIGN";
+      std::string ex = std::string("apply_unary<") + CType(a.type) + ", " + opc + ">(" + a.v + ")";
       push(a.type, ex, a.ok);
     } else if (op == AH_X_CAST) {
       if (stack.empty()) return ah_fail(c, AH_EINVALID, "expr: stack underflow");
@@ -209,17 +186,21 @@ int Generate(ah_ctx* c, const ah_expr_node* nodes, int n_nodes, const int* col_t
         if (!IsNum(a.type)) return ah_fail(c, AH_ENOTIMPL, "expr: arithmetic needs numeric operands");
         int base = (op - AH_X_ADD) % 3;  // 0 add, 1 sub, 2 mul
         bool checked = op >= AH_X_ADD_CHECKED && IsInt(a.type);  // checked float == unchecked (base_arithmetic_amd64.go:109-117)
-        const char* sym = base == 0 ? "+" : base == 1 ? "-" : "*";
         std::string ex;
-        if (checked) {
+        if (checked) {  // the slot rule of ext_kernel (ah_arith_ext.hip): a NotNull op holds 0 and reports nothing under a null
           e->has_checked = true;
-          snprintf(buf, sizeof buf, "chk<%s, %s, %s, %d>(%s, %s, %s, ovf)", T.c_str(), UType(a.type), IsSigned(a.type) ? "true" : "false", base,
-                   a.v.c_str(), b.v.c_str(), ("(" + ok + ")").c_str());
-          ex = buf;
+          const char* x = base == 0 ? "X_ADD_CHECKED" : base == 1 ? "X_SUB_CHECKED" : "X_MUL_CHECKED";
+          std::string t = "t" + std::to_string(tmp), e1 = "e" + std::to_string(tmp);
+          body += "        unsigned " + e1 + " = 0;\n";
+          body += "        const " + T + " " + t + " = apply<" + T + ", " + x + ">(" + a.v + ", " + b.v + ", " + e1 + ");\n";
+          body += (base == 2 ? "        " : "        if (" + ok + ") ") + "err |= " + e1 + ";\n";   // multiply: every slot
+          ex = base == 2 ? t : "(" + ok + ") ? " + t + " : (" + T + ")0";
         } else if (IsInt(a.type)) {
-          ex = "(" + T + ")((" + UType(a.type) + ")" + a.v + " " + sym + " (" + UType(a.type) + ")" + b.v + ")";
-        } else {
-          ex = a.v + " " + sym + " " + b.v;
+          const char* opc = base == 0 ? "OP_ADD" : base == 1 ? "OP_SUB" : "OP_MUL";
+          std::string U = UType(a.type);
+          ex = "(" + T + ")apply_binary<" + U + ", " + opc + ">((" + U + ")" + a.v + ", (" + U + ")" + b.v + ")";
+        } else {  // a language primitive, not a definition: stays infix
+          ex = a.v + " " + (base == 0 ? "+" : base == 1 ? "-" : "*") + " " + b.v;
         }
         push(a.type, ex, ok);
       } else if (op >= AH_X_EQ && op <= AH_X_LE) {
@@ -247,7 +228,7 @@ int Generate(ah_ctx* c, const ah_expr_node* nodes, int n_nodes, const int* col_t
          "  // wave-uniform on purpose (readfirstlane): row0 / cnt / bitmap addresses then live in SGPRs and\n"
          "  // the validity words are fetched once per wave instead of once per lane\n"
          "  const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));\n"
-         "  bool ovf = false;\n";
+         "  unsigned err = 0;\n";
   for (int l = 0; l < n_lits; l++) {
     std::string li = std::to_string(l);
     if (lit_types[l] == AH_BOOL_T) src += "  const bool l" + li + " = (p.lit[" + li + "] & 1) != 0;\n";
@@ -281,18 +262,20 @@ int Generate(ah_ctx* c, const ah_expr_node* nodes, int n_nodes, const int* col_t
   }
   src += "        if (p.out_valid) { u64 w = __ballot(inb && " + r.ok + "); if (lane == 0 && cnt > 0) store_word(p.out_valid, row0, cnt, w); }\n";
   src += "      }\n    }\n  }\n";
-  src += "  if (__any(ovf) && lane == 0) atomicOr(p.flag, 1u);\n}\n";
+  src += "  report_errors(err, p.flag);\n}\n";
   e->source = std::move(src);
   return AH_OK;
 }
 
-int Compile(ah_ctx* c, ah_expr* e) {
+// source → gfx950 code object (`code` may be null: compile only); ah_elementwise.h is the one header the source names
+int CompileSource(ah_ctx* c, const std::string& source, std::vector<char>* code) {
   hiprtcProgram prog;
-  if (hiprtcCreateProgram(&prog, e->source.c_str(), "ah_expr.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
+  const char* headers[] = {kOpsText};
+  const char* names[] = {"ah_elementwise.h"};
+  if (hiprtcCreateProgram(&prog, source.c_str(), "ah_expr.hip", 1, headers, names) != HIPRTC_SUCCESS)
     return ah_fail(c, AH_EHIP, "expr: hiprtcCreateProgram failed");
   const char* opts[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
-  hiprtcResult r = hiprtcCompileProgram(prog, 4, opts);
-  if (r != HIPRTC_SUCCESS) {
+  if (hiprtcCompileProgram(prog, 4, opts) != HIPRTC_SUCCESS) {
     size_t ls = 0;
     hiprtcGetProgramLogSize(prog, &ls);
     std::string log(ls, ' ');
@@ -300,11 +283,20 @@ int Compile(ah_ctx* c, ah_expr* e) {
     hiprtcDestroyProgram(&prog);
     return ah_fail(c, AH_EHIP, "expr: hiprtc compile failed: %.400s", log.c_str());
   }
-  size_t cs = 0;
-  hiprtcGetCodeSize(prog, &cs);
-  std::vector<char> code(cs);
-  hiprtcGetCode(prog, code.data());
+  if (code) {
+    size_t cs = 0;
+    hiprtcGetCodeSize(prog, &cs);
+    code->resize(cs);
+    hiprtcGetCode(prog, code->data());
+  }
   hiprtcDestroyProgram(&prog);
+  return AH_OK;
+}
+
+int Compile(ah_ctx* c, ah_expr* e) {
+  std::vector<char> code;
+  const int rc = CompileSource(c, e->source, &code);
+  if (rc != AH_OK) return rc;
   AH_HIP(c, hipModuleLoadData(&e->module, code.data()));
   AH_HIP(c, hipModuleGetFunction(&e->fn, e->module, "ah_expr_kernel"));
   return AH_OK;
@@ -374,18 +366,19 @@ AH_EXPORT int ah_expr_execute(ah_ctx* c, ah_expr* e, const void* const* col_valu
   p.out = out_values;
   p.out_valid = out_valid;
   p.flag = (unsigned*)&c->dscalars[10];
-  if (e->has_checked) AH_HIP(c, hipMemsetAsync(p.flag, 0, sizeof(unsigned), c->stream));
+  if (e->has_checked) {
+    const int rc = ah_flag_clear(c, p.flag);
+    if (rc != AH_OK) return rc;
+  }
   int64_t nchunks = (len + 63) / 64;
   int64_t blocks = ah_ceil_div(nchunks, 4 * 4);  // 4 waves per block, 4 chunks per wave
   if (blocks > ((int64_t)1 << 30)) blocks = (int64_t)1 << 30;
   void* args[] = {&p};
   AH_HIP(c, hipModuleLaunchKernel(e->fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
-  if (e->has_checked) {
-    AH_HIP(c, hipMemcpyAsync(c->pinned, p.flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    AH_HIP(c, hipStreamSynchronize(c->stream));
-    if (*(volatile unsigned*)c->pinned & 1u) return ah_fail(c, AH_EOVERFLOW, "overflow");
-  }
-  return AH_OK;
+  if (!e->has_checked) return AH_OK;
+  unsigned bits = 0;
+  const int rc = ah_flag_read(c, p.flag, &bits);
+  return rc == AH_OK ? ah_error_of_flag(c, bits) : rc;
 }
 
 AH_EXPORT int ah_expr_codegen(const ah_expr_node* nodes, int n_nodes, const int* col_types, int n_cols, const int* lit_types,
@@ -396,19 +389,7 @@ AH_EXPORT int ah_expr_codegen(const ah_expr_node* nodes, int n_nodes, const int*
   ah_expr e;
   int rc = (nodes && n_nodes > 0) ? Generate(&tmp, nodes, n_nodes, col_types, n_cols, lit_types, n_lits, &e)
                                   : ah_fail(&tmp, AH_EINVALID, "expr: empty program");
-  if (rc == AH_OK && do_compile) {
-    hiprtcProgram prog;
-    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
-    if (hiprtcCreateProgram(&prog, e.source.c_str(), "ah_expr.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS ||
-        hiprtcCompileProgram(prog, 4, opts) != HIPRTC_SUCCESS) {
-      size_t ls = 0;
-      hiprtcGetProgramLogSize(prog, &ls);
-      std::string log(ls, ' ');
-      if (ls) hiprtcGetProgramLog(prog, &log[0]);
-      rc = ah_fail(&tmp, AH_EHIP, "expr: hiprtc compile failed: %.400s", log.c_str());
-    }
-    hiprtcDestroyProgram(&prog);
-  }
+  if (rc == AH_OK && do_compile) rc = CompileSource(&tmp, e.source, nullptr);
   if (src_buf && src_cap) snprintf(src_buf, src_cap, "%s", e.source.c_str());
   if (err_buf && err_cap) snprintf(err_buf, err_cap, "%s", tmp.err);
   if (out_type_host) *out_type_host = e.out_type;

@@ -61,8 +61,6 @@ __device__ __forceinline__ LaneIndex lane_index(const IdxT* __restrict__ idx, co
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-template <typename T> struct TypeTag { using type = T; };
-
 // idx_byte_width × idx_signed → f(TypeTag<IdxT>{}); false (and no call) for a width no index type has — what that means is the call
 // site's decision ("invalid indices byte width", vector_selection.go:1157, or "this path is not used")
 template <class F>

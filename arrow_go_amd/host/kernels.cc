@@ -78,22 +78,38 @@ static Status ExecArithUnchecked(KernelCtx* k, const ExecSpan& b, ExecResult* ou
   }
 }
 
+// The operands of a binary (or, with one value, unary) call as the validity-aware leaves take them: values pointer, validity
+// bitmap and offset of an array; value pointer and validity of a scalar.
+struct BinaryOperands {
+  const void* p[2] = {nullptr, nullptr};
+  const uint8_t* valid[2] = {nullptr, nullptr};
+  int64_t off[2] = {0, 0};
+  int scalar_valid = 1, shape = AH_SHAPE_AS;
+  // skip_clean_bitmaps: no bitmap for an array that cannot have nulls
+  BinaryOperands(const ExecSpan& b, bool skip_clean_bitmaps) {
+    if (b.values.size() == 2) shape = ShapeOf(b);
+    for (size_t i = 0; i < b.values.size() && i < 2; i++) {
+      const auto& v = b.values[i];
+      if (v.IsArray()) {
+        p[i] = Values(v.array);
+        valid[i] = skip_clean_bitmaps && !v.array.MayHaveNulls() ? nullptr : v.array.buffers[0].buf;
+        off[i] = v.array.offset;
+      } else {
+        p[i] = v.scalar->value;
+        scalar_valid = v.scalar->valid;
+      }
+    }
+  }
+};
+
 // ScalarBinaryNotNull (helpers.go:284-380) for the checked integer ops
 static Status ExecArithChecked(KernelCtx* k, const ExecSpan& b, ExecResult* out, int op) {
   Session* s = k->session;
-  int type = (int)out->type->id;
   if (IsFloating(out->type->id)) return ExecArithUnchecked(k, b, out, op);  // base_arithmetic_amd64.go:109-117
   if (out->len == 0) return Status::OK();
-  int shape = ShapeOf(b);
-  const void *l, *r;
-  const uint8_t *lv = nullptr, *rv = nullptr;
-  int64_t lo = 0, ro = 0;
-  int scalar_valid = 1;
-  if (b.values[0].IsArray()) { l = Values(b.values[0].array); lv = b.values[0].array.buffers[0].buf; lo = b.values[0].array.offset; }
-  else { l = b.values[0].scalar->value; scalar_valid = b.values[0].scalar->valid; }
-  if (b.values[1].IsArray()) { r = Values(b.values[1].array); rv = b.values[1].array.buffers[0].buf; ro = b.values[1].array.offset; }
-  else { r = b.values[1].scalar->value; scalar_valid = b.values[1].scalar->valid; }
-  return s->FromStatus(ah_arithmetic_checked(s->ctx(), type, (int8_t)op, shape, l, lv, lo, r, rv, ro, scalar_valid, Values(out), out->len));
+  const BinaryOperands o(b, /*skip_clean_bitmaps=*/false);
+  return s->FromStatus(ah_arithmetic_checked(s->ctx(), (int)out->type->id, (int8_t)op, o.shape, o.p[0], o.valid[0], o.off[0], o.p[1], o.valid[1], o.off[1], o.scalar_valid,
+                                             Values(out), out->len));
 }
 
 // Go's math.Pow10 (src/math/pow10.go): a product of two table entries — pow10tab[n % 32] · pow10postab32[n / 32] — which
@@ -113,19 +129,9 @@ static double GoPow10(int64_t n) {
 static Status ExecArithExt(KernelCtx* k, const ExecSpan& b, ExecResult* out, int op) {
   Session* s = k->session;
   if (out->len == 0) return Status::OK();
-  const int type = (int)out->type->id;
-  const void *l = nullptr, *r = nullptr;
-  const uint8_t *lv = nullptr, *rv = nullptr;
-  int64_t lo = 0, ro = 0;
-  int scalar_valid = 1, shape = AH_SHAPE_AS;
-  if (b.values.size() == 2) shape = ShapeOf(b);
-  if (b.values[0].IsArray()) { l = Values(b.values[0].array); lv = b.values[0].array.MayHaveNulls() ? b.values[0].array.buffers[0].buf : nullptr; lo = b.values[0].array.offset; }
-  else { l = b.values[0].scalar->value; scalar_valid = b.values[0].scalar->valid; }
-  if (b.values.size() == 2) {
-    if (b.values[1].IsArray()) { r = Values(b.values[1].array); rv = b.values[1].array.MayHaveNulls() ? b.values[1].array.buffers[0].buf : nullptr; ro = b.values[1].array.offset; }
-    else { r = b.values[1].scalar->value; scalar_valid = b.values[1].scalar->valid; }
-  }
-  return s->FromStatus(ah_arithmetic_ext(s->ctx(), type, op, shape, l, lv, lo, r, rv, ro, scalar_valid, Values(out), out->len));
+  const BinaryOperands o(b, /*skip_clean_bitmaps=*/true);
+  return s->FromStatus(ah_arithmetic_ext(s->ctx(), (int)out->type->id, op, o.shape, o.p[0], o.valid[0], o.off[0], o.p[1], o.valid[1], o.off[1], o.scalar_valid, Values(out),
+                                         out->len));
 }
 
 static std::shared_ptr<ScalarFunction> MakeArithExt(const std::string& name, int op, int nargs, std::initializer_list<Type> types) {

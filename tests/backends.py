@@ -36,7 +36,7 @@ class OracleBackend:
     def arithmetic_unary(self, op, a, misalign=0):
         return self.o.arithmetic_unary(op, a)
 
-    def arithmetic_checked(self, op, shape, l, lvalid, loff, r, rvalid, roff, scalar_valid=True):
+    def arithmetic_checked(self, op, shape, l, lvalid, loff, r, rvalid, roff, scalar_valid=True, misalign=0):
         return self.o.arithmetic_checked(op, shape, l, lvalid, loff, r, rvalid, roff, scalar_valid)
 
     def arithmetic_ext(self, op, shape, l, lvalid, loff, r, rvalid, roff, scalar_valid=True):
@@ -198,23 +198,24 @@ class HipBackend:
         self.c.arithmetic_unary(OL.TYPE_IDS[a.dtype], op, ip, ob.ptr + misalign * a.dtype.itemsize, a.size)
         return ob.download(a.dtype, a.size, misalign * a.dtype.itemsize)
 
-    def arithmetic_checked(self, op, shape, l, lvalid, loff, r, rvalid, roff, scalar_valid=True):
+    def arithmetic_checked(self, op, shape, l, lvalid, loff, r, rvalid, roff, scalar_valid=True, misalign=0):
         import arrow_go_amd as ah
         l = np.ascontiguousarray(l); r = np.ascontiguousarray(r)
         arr = r if shape == 2 else l
-        lb, lp = (None, l) if shape == 2 else self._up(l)
-        rb, rp = (None, r) if shape == 1 else self._up(r)
+        lead = misalign * arr.dtype.itemsize
+        lb, lp = (None, l) if shape == 2 else self._up(l, misalign)
+        rb, rp = (None, r) if shape == 1 else self._up(r, misalign)
         lvb, lvp = self._upbits(lvalid)
         rvb, rvp = self._upbits(rvalid)
-        ob = self._dirty(arr.nbytes + 64)
+        ob = self._dirty(lead + arr.nbytes + 64)
         ob.memset(0xCD)
         try:
-            self.c.arithmetic_checked(OL.TYPE_IDS[arr.dtype], op, shape, lp, lvp, loff, rp, rvp, roff, scalar_valid, ob, arr.size)
+            self.c.arithmetic_checked(OL.TYPE_IDS[arr.dtype], op, shape, lp, lvp, loff, rp, rvp, roff, scalar_valid, ob.ptr + lead, arr.size)
             st = STATUS_OK
         except ah.ErrOverflow as e:
             assert "overflow" in str(e)
             st = STATUS_EOVERFLOW
-        return st, ob.download(arr.dtype, arr.size)
+        return st, ob.download(arr.dtype, arr.size, lead)
 
     def round(self, values, valid, off, ndigits, mode, multiple=None):
         import arrow_go_amd as ah

@@ -30,6 +30,18 @@ def test_codegen_compiles_offline():
     # float contraction must stay off: a*b+c rounds twice like two kernels
     src, _ = ah.expr_codegen([(N.X_FIELD, 0), (N.X_FIELD, 1), (N.X_MUL, 0), (N.X_FIELD, 2), (N.X_ADD, 0)], [N.FLOAT64] * 3, [])
     assert "v2 = v0 * v1" in src
+    # every opcode that calls into ah_elementwise.h, over every numeric type: one chain per type — each arithmetic, checked and unary
+    # opcode once, a comparison at the end — and one boolean program; what the ops compute reaches hiprtc as that header, not as text
+    binary = [N.X_ADD, N.X_SUB, N.X_MUL, N.X_ADD_CHECKED, N.X_SUB_CHECKED, N.X_MUL_CHECKED]
+    chain = [(N.X_FIELD, 0)] + [n for op in binary for n in ((N.X_FIELD, 1), (op, 0))] + [(op, 0) for op in (N.X_NEGATE, N.X_ABS, N.X_SIGN)]
+    for t in (N.UINT8, N.INT8, N.UINT16, N.INT16, N.UINT32, N.INT32, N.UINT64, N.INT64, N.FLOAT32, N.FLOAT64):
+        src, out_type = ah.expr_codegen(chain + [(N.X_LITERAL, 0), (N.X_GE, 0)], [t] * 2, [t])
+        assert out_type == N.BOOL and '#include "ah_elementwise.h"' in src and "chk<" not in src
+        assert ("apply<" in src) == (t not in (N.FLOAT32, N.FLOAT64)) and "apply_unary<" in src
+    prog = [(N.X_FIELD, 0), (N.X_FIELD, 1), (N.X_AND, 0), (N.X_FIELD, 2), (N.X_OR, 0), (N.X_FIELD, 0), (N.X_XOR, 0), (N.X_FIELD, 1), (N.X_AND_NOT, 0),
+            (N.X_INVERT, 0)]
+    src, out_type = ah.expr_codegen(prog, [N.BOOL] * 3, [])
+    assert out_type == N.BOOL
 
 
 def test_codegen_cast_nodes():
@@ -86,6 +98,8 @@ EXPRS = [
     ("xor(equal($0,$1),invert(not_equal($2,#0)))", 3, [1]),
     ("add(abs_unchecked($0),sign($1))", 2, []),
     ("or(and_not(greater_equal($0,$1),less($1,$2)),equal($2,#0))", 3, [2]),
+    # the checked ops under nulls: operands 0..5 and a literal 0, so (a + b) · (c − 0) ≤ 50 overflows in none of the types
+    ("multiply(add($0,$1),subtract($2,#0))", 3, [0]),
 ]
 
 

@@ -160,6 +160,46 @@ def test_checked_bit_exact(hip, orc_be, dtype):
             assert st_h == st_o, (dtype, op, n)
 
 
+@pytest.mark.parametrize("dtype", OL.INT_DTYPES, ids=str)
+def test_checked_all_shapes_bit_exact(hip, orc_be, dtype):
+    """The three checked ops through the one validity-aware kernel, in every shape.  Lengths (V = 16 / width elements per vector): an empty
+    call, a tail-only call, one vector short of / exactly / just past one vector, one full workgroup plus a ragged tail, a second
+    workgroup; value pointers 16-byte aligned and one element off; validity at bit offsets 5 and 9, 80 % valid; a valid and a null scalar."""
+    rng = np.random.default_rng(10)
+    V = 16 // np.dtype(dtype).itemsize
+    for n in [0, 1, V - 1, V, V + 1, 256 * V + V - 1, 512 * V + 1]:
+        lv, rv = rand_bits(rng, n + 5, 0.8), rand_bits(rng, n + 9, 0.8)
+        for small in (True, False):
+            if small:  # nothing overflows (l > r: unsigned SUB in range, l * r <= 50: int8 MUL in range) → output bytes, zeros under nulls
+                l, r = rng.integers(6, 11, n).astype(dtype), rng.integers(0, 6, n).astype(dtype)
+                ls, rs = np.array([8], dtype), np.array([3], dtype)
+            else:      # full range: the error decision must be the reference's carry test
+                l, r, ls, rs = rand(rng, dtype, n), rand(rng, dtype, n), rand(rng, dtype, 1), rand(rng, dtype, 1)
+            cases = [(AA, (l, lv, 5, r, rv, 9), True)]
+            cases += [(AS, (l, lv, 5, rs, None, 0), sv) for sv in (True, False)] + [(SA, (ls, None, 0, r, rv, 9), sv) for sv in (True, False)]
+            for op in (21, 22, 23):
+                for shape, args, sv in cases:
+                    st_o, out_o = orc_be.arithmetic_checked(op, shape, *args, scalar_valid=sv)
+                    for mis in (0, 1):
+                        st_h, out_h = hip.arithmetic_checked(op, shape, *args, scalar_valid=sv, misalign=mis)
+                        assert st_h == st_o, (dtype, op, shape, n, sv, mis, small)
+                        if small:
+                            assert st_o == STATUS_OK and out_h.tobytes() == out_o.tobytes(), (dtype, op, shape, n, sv, mis)
+    # Mul tests EVERY slot (ScalarBinary): the only overflowing product under a null — in a vector's body, then in the tail
+    n = 4 * V + 1
+    info = np.iinfo(dtype)
+    for k in (1, n - 1):
+        l, r = rng.integers(6, 11, n).astype(dtype), rng.integers(0, 6, n).astype(dtype)
+        l[k], r[k] = info.max, 2
+        valid = np.ones(n + 5, bool)
+        valid[5 + k] = False
+        lv = OL.pack_bits(valid)
+        for op, want in ((23, STATUS_EOVERFLOW), (21, STATUS_OK)):   # … which Add, a NotNull op, does not see
+            st_o, _ = orc_be.arithmetic_checked(op, AA, l, lv, 5, r, None, 0)
+            st_h, _ = hip.arithmetic_checked(op, AA, l, lv, 5, r, None, 0)
+            assert st_o == want and st_h == st_o, (dtype, op, k)
+
+
 # ---- compare ------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", OL.ALL_DTYPES, ids=str)
 def test_compare_bit_exact(hip, orc_be, dtype):

@@ -70,6 +70,8 @@ RESOURCES = {
         (r"enc_table_kernelILi8192ELb1E", 128, 0),
     ],
     "ah_take.hip": [(r"take_vec_kernelILi8EiLb[01]ELi7E", 64, 0)],
+    # checked Int64 add, array ∘ array, through the one validity-aware kernel (X_ADD_CHECKED = 9): what checked_kernel<long, OP_ADD, 0> had
+    "ah_arith_ext.hip": [(r"ext_kernelIlLi9ELi0E", 30, 0)],
     # the binned Take's hot kernels at the figures they had before the index rule moved into ah_index.h: the scatter
     # (53 VGPRs; 45 for uint32 indices), the LDS-bitmap gather of 8-byte values (58) and their un-permute (42), none with scratch
     "ah_take_binned.hip": [(r"bin_scatter_kernelI", 53, 0), (r"bin_gather_lds_kernelILi8E", 58, 0), (r"unpermute_kernelILi8ELb1E", 42, 0)],
