@@ -143,6 +143,12 @@ _SIGS = {
     "ah_cast_decimal_rescale": [_vp, _int, _int, _int, _int, _int, _vp, _vp, _i64, _i64, _vp],
     "ah_cast_int_to_decimal": [_vp, _int, _int, _int, _vp, _vp, _i64, _i64, _vp],
     "ah_cast_decimal_to_int": [_vp, _int, _int, _int, _int, _int, _vp, _vp, _i64, _i64, _vp],
+    "ah_parse_int": [_vp, _int, _vp, _vp, _vp, _i64, _i64, _int, _vp, _pi64, _pint],
+    "ah_parse_bool": [_vp, _int, _vp, _vp, _vp, _i64, _i64, _vp, _pi64],
+    "ah_format_int_offsets": [_vp, _int, _vp, _vp, _i64, _i64, _int, _vp, _pi64],
+    "ah_format_int_data": [_vp, _int, _vp, _vp, _i64, _i64, _int, _vp, _vp],
+    "ah_validate_utf8": [_vp, _int, _vp, _vp, _int, _vp, _i64, _i64, _pi64],
+    "ah_fixed_binary_offsets": [_vp, _int, _int, _i64, _i64, _vp],
     "ah_shift_time": [_vp, _int, _int, _int, _i64, _int, _vp, _vp, _i64, _i64, _vp, _vp],
     "ah_cast_bool_to_numeric": [_vp, _int, _vp, _i64, _i64, _vp],
     "ah_is_in": [_vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _int, _vp, _vp, _i64],

@@ -134,4 +134,17 @@ __device__ __forceinline__ void wave_compare(unsigned long long need, const uint
   }
 }
 
+// The offsets buffer of a var-length output from the inclusive scan of its rows' lengths (the Take of ah_varlen.hip, the formatted
+// casts of ah_cast_string.hip): out_offsets[0] = 0, out_offsets[i + 1] = incl[i]; int32 offsets: flag an overflow
+template <typename OffT, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void offsets_kernel(const long long* __restrict__ incl, int64_t n, OffT* __restrict__ out_offsets,
+                                                         unsigned* __restrict__ overflow) {
+  const int64_t stride = (int64_t)gridDim.x * BLOCK;
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i <= n; i += stride) {
+    const long long v = i == 0 ? 0 : incl[i - 1];
+    if (sizeof(OffT) == 4 && v > 2147483647ll) atomicOr(overflow, 1u);
+    out_offsets[i] = (OffT)v;
+  }
+}
+
 }  // namespace

@@ -21,6 +21,7 @@
 // the reference filters record batches (compute/selection.go:687).
 // Traffic: 2·w_off + w_idx read and w_off (+1/8) written per row in the first call (+ the scan's
 // 24 B/row), the value bytes once in and once out in the second.
+#include "ah_bytes.h"
 #include "ah_index.h"
 
 namespace {
@@ -42,18 +43,6 @@ __global__ __launch_bounds__(kBlock) void lens_kernel(const OffT* __restrict__ o
       if (ah_lane() == 0) put_chunk_bytes(out_valid, c, n, word);
     }
   });
-}
-
-// out_offsets[0] = 0, out_offsets[i + 1] = incl[i]; int32 offsets: flag an overflow
-template <typename OffT>
-__global__ __launch_bounds__(kBlock) void offsets_kernel(const long long* __restrict__ incl, int64_t n, OffT* __restrict__ out_offsets,
-                                                          unsigned* __restrict__ overflow) {
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= n; i += stride) {
-    const long long v = i == 0 ? 0 : incl[i - 1];
-    if (sizeof(OffT) == 4 && v > 2147483647ll) atomicOr(overflow, 1u);
-    out_offsets[i] = (OffT)v;
-  }
 }
 
 struct __attribute__((packed)) U32u { unsigned v; };  // 4 bytes at any address (gfx950 global memory runs in unaligned-access mode)
@@ -108,8 +97,8 @@ int run_offsets(ah_ctx* c, const void* offsets, const uint8_t* vvalid, int64_t v
   AH_LAUNCH_CHECK(c);
   int rc = ah_cumulative_sum(c, AH_INT64, lens, nullptr, 0, n, nullptr, 0, 0, incl, nullptr, nullptr);
   if (rc != AH_OK) return rc;
-  offsets_kernel<OffT><<<ah_stream_grid(c, ah_ceil_div(n + 1, kBlock), 8), kBlock, 0, c->stream>>>(incl, n, (OffT*)out_offsets,
-                                                                                                  (unsigned*)&c->dscalars[3]);
+  offsets_kernel<OffT, kBlock><<<ah_stream_grid(c, ah_ceil_div(n + 1, kBlock), 8), kBlock, 0, c->stream>>>(incl, n, (OffT*)out_offsets,
+                                                                                                          (unsigned*)&c->dscalars[3]);
   AH_LAUNCH_CHECK(c);
   return AH_OK;
 }

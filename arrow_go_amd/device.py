@@ -529,6 +529,51 @@ class Context:
             e.bad_value = bad.value
             raise
 
+    # ---- string casts (ah_cast_string.hip) -------------------------------------------------
+    def parse_int(self, offset_width: int, offsets, data, valid, off: int, n: int, out_type: int, out_values) -> None:
+        """strconv.ParseInt / ParseUint(s, 0, bits) per valid row (numeric_cast.go:742-781).  The LAST offending valid row raises
+        ErrInvalid carrying .bad_row (relative to off) and .bad_kind (1 syntax, 2 range)"""
+        bad, kind = C.c_int64(-1), C.c_int(0)
+        try:
+            check(self.handle, lib.ah_parse_int(self.handle, offset_width, _ptr(offsets), _ptr(data), _ptr(valid), off, n, out_type, _ptr(out_values),
+                                                C.byref(bad), C.byref(kind)))
+        except N.ErrInvalid as e:
+            e.bad_row, e.bad_kind = bad.value, kind.value
+            raise
+
+    def parse_bool(self, offset_width: int, offsets, data, valid, off: int, n: int, out_bits) -> None:
+        """strconv.ParseBool per valid row into a bitmap from bit 0 (boolean_cast.go:77-95); errors as parse_int"""
+        bad = C.c_int64(-1)
+        try:
+            check(self.handle, lib.ah_parse_bool(self.handle, offset_width, _ptr(offsets), _ptr(data), _ptr(valid), off, n, _ptr(out_bits), C.byref(bad)))
+        except N.ErrInvalid as e:
+            e.bad_row, e.bad_kind = bad.value, 1
+            raise
+
+    def format_int_offsets(self, in_type: int, values, valid, off: int, n: int, offset_width: int, out_offsets) -> int:
+        """offsets of the integer / boolean (in_type 1: `values` is the data bitmap) → string cast; returns the byte total"""
+        total = C.c_int64(0)
+        check(self.handle, lib.ah_format_int_offsets(self.handle, in_type, _ptr(values), _ptr(valid), off, n, offset_width, _ptr(out_offsets), C.byref(total)))
+        return total.value
+
+    def format_int_data(self, in_type: int, values, valid, off: int, n: int, offset_width: int, out_offsets, out_data) -> None:
+        """the characters of strconv.FormatInt / FormatUint / FormatBool, given format_int_offsets' offsets of the same column"""
+        check(self.handle, lib.ah_format_int_data(self.handle, in_type, _ptr(values), _ptr(valid), off, n, offset_width, _ptr(out_offsets), _ptr(out_data)))
+
+    def validate_utf8(self, offset_width: int, offsets, data, byte_width: int, valid, off: int, n: int) -> None:
+        """utf8.Valid of every valid row (string_casts.go:39-87); offset_width 0: fixed-size rows.  The FIRST offending valid row raises
+        ErrInvalid carrying .bad_row"""
+        bad = C.c_int64(-1)
+        try:
+            check(self.handle, lib.ah_validate_utf8(self.handle, offset_width, _ptr(offsets), _ptr(data), byte_width, _ptr(valid), off, n, C.byref(bad)))
+        except N.ErrInvalid as e:
+            e.bad_row = bad.value
+            raise
+
+    def fixed_binary_offsets(self, offset_width: int, byte_width: int, off: int, n: int, out_offsets) -> None:
+        """CastFsbToBinary's offsets (string_casts.go:154-193): (off + i) · byte_width, i = 0 … n"""
+        check(self.handle, lib.ah_fixed_binary_offsets(self.handle, offset_width, byte_width, off, n, _ptr(out_offsets)))
+
     def cast_bool_to_numeric(self, out_type: int, bits, off: int, n: int, out_values) -> None:
         check(self.handle, lib.ah_cast_bool_to_numeric(self.handle, out_type, _ptr(bits), off, n, _ptr(out_values)))
 

@@ -310,8 +310,8 @@ AHC_EXPORT int ahc_datum_info(ahc_datum* d, int* kind, int* type_id, int64_t* le
 
 // options: "key=value;key=value"; keys follow the Go struct tags
 //   null_selection_behavior=drop|emit_null   bounds_check=0|1   null_encoding_behavior=mask|encode
-//   to_type=<type>|d:<precision>,<scale>[,256]   safe=0|1   allow_int_overflow=0|1   allow_float_truncate=0|1
-//   allow_decimal_truncate=0|1                                                                    (CastOptions)
+//   to_type=<type>|d:<precision>,<scale>[,256]|string|large_string|binary|large_binary|w:<bytes>
+//   safe=0|1   allow_int_overflow=0|1   allow_float_truncate=0|1   allow_decimal_truncate=0|1   allow_invalid_utf8=0|1   (CastOptions)
 //   value_set=@<ahc_datum* in hex>   null_matching_behavior=match|skip|emit_null|inconclusive      (SetOptions)
 //   order=ascending|descending   null_placement=at_end|at_start                                   (SortOptions, one key)
 //   sort_keys=<col>:<asc|desc>:<at_end|at_start>,…                                                (SortOptions, several keys)
@@ -374,7 +374,11 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
       if (k == "to_type") {
         p->cast.ToType = v == "bool" ? GetDataType(Type::BOOL) : nullptr;
         for (auto& tn : kTypeNames) if (v == tn.name) p->cast.ToType = GetDataType(tn.id);
-        if (v.size() > 2 && v[0] == 'd' && v[1] == ':') p->cast.ToType = FixedWidthBinaryFromFormat(v);   // "d:22,2" / "d:22,2,256"
+        if (v.size() > 2 && (v[0] == 'd' || v[0] == 'w') && v[1] == ':') p->cast.ToType = FixedWidthBinaryFromFormat(v);   // "d:22,2" / "d:22,2,256" / "w:16"
+        if (v == "string") p->cast.ToType = GetDataType(Type::STRING);
+        if (v == "large_string") p->cast.ToType = GetDataType(Type::LARGE_STRING);
+        if (v == "binary") p->cast.ToType = GetDataType(Type::BINARY);
+        if (v == "large_binary") p->cast.ToType = GetDataType(Type::LARGE_BINARY);
         p->pick = &p->cast;
       }
       if (k == "to_logical") { p->cast.ToLogical = v; p->pick = &p->cast; }
@@ -382,6 +386,7 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
       if (k == "allow_int_overflow") { p->cast.AllowIntOverflow = v != "0"; p->pick = &p->cast; }
       if (k == "allow_time_truncate") { p->cast.AllowTimeTruncate = v != "0"; p->pick = &p->cast; }
       if (k == "allow_time_overflow") { p->cast.AllowTimeOverflow = v != "0"; p->pick = &p->cast; }
+      if (k == "allow_invalid_utf8") { p->cast.AllowInvalidUtf8 = v != "0"; p->pick = &p->cast; }
       if (k == "allow_decimal_truncate") { p->cast.AllowDecimalTruncate = v != "0"; p->pick = &p->cast; }
       if (k == "allow_float_truncate") { p->cast.AllowFloatTruncate = v != "0"; p->pick = &p->cast; }
       if (k == "value_set" && v.size() > 1 && v[0] == '@') {

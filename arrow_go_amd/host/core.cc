@@ -1453,6 +1453,8 @@ Status CallTemporal(ExecCtx* ctx, const std::string& name, const FunctionOptions
         return CastTemporalUnits(ctx, args[0], lg[0], co->ToLogical, *co, out);
       }
       if (co->ToType && storage && co->ToType->id == storage->id) { *out = bare[0]; return Status::OK(); }
+      if (co->ToType && (IsBaseBinary(co->ToType->id) || co->ToType->id == Type::FIXED_SIZE_BINARY))   // temporal → string: not built
+        return Status::Make(StatusCode::NotImplemented, std::string("unsupported cast to ") + co->ToType->name + " from " + lg[0]);
       return Status::Make(StatusCode::NotImplemented, std::string("cast from ") + lg[0] + " to " + (co->ToType ? co->ToType->name : "?") + " is not built");
     }
   }

@@ -1113,7 +1113,7 @@ void RegisterVectorHash(FunctionRegistry* reg) {
   reg->AddFunction(de, false);
 }
 
-// ---- cast (numeric ↔ numeric, bool ↔ numeric, decimal ↔ decimal, integer ↔ decimal) -----------------
+// ---- cast (numeric ↔ numeric, bool ↔ numeric, decimal ↔ decimal, integer ↔ decimal, string ↔ integer / boolean / binary) ----
 // CastIntToInt / CastFloatingToInteger / CastIntegerToFloating / CastFloatingToFloating
 // (kernels/numeric_cast.go:37-71): conversion and safe-cast check in one pass on the device
 static Status ExecCastNumeric(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
@@ -1195,10 +1195,215 @@ static Status ExecCastDecimalToInteger(KernelCtx* k, const ExecSpan& b, ExecResu
                                               in.len, Values(out)));
 }
 
+// ---- string casts (kernels/string_casts.go, numeric_cast.go:742-781, boolean_cast.go:77-95) --------------------------------
+// DataType.String() as the reference's messages print it
+static std::string CastTypeText(const DataType* t) {
+  if (t->id == Type::FIXED_SIZE_BINARY) return "fixed_size_binary[" + std::to_string(t->bit_width / 8) + "]";
+  return t->name;
+}
+static bool IsStringType(Type id) { return id == Type::STRING || id == Type::LARGE_STRING; }
+
+// the bytes of row `row` of a byte-string or fixed-size binary column, on the host (the one row an error message quotes)
+static Status DownloadRow(Session* s, const ArraySpan& in, int64_t row, std::string* bytes) {
+  bytes->clear();
+  int64_t begin = 0, len = 0;
+  const uint8_t* data = nullptr;
+  if (IsBaseBinary(in.type->id)) {
+    const int ow = in.type->bit_width / 8;
+    alignas(8) uint8_t raw[16] = {0};
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_download_async(s->ctx(), raw, in.buffers[1].buf + (in.offset + row) * ow, (size_t)(2 * ow))));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_sync(s->ctx())));
+    if (ow == 4) { int32_t o[2]; memcpy(o, raw, 8); begin = o[0]; len = (int64_t)o[1] - o[0]; }
+    else { int64_t o[2]; memcpy(o, raw, 16); begin = o[0]; len = o[1] - o[0]; }
+    data = in.buffers[2].buf;
+  } else {
+    len = in.type->bit_width / 8;
+    begin = (in.offset + row) * len;
+    data = in.buffers[1].buf;
+  }
+  if (len <= 0) return Status::OK();
+  bytes->resize((size_t)len);
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_download_async(s->ctx(), &(*bytes)[0], data + begin, (size_t)len)));
+  return s->FromStatus(ah_sync(s->ctx()));
+}
+
+// strconv.Quote for the bytes of a NumError: \" \\ \n \t \r, \xNN for every other byte outside printable ASCII
+static std::string GoQuote(const std::string& b) {
+  std::string q = "\"";
+  char hex[8];
+  for (unsigned char c : b) {
+    if (c == '"' || c == '\\') { q += '\\'; q += (char)c; }
+    else if (c == '\n') q += "\\n";
+    else if (c == '\t') q += "\\t";
+    else if (c == '\r') q += "\\r";
+    else if (c >= 0x20 && c < 0x7F) q += (char)c;
+    else { snprintf(hex, sizeof hex, "\\x%02x", c); q += hex; }
+  }
+  return q + "\"";
+}
+
+// the reference's error of a parse kernel: fmt.Errorf("%w: %s", arrow.ErrInvalid, &strconv.NumError{Func, Num, Err})
+static Status ParseError(Session* s, const ArraySpan& in, const char* func, int64_t row, int kind) {
+  std::string bytes;
+  AHC_RETURN_NOT_OK(DownloadRow(s, in, row, &bytes));
+  return Status::Make(StatusCode::Invalid, std::string("strconv.") + func + ": parsing " + GoQuote(bytes) + ": " +
+                                               (kind == 2 ? "value out of range" : "invalid syntax"));
+}
+
+// getParseStringExec (numeric_cast.go:742-781): String / Binary / LargeString / LargeBinary → the eight integer types
+static Status ExecCastStringToInteger(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  Session* s = k->session;
+  if (out->len == 0) return Status::OK();
+  const ArraySpan& in = b.values[0].array;
+  int64_t bad = -1;
+  int kind = 0;
+  const int rc = ah_parse_int(s->ctx(), in.type->bit_width / 8, in.buffers[1].buf, in.buffers[2].buf, in.MayHaveNulls() ? in.buffers[0].buf : nullptr,
+                              in.offset, in.len, (int)out->type->id, Values(out), &bad, &kind);
+  if (rc == AH_EINVALID && bad >= 0) return ParseError(s, in, IsSignedInteger(out->type->id) ? "ParseInt" : "ParseUint", bad, kind);
+  return s->FromStatus(rc);
+}
+
+// strconv.ParseBool under ScalarUnaryNotNullBinaryArgBoolOut (boolean_cast.go:77-95)
+static Status ExecCastStringToBool(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  Session* s = k->session;
+  if (out->len == 0) return Status::OK();
+  const ArraySpan& in = b.values[0].array;
+  int64_t bad = -1;
+  const int rc = ah_parse_bool(s->ctx(), in.type->bit_width / 8, in.buffers[1].buf, in.buffers[2].buf, in.MayHaveNulls() ? in.buffers[0].buf : nullptr,
+                               in.offset, in.len, out->buffers[1].buf, &bad);
+  if (rc == AH_EINVALID && bad >= 0) return ParseError(s, in, "ParseBool", bad, 1);
+  return s->FromStatus(rc);
+}
+
+// maxFormattedBytes (string_casts.go:429-442)
+static int MaxFormattedBytes(Type id) {
+  switch (id) {
+    case Type::INT8: case Type::UINT8: return 4;
+    case Type::INT16: return 6;
+    case Type::UINT16: return 5;
+    case Type::INT32: return 11;
+    case Type::UINT32: return 10;
+    case Type::INT64: case Type::UINT64: return 20;
+    default: return 0;
+  }
+}
+static Status PayloadTooLarge(int64_t total) {
+  return Status::Make(StatusCode::Invalid, "formatted cast payload (" + std::to_string(total) + " bytes) exceeds single data buffer limit (" +
+                                               std::to_string((int64_t)INT32_MAX) + " bytes) for destination builder");
+}
+
+// integer / boolean → String / LargeString (string_casts.go:444-579): the validity is the executor's (NullIntersection); offsets,
+// the byte total, the allocation, the characters
+static Status ExecCastIntegerToString(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  Session* s = k->session;
+  ArraySpan in = b.values[0].array;
+  const int ow = out->type->bit_width / 8;
+  const bool is_bool = in.type->id == Type::BOOL;
+  if (!is_bool && ow == 4) {  // reserveFormattedData: the reference refuses by its UPPER bound, before it formats a row
+    AHC_RETURN_NOT_OK(in.UpdateNullCount(s));
+    const int64_t reserve = (in.len - in.nulls) * (int64_t)MaxFormattedBytes(in.type->id);
+    if (reserve > (int64_t)INT32_MAX) return PayloadTooLarge(reserve);
+  }
+  BufferPtr ob, db;
+  AHC_RETURN_NOT_OK(k->Allocate((out->len + 1) * ow, &ob, /*zero_all=*/false));
+  out->buffers[1].WrapBuffer(ob);
+  const uint8_t* values = is_bool ? in.buffers[1].buf : Values(in);
+  const uint8_t* valid = in.MayHaveNulls() ? in.buffers[0].buf : nullptr;
+  int64_t total = 0;
+  const int rc = ah_format_int_offsets(s->ctx(), (int)in.type->id, values, valid, in.offset, in.len, ow, ob->dptr, &total);
+  if (rc == AH_EINVALID && total > (int64_t)INT32_MAX) return PayloadTooLarge(total);   // boolean input: the exact count
+  AHC_RETURN_NOT_OK(s->FromStatus(rc));
+  AHC_RETURN_NOT_OK(k->Allocate(total, &db, /*zero_all=*/false));
+  out->buffers[2].WrapBuffer(db);
+  if (in.len == 0 || total == 0) return Status::OK();
+  return s->FromStatus(ah_format_int_data(s->ctx(), (int)in.type->id, values, valid, in.offset, in.len, ow, ob->dptr, (uint8_t*)db->dptr));
+}
+
+// shouldValidateUTF8 + validateUtf8 / validateUtf8Fsb (string_casts.go:39-87)
+static Status ValidateUtf8ForCast(KernelCtx* k, const ArraySpan& in, const DataType* to) {
+  const CastOptions* opts = static_cast<const CastOptions*>(k->state);
+  if ((opts && opts->AllowInvalidUtf8) || !IsStringType(to->id) || IsStringType(in.type->id) || in.len == 0) return Status::OK();
+  Session* s = k->session;
+  const ByteLayout l = LayoutOf(in);
+  int64_t bad = -1;
+  const int rc = ah_validate_utf8(s->ctx(), l.offset_width, l.offsets, l.data, l.byte_width, in.MayHaveNulls() ? in.buffers[0].buf : nullptr, in.offset,
+                                  in.len, &bad);
+  if (rc == AH_EINVALID && bad >= 0) {
+    std::string bytes, hex;
+    AHC_RETURN_NOT_OK(DownloadRow(s, in, bad, &bytes));
+    char h[4];
+    for (unsigned char c : bytes) { snprintf(h, sizeof h, "%02x", c); hex += h; }
+    return Status::Make(StatusCode::Invalid, "invalid UTF8 bytes: " + hex);
+  }
+  return s->FromStatus(rc);
+}
+
+static Status InputTooLarge(const DataType* from, const DataType* to) {
+  return Status::Make(StatusCode::Invalid, "failed casting from " + CastTypeText(from) + " to " + CastTypeText(to) + ": input array too large");
+}
+
+// CastBinaryToBinary (string_casts.go:89-152): the same offset width shares every buffer; another one shares validity's content and
+// the data and widens or narrows the offsets
+static Status ExecCastBinaryToBinary(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  Session* s = k->session;
+  const ArraySpan& in = b.values[0].array;
+  const DataType* to = out->type;
+  AHC_RETURN_NOT_OK(ValidateUtf8ForCast(k, in, to));
+  const int iw = in.type->bit_width / 8, ow = to->bit_width / 8;
+  if (iw == ow) {  // ZeroCopyCastExec
+    *out = in;
+    out->type = to;
+    return Status::OK();
+  }
+  if (ow == 4 && in.len > 0) {  // the last offset must fit
+    int64_t last = 0;
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_download_async(s->ctx(), &last, in.buffers[1].buf + (in.offset + in.len) * 8, 8)));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_sync(s->ctx())));
+    if (last > (int64_t)INT32_MAX) return InputTooLarge(in.type, to);
+  }
+  BufferPtr ob;
+  AHC_RETURN_NOT_OK(k->Allocate((in.len + 1) * ow, &ob, /*zero_all=*/false));
+  out->buffers[1].WrapBuffer(ob);
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_cast_numeric(s->ctx(), iw == 4 ? AH_INT32 : AH_INT64, ow == 4 ? AH_INT32 : AH_INT64, in.buffers[1].buf + in.offset * iw,
+                                                  nullptr, 0, in.len + 1, /*allow_int_overflow=*/1, /*allow_float_truncate=*/1, ob->dptr)));
+  out->buffers[2] = in.buffers[2];
+  return Status::OK();
+}
+
+// CastFsbToBinary (string_casts.go:154-193): the values buffer becomes the data buffer, offsets (offset + i) · width
+static Status ExecCastFsbToBinary(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  Session* s = k->session;
+  const ArraySpan& in = b.values[0].array;
+  const DataType* to = out->type;
+  AHC_RETURN_NOT_OK(ValidateUtf8ForCast(k, in, to));
+  const int ow = to->bit_width / 8;
+  const int64_t width = in.type->bit_width / 8;
+  if (width * in.len > (ow == 4 ? (int64_t)INT32_MAX : INT64_MAX)) return InputTooLarge(in.type, to);
+  if (ow == 4 && width * (in.offset + in.len) > (int64_t)INT32_MAX) return InputTooLarge(in.type, to);   // (the reference's int32 wraps here)
+  BufferPtr ob;
+  AHC_RETURN_NOT_OK(k->Allocate((in.len + 1) * ow, &ob, /*zero_all=*/false));
+  out->buffers[1].WrapBuffer(ob);
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_fixed_binary_offsets(s->ctx(), ow, (int)width, in.offset, in.len, ob->dptr)));
+  out->buffers[2] = in.buffers[1];
+  return Status::OK();
+}
+
+// CastFsbToFsb (string_casts.go:89-99)
+static Status ExecCastFsbToFsb(KernelCtx* k, const ExecSpan& b, ExecResult* out) {
+  const ArraySpan& in = b.values[0].array;
+  const CastOptions* opts = static_cast<const CastOptions*>(k->state);
+  const DataType* to = opts && opts->ToType ? opts->ToType : out->type;
+  if (in.type->bit_width != to->bit_width)
+    return Status::Make(StatusCode::Invalid, "failed casting from " + CastTypeText(in.type) + " to " + CastTypeText(to) + ": widths must match");
+  *out = in;
+  return Status::OK();
+}
+
 // arrow.TypeEqual for the cast meta function's shortcut: decimals by precision and scale (interned: usually the same pointer), every
 // other type by its id
 static bool CastIsIdentity(const DataType* from, const DataType* to) {
   if (from->id != to->id) return false;
+  if (from->id == Type::FIXED_SIZE_BINARY) return from->bit_width == to->bit_width;
   if (!IsDecimal(from->id) || from == to) return true;
   int fp = 0, fs = 0, tp = 0, ts = 0;
   return DecimalParams(from, &fp, &fs) && DecimalParams(to, &tp, &ts) && fp == tp && fs == ts;
@@ -1207,6 +1412,9 @@ static bool CastIsIdentity(const DataType* from, const DataType* to) {
 static const char* CastFunctionName(Type t) {
   switch (t) {
     case Type::DECIMAL128: return "cast_decimal"; case Type::DECIMAL256: return "cast_decimal256";   // cast.go:883-885
+    case Type::STRING: return "cast_string"; case Type::LARGE_STRING: return "cast_large_string";              // cast.go:906-912
+    case Type::BINARY: return "cast_binary"; case Type::LARGE_BINARY: return "cast_large_binary";
+    case Type::FIXED_SIZE_BINARY: return "cast_fixed_sized_binary";
     case Type::BOOL: return "cast_boolean";
     case Type::UINT8: return "cast_uint8"; case Type::INT8: return "cast_int8"; case Type::UINT16: return "cast_uint16";
     case Type::INT16: return "cast_int16"; case Type::UINT32: return "cast_uint32"; case Type::INT32: return "cast_int32";
@@ -1217,7 +1425,7 @@ static const char* CastFunctionName(Type t) {
 }
 
 // RegisterScalarCast (compute/cast.go:83-85) + the per-target cast functions getCastFunction resolves
-// (cast.go:190-260: "cast_int32" …), numeric, boolean and decimal targets
+// (cast.go:190-260: "cast_int32" …), numeric, boolean, decimal and binary-like targets
 void RegisterScalarCast(FunctionRegistry* reg) {
   for (Type to : kNumericTypes) {
     auto fn = std::make_shared<ScalarFunction>(CastFunctionName(to), Arity{1, false});
@@ -1246,6 +1454,16 @@ void RegisterScalarCast(FunctionRegistry* reg) {
         kd.sig.out_type = to;
         kd.exec_fn = ExecCastDecimalToInteger;
         fn->AddParametricKernel(std::move(kd));
+      }
+    // … and the String / Binary / LargeString / LargeBinary kernels (numeric_cast.go:815-833), beside the table in the same way
+    if (IsInteger(to))
+      for (Type from : {Type::BINARY, Type::STRING, Type::LARGE_BINARY, Type::LARGE_STRING}) {
+        exec::ScalarKernel ks;
+        ks.sig.in_types = {from};
+        ks.sig.out_is_first_input = false;
+        ks.sig.out_type = to;
+        ks.exec_fn = ExecCastStringToInteger;
+        fn->AddParametricKernel(std::move(ks));
       }
     reg->AddFunction(fn, false);
   }
@@ -1283,7 +1501,50 @@ void RegisterScalarCast(FunctionRegistry* reg) {
     k.exec_fn = ExecCastNumericToBool;
     fb->AddKernel(std::move(k));
   }
+  for (Type from : {Type::BINARY, Type::STRING, Type::LARGE_BINARY, Type::LARGE_STRING}) {   // boolean_cast.go:77-95
+    exec::ScalarKernel k;
+    k.sig.in_types = {from};
+    k.sig.out_is_first_input = false;
+    k.sig.out_type = Type::BOOL;
+    k.exec_fn = ExecCastStringToBool;
+    fb->AddParametricKernel(std::move(k));
+  }
   reg->AddFunction(fb, false);
+  // cast_binary / cast_large_binary / cast_string / cast_large_string (cast.go:906-911; GetToBinaryKernels string_casts.go:581-607):
+  // the four base-binary inputs and FixedSizeBinary; the string targets also take the integers and Boolean.  The kernels build
+  // their own offsets and data (MemNoPrealloc); validity is the executor's, or the input's where the buffers are shared.
+  for (Type to : {Type::BINARY, Type::LARGE_BINARY, Type::STRING, Type::LARGE_STRING}) {
+    auto fn = std::make_shared<ScalarFunction>(CastFunctionName(to), Arity{1, false});
+    auto add = [&](Type from, exec::ArrayKernelExec ex) {
+      exec::ScalarKernel k;
+      k.sig.in_types = {from};
+      k.sig.out_is_first_input = false;
+      k.sig.out_type = to;
+      k.mem_alloc = exec::MemAlloc::MemNoPrealloc;
+      k.exec_fn = std::move(ex);
+      fn->AddKernel(std::move(k));
+    };
+    for (Type from : {Type::STRING, Type::BINARY, Type::LARGE_STRING, Type::LARGE_BINARY}) add(from, ExecCastBinaryToBinary);
+    add(Type::FIXED_SIZE_BINARY, ExecCastFsbToBinary);
+    if (IsStringType(to)) {
+      for (Type from : kNumericTypes)
+        if (IsInteger(from)) add(from, ExecCastIntegerToString);
+      add(Type::BOOL, ExecCastIntegerToString);
+    }
+    reg->AddFunction(fn, false);
+  }
+  // cast_fixed_sized_binary (the reference's spelling, cast.go:912; GetFsbCastKernels string_casts.go:224-232): CastFsbToFsb only
+  {
+    auto fn = std::make_shared<ScalarFunction>(CastFunctionName(Type::FIXED_SIZE_BINARY), Arity{1, false});
+    exec::ScalarKernel k;
+    k.sig.in_types = {Type::FIXED_SIZE_BINARY};
+    k.sig.out_is_first_input = true;
+    k.null_handling = exec::NullHandling::NullComputedNoPrealloc;
+    k.mem_alloc = exec::MemAlloc::MemNoPrealloc;
+    k.exec_fn = ExecCastFsbToFsb;
+    fn->AddKernel(std::move(k));
+    reg->AddFunction(fn, false);
+  }
   // castMetaFunc (cast.go:45-81)
   reg->AddFunction(std::make_shared<MetaFunction>("cast", Arity{1, false}, nullptr,
       [](ExecCtx* ctx, const FunctionOptions* o, const std::vector<Datum>& args, Datum* out) {

@@ -408,3 +408,47 @@ func (x *Context) CastDecimalToInt(inWidth, inScale int, out arrow.Type, allowTr
 	return x.err(C.ah_cast_decimal_to_int(x.c, C.int(inWidth), C.int(inScale), C.int(out), boolInt(allowTruncate), boolInt(allowOverflow),
 		values, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), dst))
 }
+
+// ParseInt mirrors getParseStringExec under ScalarUnaryNotNullBinaryArg (kernels/numeric_cast.go:742-781): strconv.ParseInt /
+// ParseUint(s, 0, bits) of every valid row of a String / Binary column (offsetWidth 4) or LargeString / LargeBinary column (8) into
+// out's slots, 0 for a null row.  offsets is the offsets buffer, off the array's offset.  On arrow.ErrInvalid badRow is the LAST
+// offending valid row (relative to off), as the reference reports it, and badKind 1 (strconv.ErrSyntax) or 2 (strconv.ErrRange).
+func (x *Context) ParseInt(offsetWidth int, offsets, data, valid unsafe.Pointer, off, n int64, out arrow.Type, dst unsafe.Pointer) (badRow int64, badKind int, err error) {
+	var row C.int64_t
+	var kind C.int
+	err = x.err(C.ah_parse_int(x.c, C.int(offsetWidth), offsets, (*C.uint8_t)(data), (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), C.int(out), dst, &row, &kind))
+	return int64(row), int(kind), err
+}
+
+// ParseBool mirrors the strconv.ParseBool kernels (kernels/boolean_cast.go:77-95): the result bitmap from bit 0.
+func (x *Context) ParseBool(offsetWidth int, offsets, data, valid unsafe.Pointer, off, n int64, dstBits unsafe.Pointer) (badRow int64, err error) {
+	var row C.int64_t
+	err = x.err(C.ah_parse_bool(x.c, C.int(offsetWidth), offsets, (*C.uint8_t)(data), (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), (*C.uint8_t)(dstBits), &row))
+	return int64(row), err
+}
+
+// FormatIntOffsets is the first half of the integer / boolean → String / LargeString cast (kernels/string_casts.go:444-579): the
+// output's offsets (from 0) and the number of bytes the caller allocates for FormatIntData.  in arrow.BOOL: values is the data bitmap.
+func (x *Context) FormatIntOffsets(in arrow.Type, values, valid unsafe.Pointer, off, n int64, offsetWidth int, dstOffsets unsafe.Pointer) (totalBytes int64, err error) {
+	var total C.int64_t
+	err = x.err(C.ah_format_int_offsets(x.c, C.int(in), values, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), C.int(offsetWidth), dstOffsets, &total))
+	return int64(total), err
+}
+
+// FormatIntData writes the characters (strconv.FormatInt / FormatUint in base 10, "true" / "false") under FormatIntOffsets' offsets.
+func (x *Context) FormatIntData(in arrow.Type, values, valid unsafe.Pointer, off, n int64, offsetWidth int, dstOffsets, dstData unsafe.Pointer) error {
+	return x.err(C.ah_format_int_data(x.c, C.int(in), values, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), C.int(offsetWidth), dstOffsets, (*C.uint8_t)(dstData)))
+}
+
+// ValidateUTF8 mirrors validateUTF8Sequence (kernels/string_casts.go:39-87): utf8.Valid of every valid row; offsetWidth 0 is a
+// FixedSizeBinary column of byteWidth bytes whose values buffer is data.  On arrow.ErrInvalid badRow is the FIRST offending valid row.
+func (x *Context) ValidateUTF8(offsetWidth int, offsets, data unsafe.Pointer, byteWidth int, valid unsafe.Pointer, off, n int64) (badRow int64, err error) {
+	var row C.int64_t
+	err = x.err(C.ah_validate_utf8(x.c, C.int(offsetWidth), offsets, (*C.uint8_t)(data), C.int(byteWidth), (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), &row))
+	return int64(row), err
+}
+
+// FixedBinaryOffsets mirrors the offsets loop of CastFsbToBinary (kernels/string_casts.go:154-193): (off + i) · byteWidth.
+func (x *Context) FixedBinaryOffsets(offsetWidth, byteWidth int, off, n int64, dstOffsets unsafe.Pointer) error {
+	return x.err(C.ah_fixed_binary_offsets(x.c, C.int(offsetWidth), C.int(byteWidth), C.int64_t(off), C.int64_t(n), dstOffsets))
+}

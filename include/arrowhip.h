@@ -48,6 +48,7 @@ extern "C" {
 #define AH_ENOTIMPL 5   /* arrow.ErrNotImplemented */
 
 /* arrow.Type ids passed verbatim — arrow/datatype.go:36-72 == kernels/_lib/types.h:20-34 */
+#define AH_BOOL 1                /* a bitmap column, where an entry says it takes one (ah_format_int_*) */
 #define AH_UINT8 2
 #define AH_INT8 3
 #define AH_UINT16 4
@@ -623,6 +624,43 @@ int ah_cast_int_to_decimal(ah_ctx* ctx, int in_type, int out_width, int scale, c
  * out_type (AH_UINT8 … AH_INT64). */
 int ah_cast_decimal_to_int(ah_ctx* ctx, int in_width, int in_scale, int out_type, int allow_truncate, int allow_overflow,
                            const void* values, const uint8_t* valid, int64_t off, int64_t n, void* out_values);
+/* ---- string casts (row §8(f)-2) --------------------------------------------------------------------------
+ * The kernels behind compute's "cast" between String / Binary / LargeString / LargeBinary / FixedSizeBinary columns and the
+ * integer and boolean types.  A byte-string column is (offset_width 4 | 8, offsets, data): `offsets` is the offsets BUFFER and
+ * `off` the array's offset into it and into `valid` (NULL: all valid).  A fixed-width column is `values` pointing at its first row
+ * with `off` the bit offset of that row in `valid`; in_type AH_BOOL: `values` is the data bitmap, read at bit `off` as well.  A
+ * null row is never looked at.
+ *
+ * ah_parse_int replaces getParseStringExec under ScalarUnaryNotNullBinaryArg (kernels/numeric_cast.go:742-781,
+ * helpers.go:130-154): strconv.ParseInt(s, 0, bits) / ParseUint(s, 0, bits) of every valid row into out_type (AH_UINT8 … AH_INT64),
+ * 0 for a null row.  The reference keeps the error of the LAST offending valid row: AH_EINVALID with that row (relative to `off`) in
+ * *bad_row_host and 1 (strconv.ErrSyntax) or 2 (strconv.ErrRange) in *bad_kind_host, for the caller to quote the row's bytes.
+ * Synchronises once (the offender word). */
+int ah_parse_int(ah_ctx* ctx, int offset_width, const void* offsets, const uint8_t* data, const uint8_t* valid, int64_t off, int64_t n,
+                 int out_type, void* out_values, int64_t* bad_row_host, int* bad_kind_host);
+/* replaces the strconv.ParseBool kernels under ScalarUnaryNotNullBinaryArgBoolOut (kernels/boolean_cast.go:77-95): 1 t T TRUE true
+ * True / 0 f F FALSE false False into the bitmap out_bits from bit 0 (ceil(n / 8) bytes, every one written; a null row gives 0).
+ * Error as ah_parse_int (always a syntax error). */
+int ah_parse_bool(ah_ctx* ctx, int offset_width, const void* offsets, const uint8_t* data, const uint8_t* valid, int64_t off, int64_t n,
+                  uint8_t* out_bits, int64_t* bad_row_host);
+/* replace the integer / boolean → string formatters of addNumericAndTemporalToStringCasts (kernels/string_casts.go:444-579):
+ * strconv.FormatInt(v, 10) / FormatUint(v, 10) / "true" | "false" of every valid row, nothing for a null row.  Two calls with the
+ * caller's allocation in between, like ah_take_binary_offsets / _data: _offsets writes out_offsets[0 … n] (starting at 0) and
+ * returns the byte total to the host (one synchronisation; 4-byte offsets and a total above INT32_MAX: AH_EINVALID); _data, given
+ * the same column and those offsets, writes the characters (never synchronises). */
+int ah_format_int_offsets(ah_ctx* ctx, int in_type, const void* values, const uint8_t* valid, int64_t off, int64_t n, int offset_width,
+                          void* out_offsets, int64_t* out_total_bytes_host);
+int ah_format_int_data(ah_ctx* ctx, int in_type, const void* values, const uint8_t* valid, int64_t off, int64_t n, int offset_width,
+                       const void* out_offsets, uint8_t* out_data);
+/* replaces validateUTF8Sequence / validateUtf8 / validateUtf8Fsb (kernels/string_casts.go:39-87): utf8.Valid of every valid row,
+ * rows independent of each other.  offset_width 0: fixed-size rows of byte_width bytes, `data` the values buffer, row `off` the
+ * first.  The FIRST offending valid row: AH_EINVALID with the row (relative to `off`) in *bad_row_host.  Synchronises once. */
+int ah_validate_utf8(ah_ctx* ctx, int offset_width, const void* offsets, const uint8_t* data, int byte_width, const uint8_t* valid,
+                     int64_t off, int64_t n, int64_t* bad_row_host);
+/* replaces the offsets loop of CastFsbToBinary (kernels/string_casts.go:154-193): out_offsets[i] = (off + i) · byte_width for
+ * i = 0 … n, the offsets under which a FixedSizeBinary column's values buffer is a Binary column's data.  4-byte offsets that
+ * cannot hold (off + n) · byte_width: AH_EINVALID.  Never synchronises. */
+int ah_fixed_binary_offsets(ah_ctx* ctx, int offset_width, int byte_width, int64_t off, int64_t n, void* out_offsets);
 /* ---- temporal unit change (the casts either side of the temporal kernels) ----------------------------
  * replaces ShiftTime[InT, OutT](ctx, op, factor, input, output) (kernels/cast_temporal.go:35-104), the leaf of the
  * timestamp / duration / time32↔time64 / date32↔date64 casts (cast_temporal.go:240-420) and of the implicit unit

@@ -181,9 +181,10 @@ int ahc_record_column(ahc_session* s, ahc_datum* d, int i, const char** name, ah
  *   FilterOptions  null_selection_behavior=drop|emit_null; output_sizing=exact|worst_case (worst_case: the output is allocated
  *                  for the input's length and the kernel runs in ONE call — ah_filter_primitive_once — instead of count → allocate → fill)
  *   TakeOptions    bounds_check=0|1
- *   CastOptions    to_type=<type name>, or a decimal by its C Data format (d:22,2 = Decimal128, d:22,2,256 = Decimal256);
+ *   CastOptions    to_type=<type name>, string | large_string | binary | large_binary, or a parametric type by its C Data format
+ *                  (d:22,2 = Decimal128, d:22,2,256 = Decimal256, w:16 = FixedSizeBinary of 16 bytes);
  *                  to_logical=<C Data format>; safe=0; allow_int_overflow= allow_float_truncate= allow_decimal_truncate=
- *                  allow_time_truncate= allow_time_overflow=0|1
+ *                  allow_invalid_utf8= allow_time_truncate= allow_time_overflow=0|1
  *   SetOptions     value_set=@<hex address of an array ahc_datum>; null_matching_behavior=match|skip|emit_null|inconclusive
  *   SortOptions    sort_keys=<col>:<asc|desc>:<at_end|at_start>,…    ArraySortOptions  order= null_placement=
  *   CumulativeSumOptions  start=<number>; skip_nulls=0|1           RoundOptions  ndigits= round_mode= multiple=
