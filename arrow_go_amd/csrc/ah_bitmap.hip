@@ -17,6 +17,7 @@
 // range, whose out-of-range bits are preserved with a masked read-modify-write by
 // the single lane that owns it.  HBM-bound: 3/8 byte per row for a binary op.
 #include "ah_common.h"
+#include "ah_reduce.h"
 
 namespace {
 
@@ -98,34 +99,21 @@ __global__ __launch_bounds__(kBlock) void popcount_kernel(const uint8_t* __restr
     }
     acc += (uint64_t)__popcll(v);
   }
-  acc = ah_wave_sum(acc);
-  __shared__ uint64_t sm[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t tot = 0;
-    for (int k = 0; k < kBlock / 64; k++) tot += sm[k];
-    partials[blockIdx.x] = tot;
-  }
+  const ah_sum_u64 tot = ah_block_reduce<kBlock>(ah_sum_u64{acc});
+  if (threadIdx.x == 0) partials[blockIdx.x] = tot.s;
 }
 
-// mb != nullptr: the call's last launch also posts {*extra, total} to the host's mailbox (ah_popcount_post)
-__global__ __launch_bounds__(kBlock) void popcount_final_kernel(const unsigned long long* __restrict__ partials, int n,
-                                                                 unsigned long long* __restrict__ total, const unsigned long long* __restrict__ extra = nullptr,
-                                                                 unsigned long long* mb = nullptr, unsigned long long seq = 0) {
-  uint64_t acc = 0;
-  for (int i = threadIdx.x; i < n; i += kBlock) acc += partials[i];
-  acc = ah_wave_sum(acc);
-  __shared__ uint64_t sm[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t tot = 0;
-    for (int k = 0; k < kBlock / 64; k++) tot += sm[k];
-    *total = tot;
-    if (mb) { const unsigned long long w[2] = {*extra, tot}; ah_mailbox_post(mb, seq, w, 2); }
+// the finish (ah_reduce.h): the total; mb != nullptr: the call's last launch also posts {*extra, total} to the host's mailbox
+struct EmitPopcount {
+  unsigned long long* total;
+  const unsigned long long* extra;
+  unsigned long long* mb;
+  unsigned long long seq;
+  __device__ __forceinline__ void operator()(const ah_sum_u64& t) const {
+    *total = t.s;
+    if (mb) { const unsigned long long w[2] = {*extra, t.s}; ah_mailbox_post(mb, seq, w, 2); }
   }
-}
+};
 
 // Kleene and/or/and_not (scalar_boolean.go:93-104,163-174,289-302)
 template <int OP>
@@ -183,35 +171,30 @@ int launch_bitmap(ah_ctx* c, const uint8_t* l, int64_t loff, const uint8_t* r, i
 
 }  // namespace
 
-int ah_popcount_async(ah_ctx* c, const uint8_t* bits, int64_t off, int64_t nbits, unsigned long long* total_dev) {
+// the popcount of [off, off + nbits) into *total_dev; out_host != nullptr: AND {*extra_dev, that count} to the host in the same two
+// launches — a call that ends with "count the output's valid rows, then tell the host" spares the posting launch
+// (out_host[0] = *extra_dev, out_host[1] = the count).  Partials in the fixed area of dscalars, its own grid rule: no scratch.
+static int popcount(ah_ctx* c, const uint8_t* bits, int64_t off, int64_t nbits, unsigned long long* total_dev, const unsigned long long* extra_dev,
+                    unsigned long long* out_host) {
   OutSpan s = make_span((uint8_t*)bits, off, nbits);
   int64_t g = ah_ceil_div(s.nwords, (int64_t)kBlock * 4);  // ≥ 4 words per lane
-  unsigned grid = (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-  unsigned long long* partials = (unsigned long long*)&c->dscalars[64];
+  unsigned grid = (unsigned)(g < 1 ? 1 : (g > kPopcountMaxPartials ? kPopcountMaxPartials : g));
+  unsigned long long* partials = (unsigned long long*)&c->dscalars[kDsPopcountPartials];
+  unsigned long long* mb = nullptr;
+  unsigned long long seq = 0;
+  int rc;
+  if (out_host && (rc = ah_mailbox_begin(c, &mb, &seq)) != AH_OK) return rc;
   popcount_kernel<<<grid, kBlock, 0, c->stream>>>(bits, off, nbits, partials);
   AH_LAUNCH_CHECK(c);
-  popcount_final_kernel<<<1, kBlock, 0, c->stream>>>(partials, (int)grid, total_dev);
-  AH_LAUNCH_CHECK(c);
-  return AH_OK;
+  if ((rc = ah_reduce_finish(c, (const ah_sum_u64*)partials, (int)grid, EmitPopcount{total_dev, extra_dev, mb, seq})) != AH_OK) return rc;
+  return out_host ? ah_mailbox_wait(c, seq, 2, out_host) : AH_OK;
 }
-
-// the popcount of [off, off + nbits) into *total_dev AND {*extra_dev, that count} to the host in the same two launches: a call that ends
-// with "count the output's valid rows, then tell the host" spares the posting launch (out_host[0] = *extra_dev, out_host[1] = the count)
+int ah_popcount_async(ah_ctx* c, const uint8_t* bits, int64_t off, int64_t nbits, unsigned long long* total_dev) {
+  return popcount(c, bits, off, nbits, total_dev, nullptr, nullptr);
+}
 int ah_popcount_post(ah_ctx* c, const uint8_t* bits, int64_t off, int64_t nbits, unsigned long long* total_dev, const unsigned long long* extra_dev,
                      unsigned long long* out_host) {
-  OutSpan s = make_span((uint8_t*)bits, off, nbits);
-  int64_t g = ah_ceil_div(s.nwords, (int64_t)kBlock * 4);
-  unsigned grid = (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-  unsigned long long* partials = (unsigned long long*)&c->dscalars[64];
-  unsigned long long* mb;
-  unsigned long long seq;
-  int rc = ah_mailbox_begin(c, &mb, &seq);
-  if (rc != AH_OK) return rc;
-  popcount_kernel<<<grid, kBlock, 0, c->stream>>>(bits, off, nbits, partials);
-  AH_LAUNCH_CHECK(c);
-  popcount_final_kernel<<<1, kBlock, 0, c->stream>>>(partials, (int)grid, total_dev, extra_dev, mb, seq);
-  AH_LAUNCH_CHECK(c);
-  return ah_mailbox_wait(c, seq, 2, out_host);
+  return popcount(c, bits, off, nbits, total_dev, extra_dev, out_host);
 }
 
 AH_EXPORT int ah_bitmap_op(ah_ctx* c, int op, const uint8_t* l, int64_t loff, const uint8_t* r, int64_t roff,
@@ -254,7 +237,7 @@ AH_EXPORT int ah_count_set_bits(ah_ctx* c, const uint8_t* bits, int64_t off, int
   *out_host = 0;
   if (nbits == 0) return AH_OK;
   if (!bits) { *out_host = nbits; return AH_OK; }
-  unsigned long long* total = (unsigned long long*)c->dscalars;
+  unsigned long long* total = (unsigned long long*)&c->dscalars[kDsSum];
   int rc = ah_popcount_async(c, bits, off, nbits, total);
   if (rc != AH_OK) return rc;
   { int mrc = ah_mailbox_read(c, total, 1, (unsigned long long*)c->pinned); if (mrc != AH_OK) return mrc; }

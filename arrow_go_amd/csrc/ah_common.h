@@ -242,8 +242,15 @@ struct TempCarver {
   size_t used = 0;
   uint8_t* take(size_t b) { uint8_t* q = base + used; used += ah_pad(b); return q; }
 };
+// The words of dscalars (ah_ctx: kDsScalars scalar words, then the popcount's partials area) the streaming reductions own.
+constexpr int kDsScalars = 64;
+constexpr int kDsSum = 0;                           // ah_sum_*, ah_count_set_bits: the one result word
+constexpr int kDsFusedSum = 8, kDsFusedCount = 9;   // cmp_filter_sum_*: {sum, count}, read home as two mailbox words
+constexpr int kDsMinMax = 12;                       // min_max: {lo, hi}, ≤ 16 bytes
+constexpr int kDsPopcountPartials = kDsScalars;     // popcount: one word per workgroup …
+constexpr int kPopcountMaxPartials = 4096;          // … and as many workgroups at the most
 // internal (ah_bitmap.hip): popcount of bits [off, off+nbits) into *total_dev (8 bytes,
-// device), enqueued on the compute stream; uses dscalars[16..] as partials — no scratch.
+// device), enqueued on the compute stream; uses dscalars[kDsPopcountPartials ..] as partials — no scratch.
 int ah_popcount_async(ah_ctx* ctx, const uint8_t* bits, int64_t off, int64_t nbits, unsigned long long* total_dev);
 int ah_popcount_post(ah_ctx* ctx, const uint8_t* bits, int64_t off, int64_t nbits, unsigned long long* total_dev, const unsigned long long* extra_dev,
                      unsigned long long* out_host /* [2]: *extra_dev, the count */);
@@ -382,11 +389,31 @@ __device__ __forceinline__ void ah_store16(ST* base, int64_t i, const ah_vec16<S
   }
 }
 
+// the wave's sum / largest value, valid in lane 0 (the o = 32 … 1 tree); ah_wave_max2: two maxima side by side
 template <typename T>
 __device__ __forceinline__ T ah_wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
+}
+template <typename T>
+__device__ __forceinline__ T ah_wave_max(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const T t = __shfl_down(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+template <typename A, typename B>
+__device__ __forceinline__ void ah_wave_max2(A& a, B& b) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const A ta = __shfl_down(a, o, 64);
+    const B tb = __shfl_down(b, o, 64);
+    a = ta > a ? ta : a;
+    b = tb > b ? tb : b;
+  }
 }
 
 __device__ __forceinline__ int ah_lane() { return (int)(threadIdx.x & 63); }

@@ -25,8 +25,8 @@ static int ctx_init_common(ah_ctx* c) {
   AH_HIP(c, hipEventCreate(&c->t0));
   AH_HIP(c, hipEventCreate(&c->t1));
   AH_HIP(c, hipHostMalloc((void**)&c->pinned, 64 * sizeof(uint64_t), hipHostMallocDefault));
-  AH_HIP(c, hipMalloc((void**)&c->dscalars, (64 + 4096) * sizeof(uint64_t)));
-  AH_HIP(c, hipMemset(c->dscalars, 0, (64 + 4096) * sizeof(uint64_t)));   // (words [33] … [36] are kept zero between calls by the kernels that use them: ah_encode_first_look; ms_offs2_kernel when the two-cut encode passes it [35] / [36] for the largest bucket)
+  AH_HIP(c, hipMalloc((void**)&c->dscalars, (kDsScalars + kPopcountMaxPartials) * sizeof(uint64_t)));
+  AH_HIP(c, hipMemset(c->dscalars, 0, (kDsScalars + kPopcountMaxPartials) * sizeof(uint64_t)));   // (words [33] … [36] are kept zero between calls by the kernels that use them: ah_encode_first_look; ms_offs2_kernel when the two-cut encode passes it [35] / [36] for the largest bucket)
   AH_HIP(c, hipHostMalloc((void**)&c->mailbox, 256, hipHostMallocCoherent | hipHostMallocMapped));   // [0..7] filter_count, [8..15] ah_mailbox_*, [16] stall reports (ah_scan.hip)
   memset(c->mailbox, 0, 256);
   hipDeviceProp_t prop;

@@ -57,12 +57,7 @@ __global__ __launch_bounds__(1024) void gb_max_kernel(const unsigned long long* 
     m = t > m ? t : m;
     im = ti > im ? ti : im;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_down(m, o, 64), ti = __shfl_down(im, o, 64);
-    m = t > m ? t : m;
-    im = ti > im ? ti : im;
-  }
+  ah_wave_max2(m, im);
   if ((threadIdx.x & 63) == 0) { s_max[threadIdx.x >> 6] = m; s_imin[threadIdx.x >> 6] = im; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -594,12 +589,7 @@ __global__ __launch_bounds__(kThreads) void gb_aggregate_kernel(const unsigned l
   }
   if (DIRECT && FX && tile_range) {
     unsigned emax = range_pk.x, imin = range_pk.y;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned a = __shfl_down(emax, o, 64), b = __shfl_down(imin, o, 64);
-      emax = a > emax ? a : emax;
-      imin = b > imin ? b : imin;
-    }
+    ah_wave_max2(emax, imin);
     if ((t & 63) == 0) {   // 16 atomics per address: a workgroup's own pair of words
       if (emax) atomicMax(&tile_range[2 * blockIdx.x], emax);
       if (imin) atomicMax(&tile_range[2 * blockIdx.x + 1], imin);
@@ -867,13 +857,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8, 8))
     if (RANGE && tile_max && live[u] && !(rw[u] & kValNull) && (a >> 52) != 0x7ff && a != 0) { vmax = a > vmax ? a : vmax; vimin = fx_inv_exp(a) > vimin ? fx_inv_exp(a) : vimin; }
   }
   if (RANGE && tile_max) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long x = __shfl_down(vmax, o, 64);
-      const unsigned xi = __shfl_down(vimin, o, 64);
-      vmax = x > vmax ? x : vmax;
-      vimin = xi > vimin ? xi : vimin;
-    }
+    ah_wave_max2(vmax, vimin);
     if ((t & 63) == 0) { s_max[t >> 6] = vmax; s_imin[t >> 6] = vimin; }
   }
   __syncthreads();
@@ -1105,12 +1089,7 @@ __global__ __launch_bounds__(1024) void gs_subregions_kernel(const unsigned* __r
       m = a > m ? a : m;
       im = b > im ? b : im;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long a = __shfl_down(m, o, 64), b = __shfl_down(im, o, 64);
-      m = a > m ? a : m;
-      im = b > im ? b : im;
-    }
+    ah_wave_max2(m, im);
     if ((t & 63) == 0) { s_max[t >> 6] = m; s_imin[t >> 6] = im; }
     __syncthreads();
     if (t == 0) {
@@ -1421,11 +1400,7 @@ __global__ __launch_bounds__(256) void fx_sample_max_kernel(const unsigned long 
       if ((b >> 52) != 0x7ff && ah_bit(vvalid, voff + i)) m = b;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long x = __shfl_down(m, o, 64);
-    m = x > m ? x : m;
-  }
+  m = ah_wave_max(m);
   if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 __global__ void fx_guess_kernel(unsigned long long* __restrict__ range) {
@@ -1443,12 +1418,7 @@ __global__ __launch_bounds__(256) void fx_guess_check_kernel(const unsigned* __r
     emax = a > emax ? a : emax;
     imin = c > imin ? c : imin;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned a = __shfl_down(emax, o, 64), c = __shfl_down(imin, o, 64);
-    emax = a > emax ? a : emax;
-    imin = c > imin ? c : imin;
-  }
+  ah_wave_max2(emax, imin);
   if ((threadIdx.x & 63) == 0) { s_e[threadIdx.x >> 6] = emax; s_i[threadIdx.x >> 6] = imin; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1602,8 +1572,7 @@ __global__ __launch_bounds__(1024) void gq_quicklook_kernel(const unsigned long 
   // the last workgroup counts the keys the table holds (tickets over-count: lanes meeting one new key at once each take one)
   unsigned held = 0;
   for (int j = t; j < kSlots; j += 1024) held += __hip_atomic_load(&seed_keys[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kEmpty ? 1u : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) held += __shfl_down(held, o, 64);
+  held = ah_wave_sum(held);
   if ((t & 63) == 0) atomicAdd(&s_held, held);
   __syncthreads();
   if (t == 0) {
@@ -1729,12 +1698,7 @@ __global__ __launch_bounds__(1024) void gd_finish_kernel(GbTable rt, GbTable gt,
       emax = a > emax ? a : emax;
       imin = c > imin ? c : imin;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned a = __shfl_down(emax, o, 64), c = __shfl_down(imin, o, 64);
-      emax = a > emax ? a : emax;
-      imin = c > imin ? c : imin;
-    }
+    ah_wave_max2(emax, imin);
     if ((t & 63) == 0) { s_e[t >> 6] = emax; s_i[t >> 6] = imin; }
     __syncthreads();
     if (t == 0) {

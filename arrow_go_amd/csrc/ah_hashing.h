@@ -220,13 +220,7 @@ __global__ __launch_bounds__(kBlock) void absmax_kernel(const unsigned long long
     }
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(vals[n - 1], n - 1);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_down(m, o, 64);
-    const unsigned ti = __shfl_down(im, o, 64);
-    m = t > m ? t : m;
-    im = ti > im ? ti : im;
-  }
+  ah_wave_max2(m, im);
   __shared__ unsigned long long s_m[kBlock / 64];
   __shared__ unsigned s_im[kBlock / 64];
   if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_im[threadIdx.x >> 6] = im; }

@@ -229,12 +229,7 @@ __global__ __launch_bounds__(1024) void gb_segments_kernel(const unsigned* __res
       m = t > m ? t : m;
       im = ti > im ? ti : im;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long t = __shfl_down(m, o, 64), ti = __shfl_down(im, o, 64);
-      m = t > m ? t : m;
-      im = ti > im ? ti : im;
-    }
+    ah_wave_max2(m, im);
     if ((threadIdx.x & 63) == 0) { s_max[threadIdx.x >> 6] = m; s_imin[threadIdx.x >> 6] = im; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -403,13 +398,7 @@ __global__ __launch_bounds__(kThreads) void gb_scatter_kernel(const unsigned lon
     }
   }
   if (tile_max) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long x = __shfl_down(vmax, o, 64);
-      const unsigned xi = __shfl_down(vimin, o, 64);
-      vmax = x > vmax ? x : vmax;
-      vimin = xi > vimin ? xi : vimin;
-    }
+    ah_wave_max2(vmax, vimin);
     if ((threadIdx.x & 63) == 0) { s_max[threadIdx.x >> 6] = vmax; s_imin[threadIdx.x >> 6] = vimin; }
   }
   __syncthreads();

@@ -105,8 +105,8 @@ struct ValId {
 template <typename T>
 __global__ __launch_bounds__(kBlock) void pairs_kernel(const T* __restrict__ values, int64_t n, int descending, unsigned long long* __restrict__ keys,
                                                         unsigned* __restrict__ rows, unsigned long long* __restrict__ res) {
-  __shared__ unsigned long long s_r[kWaves][5];
-  unsigned long long a = ~0ull, o = 0ull, mn = ~0ull, mx = 0ull, nans = 0;
+  KeyStats st;
+  st.init();
   constexpr int U = 4;
   const int64_t stride = (int64_t)gridDim.x * kBlock * U;
   for (int64_t base = (int64_t)blockIdx.x * kBlock * U + threadIdx.x; base < n; base += stride) {
@@ -117,36 +117,15 @@ __global__ __launch_bounds__(kBlock) void pairs_kernel(const T* __restrict__ val
     for (int u = 0; u < U; u++) {
       const int64_t i = base + (int64_t)u * kBlock;
       if (i >= n) continue;
-      if (std::is_floating_point<T>::value && v[u] != v[u]) { nans++; continue; }
+      if (std::is_floating_point<T>::value && v[u] != v[u]) { st.nans++; continue; }
       const unsigned long long k = make_key<T>(v[u], descending);
       __builtin_nontemporal_store(k, &keys[i]);
       __builtin_nontemporal_store((unsigned)i, &rows[i]);
-      a &= k; o |= k;
-      mn = k < mn ? k : mn;
-      mx = k > mx ? k : mx;
+      st.add(k);
     }
   }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    a &= __shfl_down(a, s, 64);
-    o |= __shfl_down(o, s, 64);
-    const unsigned long long m1 = __shfl_down(mn, s, 64), m2 = __shfl_down(mx, s, 64);
-    mn = m1 < mn ? m1 : mn;
-    mx = m2 > mx ? m2 : mx;
-    nans += __shfl_down(nans, s, 64);
-  }
-  if ((threadIdx.x & 63) == 0) { unsigned long long* r = s_r[threadIdx.x >> 6]; r[0] = a; r[1] = o; r[2] = mn; r[3] = mx; r[4] = nans; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; w++) {
-      a &= s_r[w][0]; o |= s_r[w][1];
-      mn = s_r[w][2] < mn ? s_r[w][2] : mn;
-      mx = s_r[w][3] > mx ? s_r[w][3] : mx;
-      nans += s_r[w][4];
-    }
-    unsigned long long* r = res + (size_t)blockIdx.x * 5;
-    r[0] = a; r[1] = o; r[2] = mn; r[3] = mx; r[4] = nans;
-  }
+  st = ah_block_reduce<kBlock>(st);
+  if (threadIdx.x == 0) st.store<5>(res + (size_t)blockIdx.x * 5);
 }
 
 __global__ __launch_bounds__(kBlock) void emit_kernel(const unsigned* __restrict__ rows, int64_t n, uint64_t* __restrict__ out) {

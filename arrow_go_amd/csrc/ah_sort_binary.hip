@@ -165,11 +165,7 @@ __global__ __launch_bounds__(kBlock) void longest_run_kernel(const unsigned* __r
     const unsigned len = run_start[s + 1] - run_start[s];
     mx = len > mx ? len : mx;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = __shfl_down(mx, o, 64);
-    mx = t > mx ? t : mx;
-  }
+  mx = ah_wave_max(mx);
   if ((threadIdx.x & 63) == 0 && mx) atomicMax(out, mx);
 }
 

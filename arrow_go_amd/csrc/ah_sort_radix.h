@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <vector>
 #include "ah_common.h"
+#include "ah_reduce.h"
 
 namespace {
 
@@ -166,36 +167,33 @@ __global__ __launch_bounds__(kBlock) void scatter_kernel(SRC src, int64_t n, con
   }  // tiles of this block
 }
 
-// which key bits vary at all, and the extreme keys: per workgroup {AND, OR, min, max} of its keys (the host folds the ≤ 1024
-// partial results — four same-address atomics per wave would cost more than the pass)
+// Which key bits vary at all, the extreme keys, and (pairs_kernel, ah_sort.hip) how many rows were NaN: a part of the reduction layer
+// (ah_reduce.h).  Per workgroup; the host folds the ≤ 1024 partial results — same-address atomics per wave would cost more than the pass.
+struct KeyStats {
+  unsigned long long a, o, mn, mx, nans;
+  __device__ __forceinline__ void init() { a = ~0ull; o = 0ull; mn = ~0ull; mx = 0ull; nans = 0; }
+  __device__ __forceinline__ void add(unsigned long long k) { a &= k; o |= k; mn = k < mn ? k : mn; mx = k > mx ? k : mx; }
+  __device__ __forceinline__ void merge(const KeyStats& p) {
+    a &= p.a; o |= p.o;
+    mn = p.mn < mn ? p.mn : mn;
+    mx = p.mx > mx ? p.mx : mx;
+    nans += p.nans;
+  }
+  // res[0 … NWORDS): {AND, OR, min, max} and, with NWORDS = 5, the NaN count
+  template <int NWORDS>
+  __device__ __forceinline__ void store(unsigned long long* res) const {
+    res[0] = a; res[1] = o; res[2] = mn; res[3] = mx;
+    if (NWORDS == 5) res[4] = nans;
+  }
+};
+
 __global__ __launch_bounds__(kBlock) void and_or_kernel(const unsigned long long* __restrict__ keys, int64_t n, unsigned long long* __restrict__ res) {
-  __shared__ unsigned long long s_r[kWaves][4];
-  unsigned long long a = ~0ull, o = 0ull, mn = ~0ull, mx = 0ull;
+  KeyStats st;
+  st.init();
   const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const unsigned long long k = keys[i];
-    a &= k; o |= k;
-    mn = k < mn ? k : mn;
-    mx = k > mx ? k : mx;
-  }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    a &= __shfl_down(a, s, 64);
-    o |= __shfl_down(o, s, 64);
-    const unsigned long long m1 = __shfl_down(mn, s, 64), m2 = __shfl_down(mx, s, 64);
-    mn = m1 < mn ? m1 : mn;
-    mx = m2 > mx ? m2 : mx;
-  }
-  if ((threadIdx.x & 63) == 0) { s_r[threadIdx.x >> 6][0] = a; s_r[threadIdx.x >> 6][1] = o; s_r[threadIdx.x >> 6][2] = mn; s_r[threadIdx.x >> 6][3] = mx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; w++) {
-      a &= s_r[w][0]; o |= s_r[w][1];
-      mn = s_r[w][2] < mn ? s_r[w][2] : mn;
-      mx = s_r[w][3] > mx ? s_r[w][3] : mx;
-    }
-    res[blockIdx.x * 4 + 0] = a; res[blockIdx.x * 4 + 1] = o; res[blockIdx.x * 4 + 2] = mn; res[blockIdx.x * 4 + 3] = mx;
-  }
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) st.add(keys[i]);
+  st = ah_block_reduce<kBlock>(st);
+  if (threadIdx.x == 0) st.store<4>(res + (size_t)blockIdx.x * 4);
 }
 
 // temporaries of one call, carved out of the context's temp arena (the scratch arena is used by the scan this calls)

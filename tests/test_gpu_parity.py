@@ -2399,3 +2399,129 @@ def test_graph_capture_replays_a_chain():
     for d in (da, db, dc, dmask, dother, dand, dfused, dsum):
         d.free()
     ctx.close()
+
+
+# ---- the streaming-reduction layer (ah_reduce.h): Sum, fused filter-sum, min_max, popcount, the sort's key statistics -------------
+REDUCE_SETTINGS = [(bpc, nt) for bpc in (1, 2, 8) for nt in (0, 1)]
+# rows of 8-byte types: one walk iteration of 256 × 4 vectors of two rows, ± 1 (a head row when misaligned); 2^20 makes the
+# grid-stride loop wrap at one workgroup per CU
+REDUCE_SIZES = [1, 2, 3, 2047, 2048, 2049, 2050, 4097, 1 << 20]
+
+
+def _with_reduce_settings(ctx, run):
+    """run() under every (blocks_per_cu, nt) setting → the list of its results; the context's own settings come back afterwards"""
+    import os
+    try:
+        out = []
+        for bpc, nt in REDUCE_SETTINGS:
+            ctx.set_option("blocks_per_cu", bpc)
+            ctx.set_option("nt", nt)
+            out.append(run())
+        return out
+    finally:
+        ctx.set_option("blocks_per_cu", int(os.environ.get("ARROWHIP_BLOCKS_PER_CU", 0)))
+        ctx.set_option("nt", int(os.environ.get("ARROWHIP_NT", 1)))
+
+
+def test_reductions_are_independent_of_grid_and_hint(ctx, orc_be):
+    """Sum, the fused filter-sum, min_max and the popcount return the oracle's answer whatever the grid (1, 2, 8 workgroups per CU)
+    and with or without the nontemporal hint: the walk, the workgroup reduction and the finish they share leave no row out and
+    count none twice at any of the sizes around one walk iteration."""
+    import arrow_go_amd as ah
+    N = ah._native
+    rng = np.random.default_rng(9100)
+
+    def check(what, run, want):
+        got = _with_reduce_settings(ctx, run)
+        assert all(g == want for g in got), (what, got, want)
+
+    for n in REDUCE_SIZES:
+        raw = rng.integers(0, 2**64 - 1, n, dtype=np.uint64, endpoint=True)
+        ints = rng.integers(-2**40, 2**40, n).astype(np.float64)          # integer-valued doubles: exact in any order
+        x = rng.integers(-10**9, 10**9, n, dtype=np.int64)
+        valid = rand_bits(rng, n + 5, 0.9)
+        dvalid = ctx.to_device(valid)
+        want_sum_f64 = float(ints.astype(np.int64).sum())
+        want_fused = orc_be.cmp_filter_sum_i64(GT, x, None, 0, 0), orc_be.cmp_filter_sum_i64(GT, x, valid, 5, 0)
+        for misalign in (0, 1):
+            lead = 8 * misalign
+            draw, dints, dx = ctx.alloc(lead + 8 * n + 64), ctx.alloc(lead + 8 * n + 64), ctx.alloc(lead + 8 * n + 64)
+            draw.upload(raw, lead); dints.upload(ints, lead); dx.upload(x, lead)
+            what = (n, misalign)
+            check(("sum_int64",) + what, lambda: ctx.sum_int64(draw.ptr + lead, n), orc_be.sum(raw.view(np.int64)))
+            check(("sum_uint64",) + what, lambda: ctx.sum_uint64(draw.ptr + lead, n), orc_be.sum(raw))
+            check(("sum_float64",) + what, lambda: ctx.sum_float64(dints.ptr + lead, n), want_sum_f64)
+            check(("fused",) + what, lambda: ctx.cmp_filter_sum_i64(GT, dx.ptr + lead, None, 0, n, 0), want_fused[0])
+            check(("fused, validity",) + what, lambda: ctx.cmp_filter_sum_i64(GT, dx.ptr + lead, dvalid, 5, n, 0), want_fused[1])
+            for dt in OL.INT_DTYPES:   # the same bytes as rows of every width
+                v = raw.view(dt)
+                check(("min_max", str(dt)) + what, lambda: ctx.min_max(OL.TYPE_IDS[dt], draw.ptr + lead, v.size, dt), orc_be.min_max(v))
+            for d in (draw, dints, dx):
+                d.free()
+        dvalid.free()
+    for n in (15, 16, 17, 16383, 16384, 16385, 16400):   # 1-byte rows: 16 per vector
+        for dt in (np.dtype(np.int8), np.dtype(np.uint8)):
+            v = rand(rng, dt, n)
+            for misalign in (0, 1):
+                d = ctx.alloc(misalign + n + 64)
+                d.upload(v, misalign)
+                check(("min_max", str(dt), n, misalign), lambda: ctx.min_max(OL.TYPE_IDS[dt], d.ptr + misalign, n, dt), orc_be.min_max(v))
+                d.free()
+    bits = rand_bits(rng, 300007 + 65)
+    dbits = ctx.to_device(bits)
+    for off in (0, 1, 7, 63, 64, 65):
+        for nbits in (1, 63, 64, 65, 65535, 65536, 65537, 300007):
+            check(("popcount", off, nbits), lambda: ctx.count_set_bits(dbits, off, nbits), orc_be.count_set_bits(bits, off, nbits))
+    dbits.free()
+
+
+@pytest.mark.parametrize("dtype", OL.INT_DTYPES, ids=str)
+def test_min_max_sizes_and_alignment(hip, orc_be, dtype):
+    """the extreme values in every place the kernel treats differently: the head rows before the 16-byte-aligned body, the tail rows
+    after it, the first and the last vector of the body, and the last row of the ragged walk iteration"""
+    dt = np.dtype(dtype)
+    info = np.iinfo(dt)
+    V = 16 // dt.itemsize
+    rng = np.random.default_rng(9200 + OL.TYPE_IDS[dt])
+    mid_lo, mid_hi = info.min // 2, info.max // 2
+    for nvec in (1, 3, 1023, 1024, 1025, 2 * 1024 + 7):   # vectors of the body: below, at and past one walk iteration of 256 × 4
+        for misalign in (0, 1):
+            head = (V - misalign) % V if misalign else 0    # rows before the first aligned vector
+            tail = V - 1
+            n = head + nvec * V + tail
+            base = rng.integers(mid_lo, mid_hi, n, dtype=dt, endpoint=True)
+            places = {"first body vector": head, "last body vector": head + (nvec - 1) * V, "tail row": n - 1}
+            if nvec % 1024:   # the body's last vector sits in the ragged iteration
+                places["last row of the ragged iteration"] = head + nvec * V - 1
+            if nvec >= 1024:
+                places["last row of the last full iteration"] = head + (nvec // 1024) * 1024 * V - 1
+            if head:
+                places["head row"] = 0
+            for where, i in places.items():
+                for j in (i, n - 1 - i):   # min at the place and max at its mirror image, then the other way round
+                    a = base.copy()
+                    a[i], a[j] = info.min, info.max
+                    want = orc_be.min_max(a)
+                    assert (want[0] == info.min or i == j) and want[1] == info.max
+                    assert hip.min_max(a, misalign) == want, (dtype, nvec, misalign, where)
+                    a[i], a[j] = info.max, info.min
+                    assert hip.min_max(a, misalign) == orc_be.min_max(a), (dtype, nvec, misalign, where)
+    assert hip.min_max(np.zeros(0, dt)) == orc_be.min_max(np.zeros(0, dt)) == (info.max, info.min)
+
+
+@pytest.mark.parametrize("n", [1 << 20, (1 << 20) + 1])
+def test_sort_indices_key_statistics(hip, orc_be, n):
+    """From 2^20 rows on a column without validity takes the one-pass key + statistics kernel (AND / OR / min / max of the keys and the
+    NaN count per workgroup, folded by the host).  Keys that differ only in bits 40–47: the passes the sort runs are chosen from those
+    statistics, and a wrong AND / OR would skip the one byte that matters; the Float64 column's one NaN, in the last row, must send it
+    down the partition path."""
+    rng = np.random.default_rng(9300 + n)
+    byte5 = rng.integers(0, 256, n, dtype=np.int64) << 40
+    ints = (np.int64(0x1234) << 48) + byte5 + 0x89ABCDEF01
+    flts = ((np.int64(0x4012) << 48) + byte5 + 0x89ABCDEF01).view(np.float64).copy()
+    flts[n - 1] = np.nan
+    for a in (ints, flts):
+        for desc in (False, True):
+            e = orc_be.sort_indices(a, None, 0, desc, False)
+            g = hip.sort_indices(a, None, 0, desc, False)
+            assert g.tobytes() == e.tobytes(), (a.dtype, n, desc)

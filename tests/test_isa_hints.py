@@ -35,6 +35,7 @@ EXPECT = {
     ],
     "ah_compare.hip": [(r"compare_kernelIlLi2ELi1ELb1ELb1E", {"global_load_dwordx4 nt": 4})],          # greater(Int64 array, scalar)
     "ah_fused.hip": [(r"fused_kernelIlLi2ELb0ELb1E", {"global_load_dwordx4 nt": 4})],                   # C4: Compare(>) → Filter → Sum
+    "ah_minmax.hip": [(r"minmax_partials_kernelIlLb1E", {"global_load_dwordx4 nt": 4})],               # the walk of ah_reduce.h, hinted
     "ah_arith.hip": [
         (r"binary_kernelImLi0ELi0ELb1ELb1E", {"global_load_dwordx4 nt": 8, "global_store_dwordx4 nt": 4}),   # aligned Int64 Add: the headline kernel
         (r"binary_kernelImLi0ELi0ELb0ELb1E", {"global_load_dwordx4 nt": 8, "global_store_dwordx4 nt": 4}),   # … over an element-aligned slice
@@ -85,6 +86,10 @@ RESOURCES = {
         (r"is_in_bytes_kernelILi[048]ELi2E", 58, 0),
         (r"is_in_bytes_kernelILi[048]ELi3E", 97, 0),
     ],
+    # the streaming reductions at the figures they had before they moved onto ah_reduce.h ("Streaming reductions")
+    "ah_sum.hip": [(r"sum_partials_kernelIdN\w*AccDDELb1E", 55, 0), (r"sum_partials_kernelImN\w*AccU64ELb1E", 28, 0)],
+    "ah_fused.hip": [(r"fused_kernelIlLi2ELb0ELb1E", 30, 0), (r"fused_kernelIlLi2ELb1ELb1E", 41, 0), (r"fused_kernelIdLi2ELb0ELb1E", 46, 0)],
+    "ah_minmax.hip": [(r"minmax_partials_kernelIlLb1E", 26, 0), (r"minmax_partials_kernelIaLb1E", 71, 0)],
     "ah_sort_binary.hip": [
         (r"round_keys_kernel", 23, 0),
         (r"hist_kernelINS_9BinColumnE", 18, 0),
