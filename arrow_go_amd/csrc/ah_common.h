@@ -177,6 +177,10 @@ int ah_arith_binary(ah_ctx* ctx, int type, int op, int shape, const void* l, con
 int ah_partition_by_group(ah_ctx* ctx, const int32_t* ids, const unsigned long long* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
                           int shift, int passes, unsigned* hist, unsigned* offs, unsigned long long* alt_vals, unsigned* alt_ids,
                           unsigned long long* out_vals, unsigned* out_ids);
+// internal (ah_hash_minmax.hip): per-group {min, max, count of valid values} over dense ids < ngroups, for the group-by of ah_hash.hip.
+// kind 0 / 1 / 2 = Uint64 / Int64 / Float64 order (NaNs counted, never a minimum or maximum).  Enqueued on the compute stream.
+int ah_group_min_max(ah_ctx* ctx, int kind, const int32_t* ids, const void* vals, const uint8_t* vvalid, int64_t voff, int64_t n, int64_t ngroups,
+                     void* out_mins, void* out_maxs, int64_t* out_counts);
 // internal (ah_sort_msd.hip): the `rest` range of sort_indices by two MSD partition passes + one wave per bucket; *used = 0: not
 // applicable or a bucket came out too large — the pairs are clobbered and the caller regenerates them for the LSD passes
 int ah_sort_rest_msd(ah_ctx* ctx, unsigned long long* keys, unsigned* rows, unsigned long long* alt_keys, unsigned* alt_rows, int64_t n,

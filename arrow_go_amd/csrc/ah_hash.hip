@@ -1087,6 +1087,29 @@ int hash_sum(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t kof
   return AH_OK;
 }
 
+// group-by min / max: the same groups as hash_sum (ids from encode_core), the aggregate in ah_hash_minmax.hip
+int hash_min_max(ah_ctx* c, int kind, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, const void* vals, const uint8_t* vvalid,
+                 int64_t voff, int64_t n, uint64_t* out_keys, void* out_mins, void* out_maxs, int64_t* out_counts, int64_t* out_first_rows,
+                 int64_t* out_ngroups_host, int32_t* out_null_group_host) {
+  if (n < 0 || koff < 0 || voff < 0) return ah_fail(c, AH_EINVALID, "hash_min_max: negative length/offset");
+  if (out_ngroups_host) *out_ngroups_host = 0;
+  if (out_null_group_host) *out_null_group_host = -1;
+  if (n == 0) return AH_OK;
+  if (!keys || !vals || !out_keys || !out_mins || !out_maxs || !out_counts) return ah_fail(c, AH_EINVALID, "hash_min_max: null buffer");
+  // the one temporary: a dense group id per row, in the context's temp arena (encode_core stays out of it: allow_partitioned = false)
+  void* arena = nullptr;
+  int rc = ah_temp_reserve(c, ah_pad((size_t)n * 4), &arena);
+  if (rc != AH_OK) return rc;
+  int32_t* ids = (int32_t*)arena;
+  EncodeResult res;
+  rc = encode_core(c, U64Keys{(const unsigned long long*)keys}, kvalid, koff, n, /*encode_nulls=*/1, ids, out_keys, &res, out_first_rows, /*allow_partitioned=*/false);
+  if (rc != AH_OK) return rc;
+  if ((rc = ah_group_min_max(c, kind, ids, vals, vvalid, voff, n, res.ndict, out_mins, out_maxs, out_counts)) != AH_OK) return rc;
+  if (out_ngroups_host) *out_ngroups_host = res.ndict;
+  if (out_null_group_host) *out_null_group_host = res.null_id;
+  return AH_OK;
+}
+
 }  // namespace
 
 static int ids_validity(ah_ctx* c, const uint8_t* valid, int64_t off, int64_t n, int encode_nulls, uint8_t* out_ids_valid) {
@@ -1185,6 +1208,33 @@ AH_EXPORT int ah_hash_sum_i64(ah_ctx* c, const uint64_t* keys, const uint8_t* kv
   return hash_sum<unsigned long long, unsigned long long>(c, keys, kvalid, koff, (const unsigned long long*)vals, vvalid, voff, n,
                                                           out_keys, (unsigned long long*)out_sums, out_counts, out_first_rows,
                                                           out_ngroups_host, out_null_group_host);
+}
+
+AH_EXPORT int ah_hash_min_max_i64(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
+                                  const int64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                                  uint64_t* out_keys, int64_t* out_mins, int64_t* out_maxs, int64_t* out_counts, int64_t* out_first_rows,
+                                  int64_t* out_ngroups_host, int32_t* out_null_group_host) {
+  AH_ENTER(c);
+  return hash_min_max(c, 1, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_mins, out_maxs, out_counts, out_first_rows,
+                      out_ngroups_host, out_null_group_host);
+}
+
+AH_EXPORT int ah_hash_min_max_u64(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
+                                  const uint64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                                  uint64_t* out_keys, uint64_t* out_mins, uint64_t* out_maxs, int64_t* out_counts, int64_t* out_first_rows,
+                                  int64_t* out_ngroups_host, int32_t* out_null_group_host) {
+  AH_ENTER(c);
+  return hash_min_max(c, 0, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_mins, out_maxs, out_counts, out_first_rows,
+                      out_ngroups_host, out_null_group_host);
+}
+
+AH_EXPORT int ah_hash_min_max_f64(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
+                                  const double* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                                  uint64_t* out_keys, double* out_mins, double* out_maxs, int64_t* out_counts, int64_t* out_first_rows,
+                                  int64_t* out_ngroups_host, int32_t* out_null_group_host) {
+  AH_ENTER(c);
+  return hash_min_max(c, 2, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_mins, out_maxs, out_counts, out_first_rows,
+                      out_ngroups_host, out_null_group_host);
 }
 
 // ---- key → owner partition for the multi-GPU merge (SURVEY.md §8e plan A) ----------------------

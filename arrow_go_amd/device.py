@@ -707,6 +707,19 @@ class Context:
                               _ptr(out_sums), _ptr(out_counts), _ptr(out_first_rows), C.byref(ng), C.byref(nid)))
         return ng.value, nid.value
 
+    def hash_min_max(self, kind: str, keys, kvalid, koff: int, vals, vvalid, voff: int, n: int, out_keys, out_mins, out_maxs, out_counts,
+                     out_first_rows=None):
+        """group-by min / max of 8-byte values (kind "i64" signed, "u64" unsigned, "f64": NaNs ignored, -0 < +0) over the groups of
+        hash_sum; a group with count 0 holds zero bytes.  Returns (ngroups, null_group)."""
+        fns = {"i64": lib.ah_hash_min_max_i64, "u64": lib.ah_hash_min_max_u64, "f64": lib.ah_hash_min_max_f64}
+        if kind not in fns:
+            raise ValueError(f"hash_min_max: kind must be one of 'i64', 'u64', 'f64', not {kind!r}")
+        ng = C.c_int64()
+        nid = C.c_int32()
+        check(self.handle, fns[kind](self.handle, _ptr(keys), _ptr(kvalid), koff, _ptr(vals), _ptr(vvalid), voff, n, _ptr(out_keys),
+                                     _ptr(out_mins), _ptr(out_maxs), _ptr(out_counts), _ptr(out_first_rows), C.byref(ng), C.byref(nid)))
+        return ng.value, nid.value
+
     def hash_partition(self, keys, n: int, nparts: int, out_part) -> None:
         check(self.handle, lib.ah_hash_partition_u64(self.handle, _ptr(keys), n, nparts, _ptr(out_part)))
 

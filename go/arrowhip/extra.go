@@ -165,6 +165,37 @@ func (x *Context) HashSumInt64(keys, kvalid unsafe.Pointer, koff int64, vals, vv
 	return int64(ng), int32(nid), x.err(st)
 }
 
+// HashMinMaxInt64: the group-by minimum / maximum / count with Int64 values (signed order) over the groups of HashSumInt64;
+// a group without valid values has count 0 and zero bytes in both.
+func (x *Context) HashMinMaxInt64(keys, kvalid unsafe.Pointer, koff int64, vals, vvalid unsafe.Pointer, voff, n int64,
+	outKeys, outMins, outMaxs, outCounts, outFirstRows unsafe.Pointer) (ngroups int64, nullGroup int32, err error) {
+	var ng C.int64_t
+	var nid C.int32_t
+	st := C.ah_hash_min_max_i64(x.c, (*C.uint64_t)(keys), (*C.uint8_t)(kvalid), C.int64_t(koff), (*C.int64_t)(vals), (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		(*C.uint64_t)(outKeys), (*C.int64_t)(outMins), (*C.int64_t)(outMaxs), (*C.int64_t)(outCounts), (*C.int64_t)(outFirstRows), &ng, &nid)
+	return int64(ng), int32(nid), x.err(st)
+}
+
+// HashMinMaxUint64: the same in unsigned order.
+func (x *Context) HashMinMaxUint64(keys, kvalid unsafe.Pointer, koff int64, vals, vvalid unsafe.Pointer, voff, n int64,
+	outKeys, outMins, outMaxs, outCounts, outFirstRows unsafe.Pointer) (ngroups int64, nullGroup int32, err error) {
+	var ng C.int64_t
+	var nid C.int32_t
+	st := C.ah_hash_min_max_u64(x.c, (*C.uint64_t)(keys), (*C.uint8_t)(kvalid), C.int64_t(koff), (*C.uint64_t)(vals), (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		(*C.uint64_t)(outKeys), (*C.uint64_t)(outMins), (*C.uint64_t)(outMaxs), (*C.int64_t)(outCounts), (*C.int64_t)(outFirstRows), &ng, &nid)
+	return int64(ng), int32(nid), x.err(st)
+}
+
+// HashMinMaxFloat64: the same for Float64: NaNs are counted and otherwise ignored, -0 < +0, a group of NaNs only gives the quiet NaN.
+func (x *Context) HashMinMaxFloat64(keys, kvalid unsafe.Pointer, koff int64, vals, vvalid unsafe.Pointer, voff, n int64,
+	outKeys, outMins, outMaxs, outCounts, outFirstRows unsafe.Pointer) (ngroups int64, nullGroup int32, err error) {
+	var ng C.int64_t
+	var nid C.int32_t
+	st := C.ah_hash_min_max_f64(x.c, (*C.uint64_t)(keys), (*C.uint8_t)(kvalid), C.int64_t(koff), (*C.double)(vals), (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		(*C.uint64_t)(outKeys), (*C.double)(outMins), (*C.double)(outMaxs), (*C.int64_t)(outCounts), (*C.int64_t)(outFirstRows), &ng, &nid)
+	return int64(ng), int32(nid), x.err(st)
+}
+
 // HashPartition: partition id of every key by the reference's integer hash (internal/hashing/hash_funcs.go:60-67) — the owner
 // function of the C5 merge.
 func (x *Context) HashPartition(keys unsafe.Pointer, n int64, nparts int, outPart unsafe.Pointer) error {

@@ -475,6 +475,25 @@ int ah_hash_sum_i64(ah_ctx* ctx, const uint64_t* keys, const uint8_t* kvalid, in
                     const int64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
                     uint64_t* out_keys, int64_t* out_sums, int64_t* out_counts, int64_t* out_first_rows,
                     int64_t* out_ngroups_host, int32_t* out_null_group_host);
+/* group-by min / max (NEW — no reference analogue; definition in DESIGN.md): the groups, their order, out_keys, out_first_rows, the
+ * null group and *out_ngroups_host are those of ah_hash_sum_* on the same keys.  out_counts[g] = number of valid vals of group g
+ * (Float64: NaNs included), out_mins[g] / out_maxs[g] = the smallest / largest valid value; a group with out_counts[g] == 0 has 8 zero
+ * bytes in both.  i64: signed order, u64: unsigned order.  f64: NaNs are ignored, the rest is ordered numerically with -0 < +0
+ * (+-inf take part); a group whose valid values are all NaN gives the quiet NaN 0x7FF8000000000000 in both.  The result is a function
+ * of the inputs alone: the same bytes run after run and on every path.  Outputs sized like out_dict above (n + 1 entries of room);
+ * <= 2^30 rows per call; n == 0: no groups, nothing touched. */
+int ah_hash_min_max_i64(ah_ctx* ctx, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
+                        const int64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                        uint64_t* out_keys, int64_t* out_mins, int64_t* out_maxs, int64_t* out_counts,
+                        int64_t* out_first_rows, int64_t* out_ngroups_host, int32_t* out_null_group_host);
+int ah_hash_min_max_u64(ah_ctx* ctx, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
+                        const uint64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                        uint64_t* out_keys, uint64_t* out_mins, uint64_t* out_maxs, int64_t* out_counts,
+                        int64_t* out_first_rows, int64_t* out_ngroups_host, int32_t* out_null_group_host);
+int ah_hash_min_max_f64(ah_ctx* ctx, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
+                        const double* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                        uint64_t* out_keys, double* out_mins, double* out_maxs, int64_t* out_counts,
+                        int64_t* out_first_rows, int64_t* out_ngroups_host, int32_t* out_null_group_host);
 
 /* ---- fused Compare(op scalar) → Filter(DropNulls) → Sum ------------------------------
  * NEW entry point (no reference analogue) computing in ONE pass what the reference
