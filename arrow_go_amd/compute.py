@@ -68,6 +68,8 @@ lib.ahc_scalar_set_logical.argtypes = [_vp, _vp, C.c_char_p]
 lib.ahc_ipc_bytes_uploaded.argtypes = [_vp]
 lib.ahc_ipc_bytes_uploaded.restype = C.c_int64
 lib.ahc_ipc_inspect.argtypes = [_vp, C.c_int64, C.c_char_p, C.c_int64]
+lib.ahc_ipc_stats.argtypes = [_vp, C.POINTER(C.c_int64)]
+lib.ahc_ipc_stats.restype = None
 lib.ahc_substrait_inspect.argtypes = [_vp, C.c_int64, C.c_char_p, C.c_int64]
 lib.ahc_dispatch_best.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int64]
 lib.ahc_expr_eval.argtypes = [_vp, C.c_char_p, C.c_int, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(C.c_int)]
@@ -319,6 +321,7 @@ class Session:
         if rc != 0:
             raise ErrHip("ahc_session_create failed: is a GPU visible? (no CPU fallback)")
         self.h = h
+        self.last_ipc_stats = dict(bytes_uploaded=0, device_buffers=0, host_buffers=0, device_fallbacks=0)   # of the latest read_ipc
         self.device_id = device_id
 
     def close(self):
@@ -439,7 +442,9 @@ class Session:
         return DeviceArray(self, d)
 
     def set_option(self, name: str, value: int) -> None:
-        """ExecCtx fields of this session: 'chunk_bytes' (ExecCtx.ChunkSize's role for host-resident arguments), 'host_threshold_bytes'."""
+        """ExecCtx fields of this session: 'chunk_bytes' (ExecCtx.ChunkSize's role for host-resident arguments), 'host_threshold_bytes';
+        for the read_ipc calls that follow: 'ipc_device_lz4' (1: LZ4_FRAME bodies of independent blocks are inflated in HBM, 0: on the
+        host like every other compressed body), 'ipc_device_lz4_min_bytes' (smaller compressed bodies stay on the host)."""
         self._check(lib.ahc_session_set_option(self.h, name.encode(), int(value)))
 
     def import_host(self, arr) -> "DeviceArray":
@@ -582,10 +587,17 @@ class Session:
     def read_ipc(self, buf):
         """Iterate the record batches of an Arrow IPC *stream* (bytes / pyarrow.Buffer / mmap): yields
         (field names, [DeviceArray per column], rows).  Each body goes to the device in one copy; the columns
-        are slices of it."""
+        are slices of it.  `last_ipc_stats` follows the reader batch by batch: body bytes uploaded, and how many compressed buffers
+        were inflated on the device, on the host, and on the host after the device decoder reported a status."""
         keep, addr, n = _as_bytes_ptr(buf)
         r = _vp()
         self._check(lib.ahc_ipc_open(self.h, addr, n, C.byref(r)))
+
+        def note_stats():
+            st = (C.c_int64 * 4)()
+            lib.ahc_ipc_stats(r, st)
+            self.last_ipc_stats = dict(zip(("bytes_uploaded", "device_buffers", "host_buffers", "device_fallbacks"), list(st)))
+
         try:
             nf = lib.ahc_ipc_num_fields(r)
             names = []
@@ -597,10 +609,12 @@ class Session:
                 cols = (_vp * max(nf, 1))()
                 rows = C.c_int64()
                 self._check(lib.ahc_ipc_next(r, cols, C.byref(rows)))
+                note_stats()
                 if rows.value < 0:
                     return
                 yield names, [DeviceArray(self, _vp(cols[i])) for i in range(nf)], rows.value
         finally:
+            note_stats()
             lib.ahc_ipc_close(r)
             del keep
 

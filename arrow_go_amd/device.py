@@ -720,6 +720,18 @@ class Context:
                                      _ptr(out_mins), _ptr(out_maxs), _ptr(out_counts), _ptr(out_first_rows), C.byref(ng), C.byref(nid)))
         return ng.value, nid.value
 
+    def lz4_decompress_blocks(self, src, src_bytes: int, dst, dst_bytes: int, blocks):
+        """independent LZ4 blocks of the device bytes `src` inflated into the device bytes `dst`; blocks: rows of {src_off, src_len
+        (bit 62: stored), dst_off, dst_len <= 65536}, dst_off ascending.  Returns the status byte of every block as a numpy array
+        (0 ok, 1 corrupt, 2 produced != dst_len); a block with a status leaves unspecified bytes in its own output range only."""
+        table = np.ascontiguousarray(np.asarray(blocks, np.int64).reshape(-1, 4))
+        status = np.zeros(len(table), np.uint8)
+        nbad = C.c_int64()
+        check(self.handle, lib.ah_lz4_decompress_blocks(self.handle, _ptr(src), src_bytes, _ptr(dst), dst_bytes, table.ctypes.data, len(table),
+                                                        status.ctypes.data, C.byref(nbad)))
+        assert nbad.value == int(np.count_nonzero(status))
+        return status
+
     def hash_partition(self, keys, n: int, nparts: int, out_part) -> None:
         check(self.handle, lib.ah_hash_partition_u64(self.handle, _ptr(keys), n, nparts, _ptr(out_part)))
 

@@ -23,11 +23,18 @@ using namespace arrowhip;
 using compute::Datum;
 using compute::DatumKind;
 
+// the smallest measured compressed body from which the device path's median was no worse than the host path's for both contents of
+// scripts/bench_ipc_lz4.py (profiles/ipc_lz4_device.json, DESIGN.md §3.8: the compressible content at 2^24 plain bytes)
+constexpr int64_t kIpcDeviceLz4MinBytes = 6791443;
+
 struct ahc_session {
   std::shared_ptr<Session> session;  // shared with every live buffer (Buffer::keep): destroying the handle never frees a pool a datum still returns memory to
   std::unique_ptr<compute::FunctionRegistry> child_registry;  // per-session registry, like SetExecCtx
   compute::ExecCtx ectx;
   std::string err;
+  // ahc_ipc_open: LZ4_FRAME bodies of independent blocks are inflated in HBM (1) or on the host like every other compressed body (0);
+  // bodies of fewer compressed bytes than the minimum stay on the host (default: kIpcDeviceLz4MinBytes above)
+  int64_t ipc_device_lz4 = 1, ipc_device_lz4_min_bytes = kIpcDeviceLz4MinBytes;
 };
 struct ahc_datum {
   Datum d;
@@ -238,12 +245,15 @@ AHC_EXPORT int ahc_import_host(ahc_session* s, ArrowArray* arr, ArrowSchema* sch
 AHC_EXPORT int ahc_datum_on_host(ahc_datum* d) { return d->d.kind == DatumKind::Array && d->d.array->on_host && !d->d.array->device_twin ? 1 : 0; }
 
 // the ExecCtx fields of this session: "chunk_bytes" (ExecCtx.ChunkSize's role for host-resident arguments: bytes of the widest column
-// per span, 0 = 32 MiB), "host_threshold_bytes" (ahc_import_host keeps arrays of at least this many value bytes on the host)
+// per span, 0 = 32 MiB), "host_threshold_bytes" (ahc_import_host keeps arrays of at least this many value bytes on the host);
+// "ipc_device_lz4" / "ipc_device_lz4_min_bytes": where the readers opened afterwards inflate LZ4_FRAME bodies (see ahc_session)
 AHC_EXPORT int ahc_session_set_option(ahc_session* s, const char* name, int64_t value) {
   const std::string n = name ? name : "";
   if (value < 0) return Fail(s, Status::Make(StatusCode::Invalid, "option '" + n + "': negative value"));
   if (n == "chunk_bytes") s->ectx.ChunkBytes = value;
   else if (n == "host_threshold_bytes") s->ectx.HostThresholdBytes = value;
+  else if (n == "ipc_device_lz4") s->ipc_device_lz4 = value != 0;
+  else if (n == "ipc_device_lz4_min_bytes") s->ipc_device_lz4_min_bytes = value;
   else return Fail(s, Status::Make(StatusCode::KeyError, "unknown session option '" + n + "'"));
   return 0;
 }
@@ -1047,6 +1057,7 @@ AHC_EXPORT int ahc_ipc_open(ahc_session* s, const uint8_t* bytes, int64_t len, a
   std::unique_ptr<ipc::StreamReader> r;
   Status st = ipc::StreamReader::Open(s->session.get(), bytes, len, &r);
   if (!st.ok()) return Fail(s, st);
+  r->set_device_lz4(s->ipc_device_lz4 != 0, s->ipc_device_lz4_min_bytes);
   *out = new ahc_ipc_reader{s, std::move(r)};
   return 0;
 }
@@ -1074,6 +1085,8 @@ AHC_EXPORT int ahc_ipc_next(ahc_ipc_reader* r, ahc_datum** columns, int64_t* row
   return 0;
 }
 AHC_EXPORT int64_t ahc_ipc_bytes_uploaded(ahc_ipc_reader* r) { return r->r->body_bytes_uploaded(); }
+// so far: {bytes uploaded, compressed buffers inflated on the device, … on the host, … on the host after a device status}
+AHC_EXPORT void ahc_ipc_stats(ahc_ipc_reader* r, int64_t out[4]) { r->r->stats(out); }
 
 // Walks a stream without a device: "hex(name):type_id:nullable,…|rows,rows,…" into out (NUL-terminated), or
 // the error text with the status code returned — the parser's own test entry (runs where there is no GPU).

@@ -8,6 +8,8 @@
 #include <new>
 
 #include "../../include/arrowhip.h"
+#include "../csrc/ah_lz4.h"
+#include "lz4_frame.h"
 
 namespace arrowhip {
 namespace ipc {
@@ -77,6 +79,8 @@ Status NotImpl(const std::string& m) { return Status::Make(StatusCode::NotImplem
 // frame]; −1 means "stored as it is".  The reference decompresses with pierrec/lz4 and klauspost/zstd on the host; here
 // the system's liblz4.so.1 / libzstd.so.1 do it (bound at first use — the library has no link-time dependency on them),
 // into ONE host buffer laid out like an uncompressed body, which then takes the usual single transfer.
+// An LZ4_FRAME body whose frames consist of independent 64 KiB blocks (what the reference's writer produces) is instead uploaded
+// as it is and inflated in HBM: InflateOnDevice below.
 struct Codecs {
   // lz4frame.h
   size_t (*lz4f_create)(void**, unsigned) = nullptr;
@@ -130,6 +134,27 @@ Status DecompressBuffer(int codec, const uint8_t* src, int64_t srclen, uint8_t* 
   c.lz4f_free(dctx);
   if (st.ok() && out != dstlen) st = Invalid("LZ4 buffer decompresses to " + std::to_string(out) + " bytes, announced " + std::to_string(dstlen));
   return st;
+}
+
+// The device decoder's own text (csrc/ah_lz4.h) run on the host, its 64 lanes one after the other: the second opinion on a frame the
+// device reported as corrupt and liblz4 then inflated.  liblz4 up to 1.9 inflates a match offset of 0, which the block format forbids,
+// to zero bytes; a block is taken for corrupt here only if it is corrupt whatever its output length (each is decoded against the
+// frame's 64 KiB block maximum, so a length the plan guessed wrong is not held against it).
+struct LoopLanes {
+  template <class F>
+  void lanes(F&& f) { for (int lane = 0; lane < 64; lane++) f(lane, 64); }
+  void sync() {}
+  uint32_t uni(uint32_t x) { return x; }
+};
+bool FrameHasCorruptBlock(const uint8_t* frame, const std::vector<lz4::Block>& blocks) {
+  struct alignas(16) Work { uint8_t image[kLz4MaxBlock], out[kLz4MaxBlock], win[kLz4Window]; };
+  std::unique_ptr<Work> w(new Work);
+  LoopLanes par;
+  for (const lz4::Block& b : blocks) {
+    if (b.stored) continue;
+    if (ah_lz4_decode_block(par, frame + b.src_off, (uint32_t)b.src_len, false, w->out, kLz4MaxBlock, w->image, w->win) == AH_LZ4_CORRUPT) return true;
+  }
+  return false;
 }
 
 // one Field table → DataType (metadata.go: typeFromFB / intFromFB / floatFromFB)
@@ -334,6 +359,71 @@ Status StreamReader::Next(bool* have, std::vector<ArrayDataPtr>* columns, int64_
   }
 }
 
+// A compressed LZ4_FRAME body, at least one of whose buffers PlanFrame could take apart: the body is uploaded as it is, `dev` gets
+// the layout of an uncompressed body (every piece padded to 64 bytes, the padding zero), and ONE launch inflates the planned
+// frames block by block; stored buffers are device-to-device copies.  A frame that did not qualify, and a frame one of whose blocks came
+// back with a status, is inflated by DecompressBuffer as ever and uploaded into its slot: the device decoder never decides what is
+// an error.
+Status StreamReader::InflateOnDevice(const uint8_t* body, int64_t blen, const std::vector<DevicePiece>& pieces, int64_t total, BufferPtr* dev) {
+  BufferPtr comp;
+  std::vector<std::vector<uint8_t>> host_bytes;   // the pieces inflated here: alive until their uploads have run
+  const Status st = EnqueueInflate(body, blen, pieces, total, dev, &comp, &host_bytes);
+  const Status done = s_->FromStatus(ah_sync(s_->ctx()));   // on every path: nothing in flight reads memory this frame owns
+  return st.ok() ? done : st;
+}
+
+Status StreamReader::EnqueueInflate(const uint8_t* body, int64_t blen, const std::vector<DevicePiece>& pieces, int64_t total, BufferPtr* dev,
+                                    BufferPtr* comp_out, std::vector<std::vector<uint8_t>>* host_bytes_out) {
+  BufferPtr& comp = *comp_out;
+  std::vector<std::vector<uint8_t>>& host_bytes = *host_bytes_out;
+  AHC_RETURN_NOT_OK(s_->Allocate(blen, &comp, /*zero_all=*/false));
+  AHC_RETURN_NOT_OK(s_->FromStatus(ah_upload_async(s_->ctx(), comp->dptr, body, (size_t)blen)));
+  uploaded_ += blen;
+  AHC_RETURN_NOT_OK(s_->Allocate(total, dev));
+  uint8_t* out = (uint8_t*)(*dev)->dptr;
+  auto on_host = [&](const DevicePiece& p) -> Status {
+    host_bytes.emplace_back();
+    try { host_bytes.back().resize((size_t)p.dstlen); } catch (const std::bad_alloc&) { return Invalid("cannot hold a decompressed buffer of " + std::to_string(p.dstlen) + " bytes"); }
+    AHC_RETURN_NOT_OK(DecompressBuffer(kCodecLz4Frame, body + p.src, p.srclen, host_bytes.back().data(), p.dstlen));
+    AHC_RETURN_NOT_OK(s_->FromStatus(ah_upload_async(s_->ctx(), out + p.dst, host_bytes.back().data(), (size_t)p.dstlen)));
+    uploaded_ += p.dstlen;
+    return Status::OK();
+  };
+  constexpr int64_t kStored = (int64_t)1 << 62;   // a stored BLOCK inside a planned frame
+  std::vector<int64_t> table;
+  std::vector<size_t> owner;   // block → piece
+  for (size_t i = 0; i < pieces.size(); i++) {
+    const DevicePiece& p = pieces[i];
+    if (p.dstlen == 0) continue;
+    if (p.stored) {   // a plain device-to-device copy, on the compute stream like the decoder
+      AHC_RETURN_NOT_OK(s_->FromStatus(ah_copy_async(s_->ctx(), out + p.dst, (const uint8_t*)comp->dptr + p.src, (size_t)p.dstlen)));
+    } else if (p.planned) {
+      for (const lz4::Block& b : p.blocks) {
+        table.insert(table.end(), {p.src + b.src_off, b.src_len | (b.stored ? kStored : 0), p.dst + b.dst_off, b.dst_len});
+        owner.push_back(i);
+      }
+    } else {
+      AHC_RETURN_NOT_OK(on_host(p));
+      host_inflated_++;
+    }
+  }
+  std::vector<uint8_t> status(owner.size());
+  int64_t nbad = 0;
+  AHC_RETURN_NOT_OK(s_->FromStatus(ah_lz4_decompress_blocks(s_->ctx(), (const uint8_t*)comp->dptr, blen, out, total, table.data(), (int64_t)owner.size(),
+                                                            status.data(), &nbad)));
+  std::vector<bool> bad(pieces.size(), false);
+  for (size_t b = 0; b < owner.size(); b++) if (status[b]) bad[owner[b]] = true;
+  for (size_t i = 0; i < pieces.size(); i++) {
+    const DevicePiece& p = pieces[i];
+    if (p.dstlen == 0 || p.stored || !p.planned) continue;
+    if (!bad[i]) { device_inflated_++; continue; }
+    AHC_RETURN_NOT_OK(on_host(p));   // its error is the host path's error
+    if (FrameHasCorruptBlock(body + p.src, p.blocks)) return Invalid("corrupt LZ4 frame");   // (what liblz4 lets through: see there)
+    device_fallbacks_++;
+  }
+  return Status::OK();
+}
+
 Status StreamReader::LoadColumns(const uint8_t* meta, int64_t mlen, int64_t rb, const uint8_t* body, int64_t blen,
                                  const std::vector<FieldInfo>& fields_, bool as_values, std::vector<ArrayDataPtr>* columns, int64_t* rows) {
   const bool dry = columns == nullptr;  // validate the metadata against the body, move nothing
@@ -346,6 +436,8 @@ Status StreamReader::LoadColumns(const uint8_t* meta, int64_t mlen, int64_t rb, 
   // a compressed body is inflated on the host into the layout an uncompressed body has; (offset, length) pairs follow it
   std::vector<uint8_t> plain;
   std::vector<std::pair<int64_t, int64_t>> plain_bufs;
+  BufferPtr dev;
+  bool on_device = false;
   const int64_t comp = fb.indirect(rb, 3);
   if (comp) {
     const int codec = fb.scalar<int8_t>(comp, 0, 0), method = fb.scalar<int8_t>(comp, 1, 0);
@@ -375,21 +467,38 @@ Status StreamReader::LoadColumns(const uint8_t* meta, int64_t mlen, int64_t rb, 
       static const int64_t kMaxInflated = [] { const char* e = getenv("ARROWHIP_IPC_MAX_INFLATED_BYTES"); const long long v = e ? atoll(e) : 0; return v > 0 ? (int64_t)v : ((int64_t)16 << 30); }();
       if (total > kMaxInflated) return Invalid("decompressed body beyond " + std::to_string(kMaxInflated) + " bytes (ARROWHIP_IPC_MAX_INFLATED_BYTES)");
     }
-    try { plain.resize((size_t)total); } catch (const std::bad_alloc&) { return Invalid("cannot hold a decompressed body of " + std::to_string(total) + " bytes"); }
-    for (const Piece& p : pieces) {
-      if (p.dstlen == 0) { /* nothing */ }
-      else if (p.stored) std::memcpy(plain.data() + p.dst, body + p.src, (size_t)p.dstlen);
-      else AHC_RETURN_NOT_OK(DecompressBuffer(codec, body + p.src, p.srclen, plain.data() + p.dst, p.dstlen));
-      plain_bufs.push_back({p.dst, p.dstlen});
+    // LZ4 frames of independent blocks: the compressed body crosses the link and is inflated in HBM into the same layout
+    if (!dry && codec == kCodecLz4Frame && device_lz4_ && blen >= device_lz4_min_bytes_ && total > 0) {
+      std::vector<DevicePiece> dp;
+      bool any = false;
+      for (const Piece& p : pieces) {
+        DevicePiece d{p.src, p.srclen, p.dst, p.dstlen, p.stored, false, {}};
+        if (!p.stored && p.dstlen > 0) any |= d.planned = lz4::PlanFrame(body + p.src, p.srclen, p.dstlen, &d.blocks);
+        dp.push_back(std::move(d));
+      }
+      if (any) {
+        AHC_RETURN_NOT_OK(InflateOnDevice(body, blen, dp, total, &dev));
+        on_device = true;
+      }
     }
-    body = plain.data();
+    if (!on_device) {
+      try { plain.resize((size_t)total); } catch (const std::bad_alloc&) { return Invalid("cannot hold a decompressed body of " + std::to_string(total) + " bytes"); }
+      for (const Piece& p : pieces) {
+        if (p.dstlen == 0) { /* nothing */ }
+        else if (p.stored) std::memcpy(plain.data() + p.dst, body + p.src, (size_t)p.dstlen);
+        else { AHC_RETURN_NOT_OK(DecompressBuffer(codec, body + p.src, p.srclen, plain.data() + p.dst, p.dstlen)); host_inflated_++; }
+      }
+      body = plain.data();
+    } else {
+      body = nullptr;   // the plain bytes exist in HBM only
+    }
+    for (const Piece& p : pieces) plain_bufs.push_back({p.dst, p.dstlen});
     blen = total;
   }
 
   // the whole body in one transfer; columns are slices of it
-  BufferPtr dev;
-  if (!dry) AHC_RETURN_NOT_OK(s_->Allocate(blen, &dev));
-  if (!dry && blen > 0) {
+  if (!dry && !on_device) AHC_RETURN_NOT_OK(s_->Allocate(blen, &dev));
+  if (!dry && !on_device && blen > 0) {
     AHC_RETURN_NOT_OK(s_->FromStatus(ah_upload_async(s_->ctx(), dev->dptr, body, (size_t)blen)));
     AHC_RETURN_NOT_OK(s_->FromStatus(ah_sync(s_->ctx())));
     uploaded_ += blen;
@@ -463,10 +572,19 @@ Status StreamReader::LoadColumns(const uint8_t* meta, int64_t mlen, int64_t rb, 
       const int64_t ooff = off, olen = len;
       AHC_RETURN_NOT_OK(next_buffer(&off, &len));
       d->buffers[2] = slice(off, len);
-      if (olen > 0) {  // the body is still on the host: the first and last offset bound every device read of the data
+      if (olen > 0) {  // the first and last offset bound every device read of the data: from the host's body, or back from HBM
         int64_t first, last;
-        if (w == 4) { int32_t a, b; std::memcpy(&a, body + ooff, 4); std::memcpy(&b, body + ooff + flen * 4, 4); first = a; last = b; }
-        else { std::memcpy(&first, body + ooff, 8); std::memcpy(&last, body + ooff + flen * 8, 8); }
+        uint8_t ends[16];
+        if (on_device) {
+          AHC_RETURN_NOT_OK(s_->FromStatus(ah_download_async(s_->ctx(), ends, (const uint8_t*)dev->dptr + ooff, (size_t)w)));
+          AHC_RETURN_NOT_OK(s_->FromStatus(ah_download_async(s_->ctx(), ends + 8, (const uint8_t*)dev->dptr + ooff + flen * w, (size_t)w)));
+          AHC_RETURN_NOT_OK(s_->FromStatus(ah_sync(s_->ctx())));
+        } else {
+          std::memcpy(ends, body + ooff, (size_t)w);
+          std::memcpy(ends + 8, body + ooff + flen * w, (size_t)w);
+        }
+        if (w == 4) { int32_t a, b; std::memcpy(&a, ends, 4); std::memcpy(&b, ends + 8, 4); first = a; last = b; }
+        else { std::memcpy(&first, ends, 8); std::memcpy(&last, ends + 8, 8); }
         if (first < 0 || last < first || last > len) return Invalid("field '" + fi.name + "': offsets [" + std::to_string(first) + ", " + std::to_string(last) + "] do not fit the " + std::to_string(len) + "-byte data buffer");
       }
     } else {

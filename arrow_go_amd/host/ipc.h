@@ -12,7 +12,10 @@
 // Scope: flat columns of the types the kernels take — Int8..Uint64, Float32/64, Bool, Date32/64, Time32/64, Timestamp,
 // Duration, Utf8 / Binary and their Large variants, plain or dictionary-encoded (DictionaryBatch messages, replacement and delta);
 // little-endian; bodies uncompressed or compressed per buffer with LZ4_FRAME / ZSTD (ipc/compression.go: inflated on the host
-// by the system's liblz4 / libzstd into the layout of an uncompressed body, then the same single transfer).  Anything else is
+// by the system's liblz4 / libzstd into the layout of an uncompressed body, then the same single transfer; an LZ4_FRAME body whose
+// frames are made of independent 64 KiB blocks without checksums — lz4_frame.h decides frame by frame — is uploaded compressed and
+// inflated in HBM into that same layout by ah_lz4_decompress_blocks, with the host path as the fall-back of every frame that does
+// not qualify or that the device decoder reports a status for).  Anything else is
 // ErrNotImplemented with the field named.  The metadata is a FlatBuffer (format/Message.fbs,
 // Schema.fbs); it is read with the small bounds-checked accessor in ipc.cc — the bytes come from a
 // file or a socket and are not trusted.
@@ -23,6 +26,7 @@
 #include <vector>
 
 #include "arrowhip_compute.h"
+#include "lz4_frame.h"
 
 namespace arrowhip {
 namespace ipc {
@@ -45,12 +49,24 @@ class StreamReader {
   // columns == nullptr: only check the batch's metadata against its body (no session needed).
   Status Next(bool* have, std::vector<ArrayDataPtr>* columns, int64_t* rows);
   int64_t body_bytes_uploaded() const { return uploaded_; }
+  // LZ4_FRAME bodies of at least min_bytes compressed bytes are inflated in HBM where their frames allow it (session options
+  // ipc_device_lz4 / ipc_device_lz4_min_bytes); off: every compressed buffer is inflated on the host
+  void set_device_lz4(bool on, int64_t min_bytes) { device_lz4_ = on; device_lz4_min_bytes_ = min_bytes; }
+  // {bytes uploaded, buffers inflated on the device, buffers inflated on the host, buffers inflated on the host after a device status}
+  void stats(int64_t out[4]) const { out[0] = uploaded_; out[1] = device_inflated_; out[2] = host_inflated_; out[3] = device_fallbacks_; }
 
  private:
   Status NextMessage(bool* have, const uint8_t** meta, int64_t* meta_len, const uint8_t** body, int64_t* body_len);
   // one RecordBatch table (a record batch message, or the `data` of a dictionary batch) against its body
   Status LoadColumns(const uint8_t* meta, int64_t meta_len, int64_t rb, const uint8_t* body, int64_t body_len,
                      const std::vector<FieldInfo>& fields, bool as_values, std::vector<ArrayDataPtr>* columns, int64_t* rows);
+  // one buffer of a compressed body: [src, +srclen) of the body → [dst, +dstlen) of the plain layout; `blocks` if its frame was planned
+  struct DevicePiece { int64_t src, srclen, dst, dstlen; bool stored, planned; std::vector<lz4::Block> blocks; };
+  Status InflateOnDevice(const uint8_t* body, int64_t body_len, const std::vector<DevicePiece>& pieces, int64_t total, BufferPtr* dev);
+  Status EnqueueInflate(const uint8_t* body, int64_t body_len, const std::vector<DevicePiece>& pieces, int64_t total, BufferPtr* dev,
+                        BufferPtr* comp, std::vector<std::vector<uint8_t>>* host_bytes);
+  bool device_lz4_ = true;
+  int64_t device_lz4_min_bytes_ = 0, device_inflated_ = 0, host_inflated_ = 0, device_fallbacks_ = 0;
   std::map<int64_t, ArrayDataPtr> dicts_;   // dictionary id → values (dictutils.Memo)
   std::map<int64_t, bool> seen_dict_;
   Session* s_ = nullptr;

@@ -196,6 +196,24 @@ func (x *Context) HashMinMaxFloat64(keys, kvalid unsafe.Pointer, koff int64, val
 	return int64(ng), int32(nid), x.err(st)
 }
 
+// Lz4DecompressBlocks: independent LZ4 blocks of the device bytes src inflated into the device bytes dst (ah_lz4_decompress_blocks).
+// blocks holds 4 values per block {srcOff, srcLen (bit 62: stored), dstOff, dstLen ≤ 65536}, dstOff ascending; status receives one
+// byte per block (0 ok, 1 corrupt, 2 produced != dstLen) and nbad is the number of blocks with a status — those leave unspecified
+// bytes in their own output range only and are not an error of the call.
+func (x *Context) Lz4DecompressBlocks(src unsafe.Pointer, srcBytes int64, dst unsafe.Pointer, dstBytes int64, blocks []int64, status []byte) (nbad int64, err error) {
+	if len(blocks)%4 != 0 || len(status) < len(blocks)/4 {
+		return 0, fmt.Errorf("%w: lz4 block table of %d values with %d status bytes", arrow.ErrInvalid, len(blocks), len(status))
+	}
+	if len(blocks) == 0 {
+		return 0, nil
+	}
+	tb := (*C.int64_t)(unsafe.Pointer(&blocks[0]))
+	sb := (*C.uint8_t)(unsafe.Pointer(&status[0]))
+	var bad C.int64_t
+	st := C.ah_lz4_decompress_blocks(x.c, (*C.uint8_t)(src), C.int64_t(srcBytes), (*C.uint8_t)(dst), C.int64_t(dstBytes), tb, C.int64_t(len(blocks)/4), sb, &bad)
+	return int64(bad), x.err(st)
+}
+
 // HashPartition: partition id of every key by the reference's integer hash (internal/hashing/hash_funcs.go:60-67) — the owner
 // function of the C5 merge.
 func (x *Context) HashPartition(keys unsafe.Pointer, n int64, nparts int, outPart unsafe.Pointer) error {

@@ -495,6 +495,17 @@ int ah_hash_min_max_f64(ah_ctx* ctx, const uint64_t* keys, const uint8_t* kvalid
                         uint64_t* out_keys, double* out_mins, double* out_maxs, int64_t* out_counts,
                         int64_t* out_first_rows, int64_t* out_ngroups_host, int32_t* out_null_group_host);
 
+/* ---- LZ4 blocks inflated in HBM (NEW — no reference analogue: the reference inflates IPC bodies on the host, arrow/ipc/
+ * compression.go:25-72; definition in DESIGN.md §3.8) ----------------------------------------------------------------
+ * src / dst: device memory.  blocks_host: 4 int64 per block {src_off, src_len, dst_off, dst_len}; src_len bit 62 set = stored block
+ * (copy).  dst_len <= 65536.  Blocks are independent: a match never reaches in front of its own block's output.
+ * out_status_host (nullable, nblocks bytes): 0 ok, 1 corrupt, 2 produced != dst_len; *out_nbad_host (nullable): blocks with a status.
+ * A failed block leaves unspecified bytes inside its own dst range and touches nothing else; it is not an error of the call.
+ * AH_EINVALID before anything runs if a range lies outside src_bytes / dst_bytes, a dst_len is beyond 65536, or dst_off does not
+ * ascend without overlap.  Synchronises once. */
+int ah_lz4_decompress_blocks(ah_ctx* ctx, const uint8_t* src, int64_t src_bytes, uint8_t* dst, int64_t dst_bytes,
+                             const int64_t* blocks_host, int64_t nblocks, uint8_t* out_status_host, int64_t* out_nbad_host);
+
 /* ---- fused Compare(op scalar) → Filter(DropNulls) → Sum ------------------------------
  * NEW entry point (no reference analogue) computing in ONE pass what the reference
  * computes with "greater" → "array_filter" → math.Sum: Σ x[i] over valid slots with

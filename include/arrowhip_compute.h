@@ -246,6 +246,16 @@ int ahc_ipc_field(ahc_ipc_reader* r, int i, const char** name, int* type_id, int
 /* next record batch: `columns` receives ahc_ipc_num_fields() array datums; *rows = -1 at end of stream */
 int ahc_ipc_next(ahc_ipc_reader* r, ahc_datum** columns, int64_t* rows);
 int64_t ahc_ipc_bytes_uploaded(ahc_ipc_reader* r);
+/* A body compressed with LZ4_FRAME whose frames are made of independent 64 KiB blocks without checksums (what arrow-go's writer
+ * produces) is uploaded compressed and inflated in HBM; every other compressed buffer (ZSTD, linked blocks — Arrow C++ / pyarrow —,
+ * checksums, other block sizes), and any frame the device decoder reports a status for, is inflated on the host as before.
+ * ahc_session_set_option, read when a reader is opened: "ipc_device_lz4" (1; 0 = always the host), "ipc_device_lz4_min_bytes"
+ * (bodies of fewer compressed bytes stay on the host).
+ * One outcome depends on the path: liblz4 up to 1.9 inflates a match offset of 0, which the LZ4 block format forbids, to zero bytes.
+ * A frame with such a match is an error ("corrupt LZ4 frame") where the device path examined it, and reads as those zeros on the
+ * host path (option 0, a body below the minimum, a frame that does not qualify).  Every valid stream reads the same on both.
+ * out: {body bytes uploaded, compressed buffers inflated on the device, on the host, on the host after a device status} so far */
+void ahc_ipc_stats(ahc_ipc_reader* r, int64_t out[4]);
 /* walks a stream WITHOUT a device: "hex(name):type_id:nullable:hex(logical),…|rows,rows,…" into out (NUL-terminated),
  * or the error text with the status returned */
 int ahc_ipc_inspect(const uint8_t* bytes, int64_t len, char* out, int64_t cap);
