@@ -64,6 +64,7 @@ struct ah_ctx {
   int opt_encode_early_look;   // 1 (default): calls of ≥ 2^24 rows count the first 2^16 rows' distinct keys BEFORE the global table is set up (ah_encode_first_look); 0: the look that falls out of the staged inserts
   int opt_encode_part_min;     // auto: smallest expected distinct count that takes the partition-first path (ARROWHIP_ENCODE_PART_MIN)
   int opt_hash_direct;         // unique / dictionary_encode (ah_hash.hip): 0 ids in a separate pass, 1 direct ids, 2 + LDS / re-packed table (default), 3 no re-packed table (ARROWHIP_HASH_DIRECT)
+  int opt_hash_sum_partition;  // id-based group-by sum above 4096 groups (ah_hash_agg.hip): 1 (default) partition the (value, id) pairs by id and aggregate run by run in LDS, 0 plain device atomics (ARROWHIP_HASH_PARTITION)
   int opt_sort_msd;            // sort_indices: 0 LSD passes only, 1 auto (ARROWHIP_SORT_MSD)
   int opt_scan_segment_log2;   // cumulative_sum: bytes of input per segment (ARROWHIP_SCAN_SEGMENT_LOG2; 0 = one segment)
   void* expr_cache;        // compiled expression programs (ah_expr.hip)
@@ -171,16 +172,12 @@ void ah_expr_cache_free(ah_ctx* ctx);  // ah_expr.hip
 // internal (ah_arith.hip): the unchecked add / subtract / multiply of any shape — what the checked names are for floats
 int ah_arith_binary(ah_ctx* ctx, int type, int op, int shape, const void* l, const void* r, void* out, int64_t len);
 // internal (ah_sort.hip): stable radix partition of (value bits, group id) pairs for the group-by of
-// ah_hash.hip — by (id >> shift) & 255 (passes = 1) or by (id >> shift) & 65535 (passes = 2, LSD; alt_*
+// ah_hash_agg.hip — by (id >> shift) & 255 (passes = 1) or by (id >> shift) & 65535 (passes = 2, LSD; alt_*
 // is the intermediate buffer).  A row whose value is null (vvalid bit clear) travels with bit 31 of
 // its id set.  hist / offs: 256 · ceil(n / 2048) unsigned each.
 int ah_partition_by_group(ah_ctx* ctx, const int32_t* ids, const unsigned long long* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
                           int shift, int passes, unsigned* hist, unsigned* offs, unsigned long long* alt_vals, unsigned* alt_ids,
                           unsigned long long* out_vals, unsigned* out_ids);
-// internal (ah_hash_minmax.hip): per-group {min, max, count of valid values} over dense ids < ngroups, for the group-by of ah_hash.hip.
-// kind 0 / 1 / 2 = Uint64 / Int64 / Float64 order (NaNs counted, never a minimum or maximum).  Enqueued on the compute stream.
-int ah_group_min_max(ah_ctx* ctx, int kind, const int32_t* ids, const void* vals, const uint8_t* vvalid, int64_t voff, int64_t n, int64_t ngroups,
-                     void* out_mins, void* out_maxs, int64_t* out_counts);
 // internal (ah_sort_msd.hip): the `rest` range of sort_indices by two MSD partition passes + one wave per bucket; *used = 0: not
 // applicable or a bucket came out too large — the pairs are clobbered and the caller regenerates them for the LSD passes
 int ah_sort_rest_msd(ah_ctx* ctx, unsigned long long* keys, unsigned* rows, unsigned long long* alt_keys, unsigned* alt_rows, int64_t n,
@@ -210,6 +207,10 @@ int ah_sum_short_f64(ah_ctx* ctx, const void* buf, size_t len, void* res_dev);  
 // temporaries in the temp arena; *used says whether out_* hold the result
 int ah_encode_partitioned_try(ah_ctx* ctx, const uint64_t* keys, const uint8_t* valid, int64_t off, int64_t n, int encode_nulls, int lp, int slots,
                               int32_t* out_ids, uint64_t* out_dict, int64_t* out_first_rows, int64_t* out_ndict, int32_t* out_null_id, int* used);
+// internal (ah_hash.hip): the dense first-seen group ids of 8-byte keys for the id-based aggregates of ah_hash_agg.hip — dictionary_encode with
+// nulls encoded (the null key is a group) on the global-table path only (the partition-first encode would take the temp arena the caller's ids live in)
+int ah_encode_u64_groups(ah_ctx* ctx, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, int64_t n, int32_t* ids, uint64_t* out_keys,
+                         int64_t* out_first_rows, int64_t* out_ngroups, int32_t* out_null_group);
 // … and by two cuts, 64 parents × 2^(lp − 6) partitions (lp = 11 … 13) with LDS tables of `slots` = 4096 or 8192 entries
 // distinct valid keys among the first `rows` (≤ 2^16) rows, counted exactly without a table in HBM (ah_hash_part.hip): one launch, one polled wait
 int ah_encode_first_look(ah_ctx* ctx, const uint64_t* keys, const uint8_t* valid, int64_t off, int64_t rows, uint64_t* distinct);

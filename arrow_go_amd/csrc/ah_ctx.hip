@@ -43,6 +43,7 @@ static int ctx_init_common(ah_ctx* c) {
   c->opt_groupby_partition = env_int("ARROWHIP_GROUPBY_PARTITION", 1);
   c->opt_groupby_keys = env_int("ARROWHIP_GROUPBY_KEYS", 1280);
   c->opt_hash_direct = env_int("ARROWHIP_HASH_DIRECT", 2);
+  c->opt_hash_sum_partition = env_int("ARROWHIP_HASH_PARTITION", 1);
   c->opt_encode_partition = env_int("ARROWHIP_ENCODE_PARTITION", 1);
   c->opt_encode_part_min = env_int("ARROWHIP_ENCODE_PART_MIN", 300000);
   c->opt_encode_early_look = env_int("ARROWHIP_ENCODE_EARLY_LOOK", 1);
@@ -148,6 +149,7 @@ AH_EXPORT int ah_ctx_set_option(ah_ctx* c, const char* name, int64_t value) {
   else if (!strcmp(name, "groupby_partition")) c->opt_groupby_partition = (int)value;
   else if (!strcmp(name, "groupby_keys")) c->opt_groupby_keys = (int)value;
   else if (!strcmp(name, "hash_direct")) c->opt_hash_direct = (int)value;
+  else if (!strcmp(name, "hash_sum_partition")) c->opt_hash_sum_partition = (int)value;
   else if (!strcmp(name, "encode_partition")) c->opt_encode_partition = (int)value;
   else if (!strcmp(name, "encode_part_min")) c->opt_encode_part_min = (int)value;
   else if (!strcmp(name, "encode_early_look")) c->opt_encode_early_look = (int)value;

@@ -1,4 +1,4 @@
-// ah_hash.hip — unique / dictionary_encode / group-by-sum over 8-byte keys.
+// ah_hash.hip — unique / dictionary_encode over 8-byte and byte-string keys; the dense group ids of the id-based group-by (ah_hash_agg.hip).
 //
 // Replaces: doAppendNumeric[uint64] (kernels/vector_hash.go:359-385) driving
 //   hashing.Table[uint64].InsertOrGet / GetOrInsertNull
@@ -30,7 +30,6 @@
 //
 // HBM: 8 B/row of keys + random 16-byte slot traffic (atomics-bound at high
 // cardinality, cache-resident at low cardinality).
-#include <type_traits>
 #include "ah_common.h"
 #include "ah_hashing.h"
 #include "ah_bytes.h"
@@ -253,6 +252,58 @@ __global__ __launch_bounds__(kBlock) void emit_kernel(const Slot* __restrict__ t
   }
 }
 
+// ---- what the two cached-lookup kernels below share ------------------------------------------------------------
+// Both answer a row from a read-only copy of the ranked prefix's (key → id) pairs and fall back to the insert table for a key the
+// prefix did not hold.  Their load scheduling differs (and was measured); the rows the cache does not answer are handled here.
+constexpr unsigned kLookup = 0xFFFFFFFEu;   // (no id: ids and flagged slot numbers stay below it)
+struct InsertSide {   // what those kernels know of the insert table before their first row
+  uint64_t cap;
+  int encode_nulls;
+  unsigned ones_id, null_id;   // the two dedicated slots (all-ones key, null): final ids if the prefix saw them, else kNoRow
+  __device__ __forceinline__ InsertSide(const Slot* t, uint64_t cap_, int encode_nulls_)
+      : cap(cap_), encode_nulls(encode_nulls_), ones_id(t[cap_].first_row != kNoRow ? t[cap_].id : kNoRow),
+        null_id(t[cap_ + 1].first_row != kNoRow ? t[cap_ + 1].id : kNoRow) {}
+};
+
+// The claim loop: walk key k's probe chain in the insert table up to its slot, claiming the first empty one on the way.
+// → false: the chain is longer than `limit` (overflow flagged; the host retries with a larger table).
+__device__ __forceinline__ bool claim_slot(unsigned long long k, Slot* __restrict__ table, uint64_t mask, int limit, unsigned* __restrict__ overflow,
+                                           uint64_t* slot, unsigned* inserted) {
+  uint64_t s = hash_int(k) & mask;
+  int probes = 0;
+  for (;;) {
+    unsigned long long cur = table[s].key;
+    if (cur != k && cur == kEmpty) {
+      cur = atomicCAS(&table[s].key, kEmpty, k);
+      if (cur == kEmpty) { (*inserted)++; cur = k; }
+    }
+    if (cur == k) break;
+    s = (s + 1) & mask;
+    if (++probes > limit) { atomicExch(overflow, 1u); return false; }
+  }
+  *slot = s;
+  return true;
+}
+
+// A row of those kernels, in front of and behind the kernel's own cache lookup.  row_without_lookup: the row's final id — a masked
+// null (0), an encoded null or the all-ones key whose dedicated slot the prefix ranked —, kNoRow for a dedicated slot it did not rank
+// (*s), or kLookup: the kernel's cache decides.  miss_row, for a row whose id is still kNoRow: a key the cache did not hold (probe)
+// claims its slot in the insert table; the slot's first_row is lowered to this row, and the slot number, flagged with bit 31, is left
+// for emit_kernel.  → false: overflow (claim_slot), the kernel returns.
+__device__ __forceinline__ unsigned row_without_lookup(const InsertSide& t, bool ok, unsigned long long k, uint64_t* s) {
+  *s = ok ? t.cap : t.cap + 1;   // the dedicated slot, should the row need one
+  if (!ok) return t.encode_nulls ? t.null_id : 0u;  // masked null → index 0
+  return k == kEmpty ? t.ones_id : kLookup;
+}
+__device__ __forceinline__ bool miss_row(Slot* __restrict__ table, uint64_t mask, unsigned* __restrict__ overflow, unsigned long long k, int64_t i, bool probe,
+                                         uint64_t s, unsigned* fresh, unsigned* nmiss, unsigned* r) {
+  if (probe && !claim_slot(k, table, mask, kProbeLimit, overflow, &s, fresh)) return false;
+  if (table[s].first_row > (unsigned)i) atomicMin(&table[s].first_row, (unsigned)i);
+  *r = 0x80000000u | (unsigned)s;
+  (*nmiss)++;
+  return true;
+}
+
 // ---- low cardinality: the prefix's keys in LDS ---------------------------------------------------
 // When the 2^21-row prefix shows ≤ kSmallKeys distinct keys, their ids are already final (an id is the
 // number of first occurrences before the key's own, and all of those lie in the prefix too).  The
@@ -287,9 +338,7 @@ __global__ __launch_bounds__(kSmallBlock) void insert_small_kernel(const unsigne
   __shared__ unsigned l_ids[kSmallSlots];
   for (int j = threadIdx.x; j < kSmallSlots; j += kSmallBlock) { l_keys[j] = skeys[j]; l_ids[j] = sids[j]; }
   __syncthreads();
-  // the two dedicated slots (all-ones key, null): final ids if the prefix saw them
-  const unsigned ones_id = table[cap].first_row != kNoRow ? table[cap].id : kNoRow;
-  const unsigned null_id = table[cap + 1].first_row != kNoRow ? table[cap + 1].id : kNoRow;
+  const InsertSide side(table, cap, encode_nulls);
   const uint64_t mask = cap - 1;
   const int64_t stride = (int64_t)gridDim.x * kSmallBlock * kSmallRows;
   unsigned fresh = 0, nmiss = 0;
@@ -326,46 +375,26 @@ __global__ __launch_bounds__(kSmallBlock) void insert_small_kernel(const unsigne
     for (int u = 0; u < kSmallRows; u++) {
       const int64_t i = base + (int64_t)u * kSmallBlock;
       if (i >= hi) break;
-      unsigned r = kNoRow;       // final id, or kNoRow = "take the global path with slot s"
-      uint64_t s = 0;
+      uint64_t s;
       bool probe = false;
-      if (!ok[u]) {
-        if (!encode_nulls) r = 0;  // masked null → index 0
-        else { r = null_id; s = cap + 1; }
-      } else if (k[u] == kEmpty) {
-        r = ones_id; s = cap;
-      } else if (lk0[u] == k[u]) {
-        r = id0[u];
-      } else if (lk0[u] == kEmpty) {
-        probe = true;
-      } else {
-        unsigned j = (j0[u] + 1) & (kSmallSlots - 1);
-        for (;;) {
-          const unsigned long long lk = l_keys[j];
-          if (lk == k[u]) { r = l_ids[j]; break; }
-          if (lk == kEmpty) { probe = true; break; }
-          j = (j + 1) & (kSmallSlots - 1);
-        }
-      }
-      if (r == kNoRow) {
-        if (probe) {
-          s = hash_int(k[u]) & mask;
-          int probes = 0;
+      unsigned r = row_without_lookup(side, ok[u], k[u], &s);   // final id, or kNoRow = "take the insert table with slot s"
+      if (r == kLookup) {
+        r = kNoRow;
+        if (lk0[u] == k[u]) {
+          r = id0[u];
+        } else if (lk0[u] == kEmpty) {
+          probe = true;
+        } else {
+          unsigned j = (j0[u] + 1) & (kSmallSlots - 1);
           for (;;) {
-            unsigned long long cur = table[s].key;
-            if (cur != k[u] && cur == kEmpty) {
-              cur = atomicCAS(&table[s].key, kEmpty, k[u]);
-              if (cur == kEmpty) { fresh++; cur = k[u]; }
-            }
-            if (cur == k[u]) break;
-            s = (s + 1) & mask;
-            if (++probes > kProbeLimit) { atomicExch(overflow, 1u); return; }
+            const unsigned long long lk = l_keys[j];
+            if (lk == k[u]) { r = l_ids[j]; break; }
+            if (lk == kEmpty) { probe = true; break; }
+            j = (j + 1) & (kSmallSlots - 1);
           }
         }
-        if (table[s].first_row > (unsigned)i) atomicMin(&table[s].first_row, (unsigned)i);
-        r = 0x80000000u | (unsigned)s;
-        nmiss++;
       }
+      if (r == kNoRow && !miss_row(table, mask, overflow, k[u], i, probe, s, &fresh, &nmiss, &r)) return;
       if (out_ids) __builtin_nontemporal_store(r, &out_ids[i]);
     }
   }
@@ -402,8 +431,7 @@ __global__ __launch_bounds__(kBlock) void insert_compact_kernel(const unsigned l
                                                                  uint64_t cap, const CSlot* __restrict__ ctab, uint64_t cmask,
                                                                  unsigned* __restrict__ out_ids, unsigned long long* __restrict__ distinct,
                                                                  unsigned* __restrict__ overflow, unsigned long long* __restrict__ misses) {
-  const unsigned ones_id = table[cap].first_row != kNoRow ? table[cap].id : kNoRow;
-  const unsigned null_id = table[cap + 1].first_row != kNoRow ? table[cap + 1].id : kNoRow;
+  const InsertSide side(table, cap, encode_nulls);
   const uint64_t mask = cap - 1;
   const int64_t stride = (int64_t)gridDim.x * kBlock * kCompactRows;
   unsigned fresh = 0, nmiss = 0;
@@ -423,15 +451,11 @@ __global__ __launch_bounds__(kBlock) void insert_compact_kernel(const unsigned l
     for (int u = 0; u < kCompactRows; u++) {
       const int64_t i = base + (int64_t)u * kBlock;
       if (i >= hi) break;
-      unsigned r = kNoRow;  // final id, or kNoRow = "take the insert table with slot s"
-      uint64_t s = 0;
+      uint64_t s;
       bool probe = false;
-      if (!ok[u]) {
-        if (!encode_nulls) r = 0;  // masked null → index 0
-        else { r = null_id; s = cap + 1; }
-      } else if (k[u] == kEmpty) {
-        r = ones_id; s = cap;
-      } else {
+      unsigned r = row_without_lookup(side, ok[u], k[u], &s);   // final id, or kNoRow = "take the insert table with slot s"
+      if (r == kLookup) {
+        r = kNoRow;
         uint64_t j = hash_int(k[u]) & cmask;
         uint4 c = cs[u];
         for (;;) {
@@ -442,222 +466,12 @@ __global__ __launch_bounds__(kBlock) void insert_compact_kernel(const unsigned l
           c = *reinterpret_cast<const uint4*>(&ctab[j]);
         }
       }
-      if (r == kNoRow) {
-        if (probe) {
-          s = hash_int(k[u]) & mask;
-          int probes = 0;
-          for (;;) {
-            unsigned long long cur = table[s].key;
-            if (cur != k[u] && cur == kEmpty) {
-              cur = atomicCAS(&table[s].key, kEmpty, k[u]);
-              if (cur == kEmpty) { fresh++; cur = k[u]; }
-            }
-            if (cur == k[u]) break;
-            s = (s + 1) & mask;
-            if (++probes > kProbeLimit) { atomicExch(overflow, 1u); return; }
-          }
-        }
-        if (table[s].first_row > (unsigned)i) atomicMin(&table[s].first_row, (unsigned)i);
-        r = 0x80000000u | (unsigned)s;
-        nmiss++;
-      }
+      if (r == kNoRow && !miss_row(table, mask, overflow, k[u], i, probe, s, &fresh, &nmiss, &r)) return;
       if (out_ids) __builtin_nontemporal_store(r, &out_ids[i]);
     }
   }
   if (fresh) atomicAdd(distinct, (unsigned long long)fresh);
   if (nmiss) atomicAdd(misses, (unsigned long long)nmiss);
-}
-
-// Per-group accumulation.  ids are dense and in first-seen order, so a low-cardinality
-// column keeps ALL its groups in a per-workgroup LDS table (kLdsGroups × {sum, count}):
-// rows hit LDS atomics, and each workgroup flushes every touched group to HBM once —
-// instead of two same-address global atomics per row (~12 ns each, serialised at L2),
-// which is what made 2^10 groups 20× slower than 2^16 before.
-constexpr int kLdsGroups = 4096;
-
-template <typename VT, typename AT, bool USE_LDS>
-__global__ __launch_bounds__(kBlock) void group_sum_kernel(const int32_t* __restrict__ ids, const VT* __restrict__ vals,
-                                                            const uint8_t* __restrict__ vvalid, int64_t voff, int64_t n,
-                                                            AT* __restrict__ sums, unsigned long long* __restrict__ counts, int ngroups, FxAcc fx) {
-  constexpr bool kFx = std::is_same<VT, double>::value;   // doubles: 128-bit fixed point (s_sum = low words, s_hi = high words)
-  __shared__ unsigned long long s_sum[USE_LDS ? kLdsGroups : 1];
-  __shared__ unsigned long long s_hi[USE_LDS && kFx ? kLdsGroups : 1];
-  __shared__ unsigned s_cnt[USE_LDS ? kLdsGroups : 1];
-  const int nl = ngroups < kLdsGroups ? ngroups : kLdsGroups;
-  if (USE_LDS) {
-    for (int g = threadIdx.x; g < nl; g += kBlock) { s_sum[g] = 0; s_cnt[g] = 0; if (kFx) s_hi[g] = 0; }
-    __syncthreads();
-  }
-  int sh = 0;
-  if constexpr (kFx) sh = fx_shift(*fx.absmax);   // wide columns (fx.gmax): the group's own scale, looked up per row below
-  constexpr int U = 8;  // rows per lane per step: 8 id loads + 8 value loads in flight (one row at a time is latency-bound)
-  const int64_t stride = (int64_t)gridDim.x * kBlock * U;
-  for (int64_t base = (int64_t)blockIdx.x * kBlock * U + threadIdx.x; base < n; base += stride) {
-    int32_t g[U];
-    VT v[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int64_t i = base + (int64_t)u * kBlock;
-      const bool ok = i < n && ah_bit(vvalid, voff + i);
-      g[u] = ok ? __builtin_nontemporal_load(&ids[i]) : -1;
-      v[u] = ok ? __builtin_nontemporal_load(&vals[i]) : (VT)0;
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      if (g[u] < 0) continue;
-      const bool lds = USE_LDS && g[u] < nl;
-      if constexpr (kFx) {
-        if (fx_finite(v[u])) {
-          unsigned long long lo, hi;
-          fx_split(v[u], fx.gmax ? fx_shift(fx.gmax[g[u]]) : sh, &lo, &hi);
-          if (lds) fx_add(s_sum, s_hi, (size_t)g[u], lo, hi);
-          else fx_add(fx.lo, fx.hi, (size_t)g[u], lo, hi);
-        } else {
-          atomicOr(&fx.flags[g[u]], fx_flag(v[u]));
-        }
-      } else {
-        if (lds) atomicAdd(&s_sum[g[u]], (unsigned long long)v[u]);
-        else atomicAdd(&sums[g[u]], (AT)v[u]);
-      }
-      if (lds) atomicAdd(&s_cnt[g[u]], 1u);
-      else atomicAdd(&counts[g[u]], 1ull);
-    }
-  }
-  if (USE_LDS) {
-    __syncthreads();
-    for (int g = threadIdx.x; g < nl; g += kBlock) {
-      unsigned cnt = s_cnt[g];
-      if (cnt) {
-        if constexpr (kFx) fx_add(fx.lo, fx.hi, (size_t)g, s_sum[g], s_hi[g]);
-        else atomicAdd(&sums[g], (AT)s_sum[g]);
-        atomicAdd(&counts[g], (unsigned long long)cnt);
-      }
-    }
-  }
-}
-
-// wide columns (ah_hashing.h): largest finite |x| per group = the group's fixed-point scale.  A look before the atomic: once a
-// group's maximum has been seen (early, on average) its rows issue none.
-__global__ __launch_bounds__(kBlock) void group_max_kernel(const int32_t* __restrict__ ids, const unsigned long long* __restrict__ vals,
-                                                            const uint8_t* __restrict__ vvalid, int64_t voff, int64_t n,
-                                                            unsigned long long* __restrict__ gmax) {
-  constexpr int U = 8;
-  const int64_t stride = (int64_t)gridDim.x * kBlock * U;
-  for (int64_t base = (int64_t)blockIdx.x * kBlock * U + threadIdx.x; base < n; base += stride) {
-    int32_t g[U];
-    unsigned long long a[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int64_t i = base + (int64_t)u * kBlock;
-      const bool ok = i < n && ah_bit(vvalid, voff + i);
-      g[u] = ok ? __builtin_nontemporal_load(&ids[i]) : -1;
-      a[u] = ok ? __builtin_nontemporal_load(&vals[i]) & 0x7fffffffffffffffull : 0ull;
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      if (g[u] < 0 || (a[u] >> 52) == 0x7ff || a[u] == 0) continue;
-      if (__hip_atomic_load(&gmax[g[u]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a[u]) atomicMax(&gmax[g[u]], a[u]);
-    }
-  }
-}
-
-// Above 4 Ki groups LDS cannot hold all groups, and two global atomics per row run at ≈ 25 G atomics/s
-// device-wide (5.4 ms for 2^26 rows, whatever the number of copies of the sums — measured).  So the
-// (value, group id) pairs are first partitioned by id >> 12 with ah_sort.hip's stable radix kernels — one
-// 256-way pass up to 1 Mi groups, two passes (65 536 windows) up to 256 Mi — which makes every 64 Ki-row
-// chunk a short sequence of runs, each inside one 4096-group window.  A workgroup walks the runs of its
-// chunk: aggregate the run in LDS, flush the groups it touched (consecutive addresses), next run.
-constexpr int kBucketShift = 12;                     // log2(kLdsGroups)
-constexpr int64_t kPartitionOnePass = 1 << 20;       // 256 windows of 4096 groups
-constexpr int64_t kPartitionMaxGroups = 1ll << 28;   // 65 536 windows
-constexpr int64_t kChunkRows = 1 << 16;
-constexpr int64_t kShortRun = 1024;                  // runs shorter than this go straight to global atomics
-
-template <typename AT>
-__global__ __launch_bounds__(kBlock) void bucket_sum_kernel(const unsigned long long* __restrict__ vals, const unsigned* __restrict__ ids, int64_t n,
-                                                             AT* __restrict__ sums, unsigned long long* __restrict__ counts, FxAcc fx) {
-  constexpr bool kFx = std::is_same<AT, double>::value;
-  __shared__ unsigned long long s_sum[kLdsGroups];
-  __shared__ unsigned long long s_hi[kFx ? kLdsGroups : 1];
-  __shared__ unsigned s_cnt[kLdsGroups];
-  int sh = 0;
-  if constexpr (kFx) sh = fx_shift(*fx.absmax);
-  // one row into the LDS window (base = nullptr) or straight into the global accumulators
-  auto add_row = [&](unsigned id, unsigned long long bits, bool lds) {
-    const size_t g = lds ? (size_t)(id & (kLdsGroups - 1)) : (size_t)id;
-    if constexpr (kFx) {
-      const double x = __builtin_bit_cast(double, bits);
-      if (fx_finite(x)) {
-        unsigned long long lo, hi;
-        fx_split(x, sh, &lo, &hi);
-        if (lds) fx_add(s_sum, s_hi, g, lo, hi);
-        else fx_add(fx.lo, fx.hi, g, lo, hi);
-      } else {
-        atomicOr(&fx.flags[id], fx_flag(x));
-      }
-    } else {
-      if (lds) atomicAdd(&s_sum[g], bits);
-      else atomicAdd(&sums[g], (AT)bits);
-    }
-    if (lds) atomicAdd(&s_cnt[g], 1u);
-    else atomicAdd(&counts[g], 1ull);
-  };
-  const int64_t lo = (int64_t)blockIdx.x * kChunkRows, hi = lo + kChunkRows < n ? lo + kChunkRows : n;
-  int64_t pos = lo;
-  while (pos < hi) {
-    const unsigned bucket = (ids[pos] & 0x7fffffffu) >> kBucketShift;
-    // end of this window's run inside the chunk (rows are ordered by window): 256-ary search, every
-    // thread probes one sample per round, the samples still inside the window form a prefix
-    int64_t a = pos, span = hi - pos;
-    while (span > 1) {
-      const int64_t step = (span + kBlock - 1) / kBlock;
-      const int64_t idx = a + (int64_t)threadIdx.x * step;
-      const bool inside = idx < a + span && ((ids[idx] & 0x7fffffffu) >> kBucketShift) == bucket;
-      const int cnt = __syncthreads_count(inside);  // ≥ 1: the sample of thread 0 is row a
-      const int64_t lim = a + span;
-      a += (int64_t)(cnt - 1) * step;
-      span = lim - a < step ? lim - a : step;
-    }
-    const int64_t end = a + 1;
-    if (end - pos < kShortRun) {
-      for (int64_t i = pos + threadIdx.x; i < end; i += kBlock) {
-        const unsigned id = ids[i];
-        if (id & 0x80000000u) continue;  // null value: neither summed nor counted
-        add_row(id, vals[i], false);
-      }
-    } else {
-      for (int g = threadIdx.x; g < kLdsGroups; g += kBlock) { s_sum[g] = 0; s_cnt[g] = 0; if (kFx) s_hi[g] = 0; }
-      __syncthreads();
-      constexpr int U = 4;
-      for (int64_t b0 = pos + threadIdx.x; b0 < end; b0 += (int64_t)kBlock * U) {
-        unsigned id[U];
-        unsigned long long v[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-          const int64_t i = b0 + (int64_t)u * kBlock;
-          id[u] = i < end ? __builtin_nontemporal_load(&ids[i]) : 0x80000000u;
-          v[u] = i < end ? __builtin_nontemporal_load(&vals[i]) : 0ull;
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-          if (id[u] & 0x80000000u) continue;  // null value (or past the run)
-          add_row(id[u], v[u], true);
-        }
-      }
-      __syncthreads();
-      for (int g = threadIdx.x; g < kLdsGroups; g += kBlock) {
-        const unsigned cnt = s_cnt[g];
-        if (cnt) {
-          const size_t gg = ((size_t)bucket << kBucketShift) + g;
-          if constexpr (kFx) fx_add(fx.lo, fx.hi, gg, s_sum[g], s_hi[g]);
-          else atomicAdd(&sums[gg], (AT)s_sum[g]);
-          atomicAdd(&counts[gg], (unsigned long long)cnt);
-        }
-      }
-      __syncthreads();
-    }
-    pos = end;
-  }
 }
 
 static uint64_t next_pow2_u64(uint64_t x) {
@@ -977,152 +791,35 @@ int encode_core(ah_ctx* c, const K keys, const uint8_t* valid, int64_t off, int6
   }
 }
 
-template <typename VT, typename AT>
-int hash_sum(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, const VT* vals, const uint8_t* vvalid,
-             int64_t voff, int64_t n, uint64_t* out_keys, AT* out_sums, int64_t* out_counts, int64_t* out_first_rows,
-             int64_t* out_ngroups_host, int32_t* out_null_group_host) {
-  if (n < 0 || koff < 0 || voff < 0) return ah_fail(c, AH_EINVALID, "hash_sum: negative length/offset");
-  if (out_ngroups_host) *out_ngroups_host = 0;
-  if (out_null_group_host) *out_null_group_host = -1;
-  if (n == 0) return AH_OK;
-  if (!keys || !vals || !out_keys || !out_sums || !out_counts) return ah_fail(c, AH_EINVALID, "hash_sum: null buffer");
-  if (sizeof(VT) == 8) {
-    // large inputs with up to ~10^6 groups: cut the rows by key hash first, aggregate each partition in LDS (ah_groupby.hip)
-    int used = 0;
-    int64_t ng = 0;
-    int32_t nullg = -1;
-    int prc = ah_groupby_partitioned_try(c, std::is_same<VT, double>::value ? 1 : 0, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums,
-                                         out_counts, out_first_rows, &ng, &nullg, &used);
-    if (prc != AH_OK) return prc;
-    if (used) {
-      if (out_ngroups_host) *out_ngroups_host = ng;
-      if (out_null_group_host) *out_null_group_host = nullg;
-      return AH_OK;
-    }
-  }
-  // temporaries: a dense group id per row and, above 4096 groups, the partitioned (value, id) pairs with their
-  // histograms — one reservation in the context's temp arena, sized for the two-pass partition, reused by the next call
-  const int64_t nb = ah_ceil_div(n, 2048);
-  const size_t pv = (size_t)n * 8, pi = (((size_t)n * 4) + 255) & ~(size_t)255, ph = (size_t)256 * nb * 4;
-  constexpr bool kFx = std::is_same<VT, double>::value;
-  // doubles: 128-bit fixed-point accumulators + flag word per group (≤ n + 1 groups) and the absmax word
-  const size_t fxw = kFx ? (((size_t)(n + 1) * 8) + 255) & ~(size_t)255 : 0, fxf = kFx ? (((size_t)(n + 1) * 4) + 255) & ~(size_t)255 : 0;
-  void* arena = nullptr;
-  int rc = ah_temp_reserve(c, pi + 2 * (pv + pi) + 2 * ph + 256 + 2 * fxw + fxf + 256, &arena);
-  if (rc != AH_OK) return rc;
-  int32_t* ids = (int32_t*)arena;
-  uint8_t* part = (uint8_t*)arena + pi;
-  uint8_t* fxbase = part + 2 * (pv + pi) + 2 * ph + 256;
-  FxAcc fx{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (kFx) {
-    fx = FxAcc{(unsigned long long*)fxbase, (unsigned long long*)(fxbase + fxw), (unsigned*)(fxbase + 2 * fxw),
-               (const unsigned long long*)(fxbase + 2 * fxw + fxf), nullptr};
-    AH_HIP(c, hipMemsetAsync((void*)fx.absmax, 0, 16, c->stream));
-    absmax_kernel<<<ah_stream_grid(c, ah_ceil_div(n, (int64_t)kBlock * 8), 2), kBlock, 0, c->stream>>>((const unsigned long long*)vals, vvalid, voff, n,
-                                                                                                        (unsigned long long*)fx.absmax);
-    AH_LAUNCH_CHECK(c);
-  }
-  EncodeResult res;
-  rc = encode_core(c, U64Keys{(const unsigned long long*)keys}, kvalid, koff, n, /*encode_nulls=*/1, ids, out_keys, &res, out_first_rows, /*allow_partitioned=*/false);
-  if (rc == AH_OK) {
-    hipError_t e1 = hipMemsetAsync(out_sums, 0, (size_t)res.ndict * sizeof(AT), c->stream);
-    hipError_t e2 = hipMemsetAsync(out_counts, 0, (size_t)res.ndict * sizeof(int64_t), c->stream);
-    if (kFx && e1 == hipSuccess) e1 = hipMemsetAsync(fx.lo, 0, (size_t)res.ndict * 8, c->stream);
-    if (kFx && e1 == hipSuccess) e1 = hipMemsetAsync(fx.hi, 0, (size_t)res.ndict * 8, c->stream);
-    if (kFx && e1 == hipSuccess) e1 = hipMemsetAsync(fx.flags, 0, (size_t)res.ndict * 4, c->stream);
-    if (e1 != hipSuccess || e2 != hipSuccess) rc = ah_fail(c, AH_EHIP, "hash_sum: memset failed");
-  }
-  bool wide = false;
-  if (kFx && rc == AH_OK) {
-    // one scale for the call, or one per group?  (ah_hashing.h: a column spanning more than 42 binades)
-    hipError_t e = hipMemcpyAsync(&c->pinned[2], fx.absmax, 16, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) rc = ah_fail(c, AH_EHIP, "hash_sum: range read-back failed");
-    else wide = fx_wide(*(volatile uint64_t*)&c->pinned[2], *(volatile uint64_t*)&c->pinned[3]);
-    if (rc == AH_OK && wide) {
-      unsigned long long* gmax = (unsigned long long*)part;   // the partition temporaries are idle on this route
-      if (hipMemsetAsync(gmax, 0, (size_t)res.ndict * 8, c->stream) != hipSuccess) rc = ah_fail(c, AH_EHIP, "hash_sum: memset failed");
-      if (rc == AH_OK) {
-        group_max_kernel<<<ah_stream_grid(c, ah_ceil_div(n, (int64_t)kBlock * 8)), kBlock, 0, c->stream>>>(ids, (const unsigned long long*)vals, vvalid, voff, n, gmax);
-        if (hipGetLastError() != hipSuccess) rc = ah_fail(c, AH_EHIP, "hash_sum: launch failed");
-      }
-      fx.gmax = gmax;
-    }
-  }
-  if (rc == AH_OK) {
-    static const int partition_path = getenv("ARROWHIP_HASH_PARTITION") ? atoi(getenv("ARROWHIP_HASH_PARTITION")) : 1;
-    if (res.ndict <= kLdsGroups) {
-      unsigned grid = ah_stream_grid(c, ah_ceil_div(n, (int64_t)kBlock * 8), /*default_bpc=*/2);
-      group_sum_kernel<VT, AT, true><<<grid, kBlock, 0, c->stream>>>(ids, vals, vvalid, voff, n, out_sums,
-                                                                     (unsigned long long*)out_counts, (int)res.ndict, fx);
-    } else if (partition_path && !wide && res.ndict <= kPartitionMaxGroups && sizeof(VT) == 8) {
-      const int passes = res.ndict <= kPartitionOnePass ? 1 : 2;
-      unsigned long long* pvals = (unsigned long long*)part;
-      unsigned* pids = (unsigned*)(part + pv);
-      unsigned* hist = (unsigned*)(part + pv + pi);
-      unsigned* offs = (unsigned*)(part + pv + pi + ph);
-      unsigned long long* avals = passes == 2 ? (unsigned long long*)(part + pv + pi + 2 * ph) : nullptr;
-      unsigned* aids = passes == 2 ? (unsigned*)((uint8_t*)avals + pv) : nullptr;
-      rc = ah_partition_by_group(c, ids, (const unsigned long long*)vals, vvalid, voff, n, kBucketShift, passes, hist, offs, avals, aids, pvals, pids);
-      if (rc == AH_OK) {
-        bucket_sum_kernel<AT><<<(unsigned)ah_ceil_div(n, kChunkRows), kBlock, 0, c->stream>>>(pvals, pids, n, out_sums, (unsigned long long*)out_counts, fx);
-        if (hipGetLastError() != hipSuccess) rc = ah_fail(c, AH_EHIP, "hash_sum: launch failed");
-      }
-    } else {
-      unsigned grid = ah_stream_grid(c, ah_ceil_div(n, (int64_t)kBlock * 8));
-      group_sum_kernel<VT, AT, false><<<grid, kBlock, 0, c->stream>>>(ids, vals, vvalid, voff, n, out_sums,
-                                                                      (unsigned long long*)out_counts, (int)(res.ndict > 0x7fffffff ? 0x7fffffff : res.ndict), fx);
-    }
-    if (hipGetLastError() != hipSuccess) rc = ah_fail(c, AH_EHIP, "hash_sum: launch failed");
-    if constexpr (kFx) {
-      if (rc == AH_OK && res.ndict > 0) {
-        fx_finalize_kernel<<<(unsigned)ah_ceil_div(res.ndict, kBlock), kBlock, 0, c->stream>>>(fx, res.ndict, (double*)out_sums);
-        if (hipGetLastError() != hipSuccess) rc = ah_fail(c, AH_EHIP, "hash_sum: launch failed");
-      }
-    }
-  }
-  if (rc != AH_OK) return rc;
-  if (out_ngroups_host) *out_ngroups_host = res.ndict;
-  if (out_null_group_host) *out_null_group_host = res.null_id;
-  return AH_OK;
-}
-
-// group-by min / max: the same groups as hash_sum (ids from encode_core), the aggregate in ah_hash_minmax.hip
-int hash_min_max(ah_ctx* c, int kind, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, const void* vals, const uint8_t* vvalid,
-                 int64_t voff, int64_t n, uint64_t* out_keys, void* out_mins, void* out_maxs, int64_t* out_counts, int64_t* out_first_rows,
-                 int64_t* out_ngroups_host, int32_t* out_null_group_host) {
-  if (n < 0 || koff < 0 || voff < 0) return ah_fail(c, AH_EINVALID, "hash_min_max: negative length/offset");
-  if (out_ngroups_host) *out_ngroups_host = 0;
-  if (out_null_group_host) *out_null_group_host = -1;
-  if (n == 0) return AH_OK;
-  if (!keys || !vals || !out_keys || !out_mins || !out_maxs || !out_counts) return ah_fail(c, AH_EINVALID, "hash_min_max: null buffer");
-  // the one temporary: a dense group id per row, in the context's temp arena (encode_core stays out of it: allow_partitioned = false)
-  void* arena = nullptr;
-  int rc = ah_temp_reserve(c, ah_pad((size_t)n * 4), &arena);
-  if (rc != AH_OK) return rc;
-  int32_t* ids = (int32_t*)arena;
-  EncodeResult res;
-  rc = encode_core(c, U64Keys{(const unsigned long long*)keys}, kvalid, koff, n, /*encode_nulls=*/1, ids, out_keys, &res, out_first_rows, /*allow_partitioned=*/false);
-  if (rc != AH_OK) return rc;
-  if ((rc = ah_group_min_max(c, kind, ids, vals, vvalid, voff, n, res.ndict, out_mins, out_maxs, out_counts)) != AH_OK) return rc;
-  if (out_ngroups_host) *out_ngroups_host = res.ndict;
-  if (out_null_group_host) *out_null_group_host = res.null_id;
-  return AH_OK;
-}
-
 }  // namespace
 
-static int ids_validity(ah_ctx* c, const uint8_t* valid, int64_t off, int64_t n, int encode_nulls, uint8_t* out_ids_valid) {
-  // indices validity: all set when nulls are encoded (or there is no validity);
-  // otherwise the input validity (NullEncodingMask, vector_hash.go:224-230)
-  // the bitmap is this call's to define up to its last byte: the bits behind row n − 1 are zero (ah_copy_bitmap and ah_set_bits_to keep
-  // what lies outside their range — right for an executor's slice, wrong for a fresh output whose memory held something else before)
-  int rc;
-  AH_HIP(c, hipMemsetAsync(out_ids_valid, 0, (size_t)((n + 7) / 8), c->stream));
-  if (valid && !encode_nulls) rc = ah_copy_bitmap(c, valid, off, n, out_ids_valid, 0, 0);
-  else rc = ah_set_bits_to(c, out_ids_valid, 0, n, 1);
+// the ids of the id-based group-by (ah_hash_agg.hip): nulls are a group, and the partition-first encode is not tried — the caller's own
+// temporaries live in the arena that path would take
+int ah_encode_u64_groups(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, int64_t n, int32_t* ids, uint64_t* out_keys,
+                         int64_t* out_first_rows, int64_t* out_ngroups, int32_t* out_null_group) {
+  EncodeResult res;
+  int rc = encode_core(c, U64Keys{(const unsigned long long*)keys}, kvalid, koff, n, /*encode_nulls=*/1, ids, out_keys, &res, out_first_rows, /*allow_partitioned=*/false);
   if (rc != AH_OK) return rc;
-  AH_HIP(c, hipStreamSynchronize(c->stream));
+  *out_ngroups = res.ndict;
+  *out_null_group = res.null_id;
+  return AH_OK;
+}
+
+// what the three encode exports end with: the validity of the indices, then the sizes
+static int encode_finish(ah_ctx* c, const EncodeResult& res, const uint8_t* valid, int64_t off, int64_t n, int encode_nulls, uint8_t* out_ids_valid,
+                         int64_t* out_ndict_host, int32_t* out_null_id_host) {
+  if (out_ids_valid) {
+    // indices validity: all set when nulls are encoded (or there is no validity);
+    // otherwise the input validity (NullEncodingMask, vector_hash.go:224-230)
+    // the bitmap is this call's to define up to its last byte: the bits behind row n − 1 are zero (ah_copy_bitmap and ah_set_bits_to keep
+    // what lies outside their range — right for an executor's slice, wrong for a fresh output whose memory held something else before)
+    AH_HIP(c, hipMemsetAsync(out_ids_valid, 0, (size_t)((n + 7) / 8), c->stream));
+    int rc = valid && !encode_nulls ? ah_copy_bitmap(c, valid, off, n, out_ids_valid, 0, 0) : ah_set_bits_to(c, out_ids_valid, 0, n, 1);
+    if (rc != AH_OK) return rc;
+    AH_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  if (out_ndict_host) *out_ndict_host = res.ndict;
+  if (out_null_id_host) *out_null_id_host = res.null_id;
   return AH_OK;
 }
 
@@ -1142,10 +839,7 @@ AH_EXPORT int ah_hash_binary_encode(ah_ctx* c, int offset_width, const void* off
                ? encode_core(c, ByteKeys<4>{byte_rows(4, offsets, data, 0, off)}, valid, off, n, encode_nulls, out_ids, nullptr, &res, out_first_rows)
                : encode_core(c, ByteKeys<8>{byte_rows(8, offsets, data, 0, off)}, valid, off, n, encode_nulls, out_ids, nullptr, &res, out_first_rows);
   if (rc != AH_OK) return rc;
-  if (out_ids_valid && (rc = ids_validity(c, valid, off, n, encode_nulls, out_ids_valid)) != AH_OK) return rc;
-  if (out_ndict_host) *out_ndict_host = res.ndict;
-  if (out_null_id_host) *out_null_id_host = res.null_id;
-  return AH_OK;
+  return encode_finish(c, res, valid, off, n, encode_nulls, out_ids_valid, out_ndict_host, out_null_id_host);
 }
 
 AH_EXPORT int ah_hash_fixed_encode(ah_ctx* c, int byte_width, const uint8_t* data, const uint8_t* valid, int64_t off, int64_t n, int encode_nulls,
@@ -1167,10 +861,7 @@ AH_EXPORT int ah_hash_fixed_encode(ah_ctx* c, int byte_width, const uint8_t* dat
     AH_LAUNCH_CHECK(c);
     AH_HIP(c, hipStreamSynchronize(c->stream));
   }
-  if (out_ids_valid && (rc = ids_validity(c, valid, off, n, encode_nulls, out_ids_valid)) != AH_OK) return rc;
-  if (out_ndict_host) *out_ndict_host = res.ndict;
-  if (out_null_id_host) *out_null_id_host = res.null_id;
-  return AH_OK;
+  return encode_finish(c, res, valid, off, n, encode_nulls, out_ids_valid, out_ndict_host, out_null_id_host);
 }
 
 AH_EXPORT int ah_hash_u64_encode(ah_ctx* c, const uint64_t* keys, const uint8_t* valid, int64_t off, int64_t n,
@@ -1185,56 +876,7 @@ AH_EXPORT int ah_hash_u64_encode(ah_ctx* c, const uint64_t* keys, const uint8_t*
   EncodeResult res;
   int rc = encode_core(c, U64Keys{(const unsigned long long*)keys}, valid, off, n, encode_nulls, out_ids, out_dict, &res);
   if (rc != AH_OK) return rc;
-  if (out_ids_valid && (rc = ids_validity(c, valid, off, n, encode_nulls, out_ids_valid)) != AH_OK) return rc;
-  if (out_ndict_host) *out_ndict_host = res.ndict;
-  if (out_null_id_host) *out_null_id_host = res.null_id;
-  return AH_OK;
-}
-
-AH_EXPORT int ah_hash_sum_f64(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
-                              const double* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
-                              uint64_t* out_keys, double* out_sums, int64_t* out_counts, int64_t* out_first_rows,
-                              int64_t* out_ngroups_host, int32_t* out_null_group_host) {
-  AH_ENTER(c);
-  return hash_sum<double, double>(c, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows,
-                                  out_ngroups_host, out_null_group_host);
-}
-
-AH_EXPORT int ah_hash_sum_i64(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
-                              const int64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
-                              uint64_t* out_keys, int64_t* out_sums, int64_t* out_counts, int64_t* out_first_rows,
-                              int64_t* out_ngroups_host, int32_t* out_null_group_host) {
-  AH_ENTER(c);
-  return hash_sum<unsigned long long, unsigned long long>(c, keys, kvalid, koff, (const unsigned long long*)vals, vvalid, voff, n,
-                                                          out_keys, (unsigned long long*)out_sums, out_counts, out_first_rows,
-                                                          out_ngroups_host, out_null_group_host);
-}
-
-AH_EXPORT int ah_hash_min_max_i64(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
-                                  const int64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
-                                  uint64_t* out_keys, int64_t* out_mins, int64_t* out_maxs, int64_t* out_counts, int64_t* out_first_rows,
-                                  int64_t* out_ngroups_host, int32_t* out_null_group_host) {
-  AH_ENTER(c);
-  return hash_min_max(c, 1, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_mins, out_maxs, out_counts, out_first_rows,
-                      out_ngroups_host, out_null_group_host);
-}
-
-AH_EXPORT int ah_hash_min_max_u64(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
-                                  const uint64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
-                                  uint64_t* out_keys, uint64_t* out_mins, uint64_t* out_maxs, int64_t* out_counts, int64_t* out_first_rows,
-                                  int64_t* out_ngroups_host, int32_t* out_null_group_host) {
-  AH_ENTER(c);
-  return hash_min_max(c, 0, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_mins, out_maxs, out_counts, out_first_rows,
-                      out_ngroups_host, out_null_group_host);
-}
-
-AH_EXPORT int ah_hash_min_max_f64(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
-                                  const double* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
-                                  uint64_t* out_keys, double* out_mins, double* out_maxs, int64_t* out_counts, int64_t* out_first_rows,
-                                  int64_t* out_ngroups_host, int32_t* out_null_group_host) {
-  AH_ENTER(c);
-  return hash_min_max(c, 2, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_mins, out_maxs, out_counts, out_first_rows,
-                      out_ngroups_host, out_null_group_host);
+  return encode_finish(c, res, valid, off, n, encode_nulls, out_ids_valid, out_ndict_host, out_null_id_host);
 }
 
 // ---- key → owner partition for the multi-GPU merge (SURVEY.md §8e plan A) ----------------------

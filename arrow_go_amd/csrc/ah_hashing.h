@@ -1,4 +1,4 @@
-// ah_hashing.h — pieces shared by ah_hash.hip (unique / dictionary_encode / the id-based group-by) and
+// ah_hashing.h — pieces shared by ah_hash.hip (unique / dictionary_encode), ah_hash_agg.hip (the id-based group-by) and
 // ah_groupby.hip (the partition-first group-by): the reference's integer hash, first-seen ranking over an n-bit
 // "first occurrence" bitmap, and the 128-bit fixed-point accumulation that makes Float64 group sums reproducible.
 #pragma once

@@ -136,6 +136,7 @@ const char* ah_last_error(ah_ctx* ctx); /* never NULL; owned by ctx */
  * compute entry point and by uploads / copies / memsets into the vector, sampled again on every 32nd use; every path returns the same bytes, so an entry
  * gone stale behind the library's back costs speed, never results; 0, the default of ah_ctx_create_on_stream: sample on every call), "take_gather_wg_per_cu", "take_gather_load", "scan_segment_log2",
  * "hash_direct" (unique / dictionary_encode: 0 ids in a separate pass … 2 default, 3 without the re-packed table),
+ * "hash_sum_partition" (id-based hash + sum above 4096 groups: 1 default, 0 plain device atomics),
  * "groupby_partition" (hash + sum: 0 id-based path only, 1 auto, k >= 5 always 2^(k-2) partitions, 2 sort-based, 3 / 4 two levels,
  * -2 no cut), "groupby_keys" (expected keys per partition the auto choice aims at, default 1280), "sort_msd" (sort_indices:
  * 0 LSD passes only, 1 auto), "groupby_seed" (hash + sum with few groups: 1 the workgroups' LDS tables start from the keys a quick look

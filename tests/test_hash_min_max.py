@@ -105,14 +105,15 @@ def test_entry_points_are_declared_exported_and_bound():
 
 
 def test_kernels_have_no_scratch_and_fit_the_lds():
-    """every kernel of ah_hash_minmax.hip compiles for gfx950 with zero scratch bytes and a group segment inside gfx950's 160 KiB (read
-    from the ISA the way tests/test_cast_decimal.py reads it); the LDS regime's table is the 80 KiB the design states"""
+    """every kernel of ah_hash_agg.hip compiles for gfx950 with zero scratch bytes and a group segment inside gfx950's 160 KiB (read
+    from the ISA the way tests/test_cast_decimal.py reads it); the LDS regime's tables are what the declarations state: per group a
+    32-bit count and 8 bytes (Int64 sum) or 16 bytes (Float64 sum: 128-bit fixed point; min / max) of aggregate"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc), "hipcc not found: the library under test cannot have been built without it"
     with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "hash_minmax.s")
+        out = os.path.join(d, "hash_agg.s")
         r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-S",
-                            "--cuda-device-only", "-o", out, os.path.join(CSRC, "ah_hash_minmax.hip")], capture_output=True, text=True, timeout=900)
+                            "--cuda-device-only", "-o", out, os.path.join(CSRC, "ah_hash_agg.hip")], capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         text = open(out).read()
     kernels = {}
@@ -120,13 +121,21 @@ def test_kernels_have_no_scratch_and_fit_the_lds():
         p = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(2))
         g = re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", m.group(2))
         kernels[m.group(1)] = (int(p.group(1)), int(g.group(1)))
-    assert sum("group_min_max_kernel" in k for k in kernels) == 6           # {u64, i64, f64} × {LDS table, device atomics}
+    lds_of = lambda *words: sorted(lds for k, (_, lds) in kernels.items() if all(w in k for w in words))
+    assert len(lds_of("group_agg_kernel", "MinMax")) == 6                   # {u64, i64, f64} × {LDS table, device atomics}
     assert sum("min_max_finish_kernel" in k for k in kernels) == 3
     assert sum("min_max_init_kernel" in k for k in kernels) == 1
     for k, (scratch, lds) in kernels.items():
         assert scratch == 0, f"{k}: {scratch} bytes of scratch"
         assert lds <= 163840, f"{k}: {lds} bytes of LDS"
-    assert sorted(lds for k, (_, lds) in kernels.items() if "group_min_max_kernel" in k) == [0] * 3 + [4096 * 20] * 3
+    assert lds_of("group_agg_kernel", "MinMax") == [0] * 3 + [4096 * 20] * 3
+    # the sums: {LDS table, device atomics} each, and the run-by-run kernel behind the partition (its table + the block-wide count's words)
+    assert lds_of("group_agg_kernel", "SumI64") == [0, 4096 * 12]
+    assert lds_of("group_agg_kernel", "SumF64") == [0, 4096 * 20]
+    assert lds_of("group_agg_kernel", "AbsMax") == [0]                      # the per-group scale of wide Float64 columns: device atomics only
+    bucket_i64, bucket_f64 = lds_of("bucket_sum_kernel", "SumI64"), lds_of("bucket_sum_kernel", "SumF64")
+    assert len(bucket_i64) == 1 and 4096 * 12 <= bucket_i64[0] <= 4096 * 12 + 1024
+    assert len(bucket_f64) == 1 and 4096 * 20 <= bucket_f64[0] <= 4096 * 20 + 1024
 
 
 # ---- on the GPU -----------------------------------------------------------------------------------------------------------------------
