@@ -176,6 +176,8 @@ _SIGS = {
     "ah_hash_min_max_u64": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _pi64, _pi32],
     "ah_hash_min_max_f64": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _pi64, _pi32],
     "ah_lz4_decompress_blocks": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _pi64],
+    "ah_lz4_compress_blocks": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    "ah_ipc_pack_body": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64],
     "ah_cmp_filter_sum_i64": [_vp, _int, _vp, _vp, _i64, _i64, _i64, _pi64, _pi64],
     "ah_cmp_filter_sum_f64": [_vp, _int, _vp, _vp, _i64, _i64, C.c_double, _pd, _pi64],
     "ah_cmp_filter_sum_i64_dev": [_vp, _int, _vp, _vp, _i64, _i64, _i64, _vp],

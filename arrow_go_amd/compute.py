@@ -70,6 +70,13 @@ lib.ahc_ipc_bytes_uploaded.restype = C.c_int64
 lib.ahc_ipc_inspect.argtypes = [_vp, C.c_int64, C.c_char_p, C.c_int64]
 lib.ahc_ipc_stats.argtypes = [_vp, C.POINTER(C.c_int64)]
 lib.ahc_ipc_stats.restype = None
+lib.ahc_ipc_writer_open.argtypes = [_vp, C.c_char_p, C.POINTER(_vp)]
+lib.ahc_ipc_write_batch.argtypes = [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(_vp)]
+lib.ahc_ipc_writer_finish.argtypes = [_vp, C.POINTER(_vp), C.POINTER(C.c_int64)]
+lib.ahc_ipc_writer_stats.argtypes = [_vp, C.POINTER(C.c_int64)]
+lib.ahc_ipc_writer_stats.restype = None
+lib.ahc_ipc_writer_close.argtypes = [_vp]
+lib.ahc_ipc_writer_close.restype = None
 lib.ahc_substrait_inspect.argtypes = [_vp, C.c_int64, C.c_char_p, C.c_int64]
 lib.ahc_dispatch_best.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int64]
 lib.ahc_expr_eval.argtypes = [_vp, C.c_char_p, C.c_int, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(C.c_int)]
@@ -322,6 +329,7 @@ class Session:
             raise ErrHip("ahc_session_create failed: is a GPU visible? (no CPU fallback)")
         self.h = h
         self.last_ipc_stats = dict(bytes_uploaded=0, device_buffers=0, host_buffers=0, device_fallbacks=0)   # of the latest read_ipc
+        self.last_ipc_write_stats = dict(raw_bytes=0, body_bytes=0, buffers_compressed=0, buffers_raw=0)   # of the latest write_ipc
         self.device_id = device_id
 
     def close(self):
@@ -617,6 +625,40 @@ class Session:
             note_stats()
             lib.ahc_ipc_close(r)
             del keep
+
+    # -- ipc.NewWriter / Writer.Write / Close, with the bodies compressed in HBM
+    def write_ipc(self, names, batches, compression: str = "lz4") -> bytes:
+        """The Arrow IPC *stream* of `batches` — an iterable of lists of DeviceArray, one per name, all of one length per batch —
+        as bytes.  compression "lz4": every buffer is compressed on the device (LZ4 frames of independent 64 KiB blocks, which
+        read_ipc inflates on the device) and only the compressed body comes down; "none": the plain body.  The first batch fixes
+        the schema.  `last_ipc_write_stats`: plain bytes of all buffers, body bytes written, buffers written as frames, buffers
+        written raw because their frame would not have been smaller."""
+        if compression not in ("lz4", "none"):
+            raise ValueError(f"write_ipc: compression must be 'lz4' or 'none', not {compression!r}")
+        names = list(names)
+        w = _vp()
+        self._check(lib.ahc_ipc_writer_open(self.h, f"compression={compression}".encode(), C.byref(w)))
+
+        def note_stats():
+            st = (C.c_int64 * 4)()
+            lib.ahc_ipc_writer_stats(w, st)
+            self.last_ipc_write_stats = dict(zip(("raw_bytes", "body_bytes", "buffers_compressed", "buffers_raw"), list(st)))
+
+        try:
+            cnames = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+            for batch in batches:
+                batch = list(batch)
+                if len(batch) != len(names):
+                    raise ValueError(f"write_ipc: a batch of {len(batch)} columns for {len(names)} names")
+                cols = (_vp * max(len(batch), 1))(*[c.h for c in batch])
+                self._check(lib.ahc_ipc_write_batch(w, len(batch), cnames, cols))
+                note_stats()
+            p, n = _vp(), C.c_int64()
+            self._check(lib.ahc_ipc_writer_finish(w, C.byref(p), C.byref(n)))
+            return C.string_at(p.value, n.value) if n.value else b""
+        finally:
+            note_stats()
+            lib.ahc_ipc_writer_close(w)
 
     # -- compute.Expression / exprs.ExecuteScalarExpression
     def eval_expression(self, text: str, columns, literals=(), fuse: bool = True, raw: bool = False):

@@ -732,6 +732,26 @@ class Context:
         assert nbad.value == int(np.count_nonzero(status))
         return status
 
+    def lz4_compress_blocks(self, src, src_bytes: int, dst, dst_bytes: int, blocks):
+        """blocks of at most 65536 device bytes of `src`, each compressed on its own as one LZ4 block into its slot of `dst`; blocks:
+        rows of {src_off, src_len, dst_off}, the slots dst[dst_off, dst_off + src_len) ascending without overlap.  Returns (sizes,
+        stored) as numpy arrays: the bytes written to each slot, and 1 where the block did not shrink and its slot holds the input."""
+        table = np.ascontiguousarray(np.asarray(blocks, np.int64).reshape(-1, 3))
+        sizes = np.zeros(len(table), np.int32)
+        stored = np.zeros(len(table), np.uint8)
+        check(self.handle, lib.ah_lz4_compress_blocks(self.handle, _ptr(src), src_bytes, _ptr(dst), dst_bytes, table.ctypes.data, len(table),
+                                                      sizes.ctypes.data, stored.ctypes.data))
+        return sizes, stored
+
+    def ipc_pack_body(self, comp, comp_bytes: int, plain, plain_bytes: int, lits: bytes, rows, dst, dst_bytes: int) -> None:
+        """dst[0, dst_bytes) := the pieces of `rows` {src_off, len, dst_off, word} end to end; word & 3: 0 the device bytes `comp`, 1 the
+        device bytes `plain`, 2 the host bytes `lits`; word bit 8: the 32 bits above bit 32 go, little-endian, in front of the piece.
+        The rows must tile the output exactly."""
+        table = np.ascontiguousarray(np.asarray(rows, np.int64).reshape(-1, 4))
+        lit = np.frombuffer(bytes(lits), np.uint8)
+        check(self.handle, lib.ah_ipc_pack_body(self.handle, _ptr(comp), comp_bytes, _ptr(plain), plain_bytes, lit.ctypes.data if len(lit) else None,
+                                                len(lit), table.ctypes.data if len(table) else None, len(table), _ptr(dst), dst_bytes))
+
     def hash_partition(self, keys, n: int, nparts: int, out_part) -> None:
         check(self.handle, lib.ah_hash_partition_u64(self.handle, _ptr(keys), n, nparts, _ptr(out_part)))
 

@@ -13,6 +13,7 @@
 #include <string>
 
 #include "arrowhip_compute.h"
+#include "capi_internal.h"
 #include "ipc.h"
 
 // the public C header: the Arrow C Data / C Device Data structs and every ahc_* prototype — including it here makes the
@@ -1087,6 +1088,11 @@ AHC_EXPORT int ahc_ipc_next(ahc_ipc_reader* r, ahc_datum** columns, int64_t* row
 AHC_EXPORT int64_t ahc_ipc_bytes_uploaded(ahc_ipc_reader* r) { return r->r->body_bytes_uploaded(); }
 // so far: {bytes uploaded, compressed buffers inflated on the device, … on the host, … on the host after a device status}
 AHC_EXPORT void ahc_ipc_stats(ahc_ipc_reader* r, int64_t out[4]) { r->r->stats(out); }
+
+// what host/ipc_writer.cc needs of the opaque handles for its ahc_ipc_writer_* exports (capi_internal.h)
+Session* ahc_internal_session(ahc_session* s) { return s->session.get(); }
+int ahc_internal_fail(ahc_session* s, const Status& st) { return Fail(s, st); }
+const Datum* ahc_internal_datum(const ahc_datum* d) { return &d->d; }
 
 // Walks a stream without a device: "hex(name):type_id:nullable,…|rows,rows,…" into out (NUL-terminated), or
 // the error text with the status code returned — the parser's own test entry (runs where there is no GPU).

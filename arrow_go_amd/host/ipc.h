@@ -75,5 +75,37 @@ class StreamReader {
   std::vector<FieldInfo> fields_;
 };
 
+// Record batches resident in HBM → an Arrow IPC stream (ipc.NewWriter / Writer.Write / Close, arrow/ipc/writer.go:85-260); the
+// definition is in ipc_writer.cc and DESIGN.md §3.8.  The Schema message is written with the first batch, whose columns fix the
+// fields: the types the reader above takes, plain or dictionary-encoded; anything else is ErrNotImplemented with the column named.
+// A dictionary-encoded column gets a DictionaryBatch (isDelta = false) before the first record batch that uses it, and a
+// replacement before any batch whose dictionary is not the identical device buffers of the one written last for that id.
+// A column may be a slice: the bytes written are those of an offset-0 array of its rows.  Every byte of the stream is defined.
+// With lz4 every buffer is an LZ4 frame of independent 64 KiB blocks without checksums — what the reader's device path accepts —
+// compressed in HBM, or its raw bytes behind a −1 prefix where the frame would not be smaller; a buffer of no bytes has length 0.
+// A Write that fails appends nothing (the first one may leave the Schema message) and the writer stays usable.
+class StreamWriter {
+ public:
+  StreamWriter(Session* s, bool lz4);
+  Status Write(const std::vector<std::string>& names, const std::vector<ArrayDataPtr>& columns);
+  Status Close();   // the end-of-stream marker; Write is refused afterwards
+  const std::vector<uint8_t>& bytes() const { return out_; }
+  // {plain bytes of all buffers, body bytes written, buffers written as frames, buffers written raw behind −1} so far
+  void stats(int64_t out[4]) const { for (int i = 0; i < 4; i++) out[i] = stats_[i]; }
+
+ private:
+  struct Piece;
+  struct Column;
+  struct Message;
+  Status Describe(const std::string& name, const ArrayData& a, int64_t next_dict_id, FieldInfo* out) const;
+  Status WriteSchema();
+  Session* s_;
+  bool lz4_, have_schema_ = false, closed_ = false;
+  std::vector<FieldInfo> fields_;
+  std::map<int64_t, ArrayDataPtr> written_dicts_;   // dictionary id → the dictionary written last (kept alive: see SameBuffers)
+  std::vector<uint8_t> out_;
+  int64_t stats_[4] = {0, 0, 0, 0};
+};
+
 }  // namespace ipc
 }  // namespace arrowhip

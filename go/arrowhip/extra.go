@@ -214,6 +214,41 @@ func (x *Context) Lz4DecompressBlocks(src unsafe.Pointer, srcBytes int64, dst un
 	return int64(bad), x.err(st)
 }
 
+// Lz4CompressBlocks: blocks of at most 65536 bytes of the device bytes src, each compressed on its own as one LZ4 block into its slot
+// of the device bytes dst (ah_lz4_compress_blocks).  blocks holds 3 values per block {srcOff, srcLen, dstOff}; the slots
+// dst[dstOff, dstOff+srcLen) ascend without overlap.  sizes receives the bytes written to every slot, stored 1 where the block did
+// not shrink and its slot holds the input bytes.
+func (x *Context) Lz4CompressBlocks(src unsafe.Pointer, srcBytes int64, dst unsafe.Pointer, dstBytes int64, blocks []int64, sizes []int32, stored []byte) error {
+	n := len(blocks) / 3
+	if len(blocks)%3 != 0 || len(sizes) < n || len(stored) < n {
+		return fmt.Errorf("%w: lz4 block table of %d values with %d sizes and %d flags", arrow.ErrInvalid, len(blocks), len(sizes), len(stored))
+	}
+	if n == 0 {
+		return nil
+	}
+	return x.err(C.ah_lz4_compress_blocks(x.c, (*C.uint8_t)(src), C.int64_t(srcBytes), (*C.uint8_t)(dst), C.int64_t(dstBytes),
+		(*C.int64_t)(unsafe.Pointer(&blocks[0])), C.int64_t(n), (*C.int32_t)(unsafe.Pointer(&sizes[0])), (*C.uint8_t)(unsafe.Pointer(&stored[0]))))
+}
+
+// IpcPackBody: the device bytes dst[0, dstBytes) put together from the pieces of rows, 4 values per row {srcOff, len, dstOff, word}
+// (ah_ipc_pack_body): word&3 selects the device bytes comp (0), the device bytes plain (1) or the host bytes lits (2); word bit 8
+// writes the 32 bits above bit 32 of word, little-endian, in the 4 bytes before dstOff.  The rows must tile the output exactly.
+func (x *Context) IpcPackBody(comp unsafe.Pointer, compBytes int64, plain unsafe.Pointer, plainBytes int64, lits []byte, rows []int64, dst unsafe.Pointer, dstBytes int64) error {
+	if len(rows)%4 != 0 {
+		return fmt.Errorf("%w: pack table of %d values", arrow.ErrInvalid, len(rows))
+	}
+	var lp *C.uint8_t
+	if len(lits) > 0 {
+		lp = (*C.uint8_t)(unsafe.Pointer(&lits[0]))
+	}
+	var rp *C.int64_t
+	if len(rows) > 0 {
+		rp = (*C.int64_t)(unsafe.Pointer(&rows[0]))
+	}
+	return x.err(C.ah_ipc_pack_body(x.c, (*C.uint8_t)(comp), C.int64_t(compBytes), (*C.uint8_t)(plain), C.int64_t(plainBytes), lp, C.int64_t(len(lits)),
+		rp, C.int64_t(len(rows)/4), (*C.uint8_t)(dst), C.int64_t(dstBytes)))
+}
+
 // HashPartition: partition id of every key by the reference's integer hash (internal/hashing/hash_funcs.go:60-67) — the owner
 // function of the C5 merge.
 func (x *Context) HashPartition(keys unsafe.Pointer, n int64, nparts int, outPart unsafe.Pointer) error {

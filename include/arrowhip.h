@@ -507,6 +507,30 @@ int ah_hash_min_max_f64(ah_ctx* ctx, const uint64_t* keys, const uint8_t* kvalid
 int ah_lz4_decompress_blocks(ah_ctx* ctx, const uint8_t* src, int64_t src_bytes, uint8_t* dst, int64_t dst_bytes,
                              const int64_t* blocks_host, int64_t nblocks, uint8_t* out_status_host, int64_t* out_nbad_host);
 
+/* ---- LZ4 blocks compressed in HBM, and an IPC body put together from them (NEW — no reference analogue: the reference compresses
+ * IPC bodies on the host, arrow/ipc/writer.go:430-470, compression.go:66-72; definition in DESIGN.md §3.8) ---------------------
+ * ah_lz4_compress_blocks: src / dst: device memory.  blocks_host: 3 int64 per block {src_off, src_len, dst_off}, src_len <= 65536.
+ * Block i is compressed on its own (a match never reaches in front of its block) into its slot dst[dst_off, dst_off + src_len);
+ * the bytes are a function of the block's bytes alone — not of where the block or its slot lie, and the same on every run.
+ * out_sizes_host[i]: bytes written to the slot; out_stored_host[i]: 1 = the block would not have come out smaller than src_len, and
+ * its slot holds the src_len input bytes instead (what an LZ4 frame marks with bit 31 of the block size).  src_len == 0: size 0,
+ * stored.  Nothing outside the first out_sizes_host[i] bytes of a slot is written.  dst must not overlap src: a block's compressed
+ * bytes reach its slot while other blocks are still being read.
+ * AH_EINVALID before anything runs if a source range lies outside src_bytes, a src_len is beyond 65536, a slot lies outside
+ * dst_bytes, or the slots do not ascend without overlap.  One launch; synchronises once.
+ *
+ * ah_ipc_pack_body: dst[0, dst_bytes) := the concatenation of nrows pieces.  rows_host: 4 int64 per row {src_off, len, dst_off,
+ * word}; word & 3 selects the source — 0: comp (device), 1: plain (device), 2: lits_host (host bytes, uploaded with the rows) —
+ * and word bit 8 asks for the 32 bits above bit 32 of word to be written, little-endian, in the 4 bytes BEFORE dst_off (the block
+ * size word of an LZ4 frame); every other bit of word must be 0.  The rows must tile the output: row 0 (with its 4 leading bytes,
+ * if any) starts at 0, every row starts where the one before it ended, the last ends at dst_bytes — so every byte of dst is
+ * written, and written once.  AH_EINVALID before anything runs otherwise, or if a source range lies outside its source.
+ * dst must not overlap comp or plain.  One launch; synchronises once. */
+int ah_lz4_compress_blocks(ah_ctx* ctx, const uint8_t* src, int64_t src_bytes, uint8_t* dst, int64_t dst_bytes,
+                           const int64_t* blocks_host, int64_t nblocks, int32_t* out_sizes_host, uint8_t* out_stored_host);
+int ah_ipc_pack_body(ah_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const uint8_t* plain, int64_t plain_bytes,
+                     const uint8_t* lits_host, int64_t lits_bytes, const int64_t* rows_host, int64_t nrows, uint8_t* dst, int64_t dst_bytes);
+
 /* ---- fused Compare(op scalar) → Filter(DropNulls) → Sum ------------------------------
  * NEW entry point (no reference analogue) computing in ONE pass what the reference
  * computes with "greater" → "array_filter" → math.Sum: Σ x[i] over valid slots with

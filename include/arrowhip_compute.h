@@ -97,6 +97,7 @@ struct ArrowDeviceArray {
 
 typedef struct ahc_session ahc_session;       /* ah_ctx + compute.ExecCtx with its own child registry (compute/executor.go:46-112) */
 typedef struct ahc_datum ahc_datum;           /* compute.Datum */
+typedef struct ahc_ipc_writer ahc_ipc_writer; /* ipc.Writer (arrow/ipc/writer.go:85-110) */
 typedef struct ahc_ipc_reader ahc_ipc_reader; /* ipc.Reader (arrow/ipc/reader.go:45-70) */
 
 /* ---- session / registry ------------------------------------------------------------------------------------------ */
@@ -256,6 +257,25 @@ int64_t ahc_ipc_bytes_uploaded(ahc_ipc_reader* r);
  * host path (option 0, a body below the minimum, a frame that does not qualify).  Every valid stream reads the same on both.
  * out: {body bytes uploaded, compressed buffers inflated on the device, on the host, on the host after a device status} so far */
 void ahc_ipc_stats(ahc_ipc_reader* r, int64_t out[4]);
+/* ---- HBM → Arrow IPC (ipc.NewWriter / Writer.Write / Close, arrow/ipc/writer.go:85-260) ------------------------------ */
+/* A stream of record batches whose columns live in HBM.  options: "compression=lz4" (the default for NULL / "") or
+ * "compression=none".  With lz4 every buffer of a body is compressed IN HBM — an LZ4 frame of independent 64 KiB blocks without
+ * checksums, the kind ahc_ipc_open inflates in HBM — or written raw behind a -1 length where the frame would not be smaller, and only
+ * the compressed body crosses the link: per batch one compress launch, one launch that assembles the messages, one download.
+ * ahc_ipc_write_batch: array datums only, all of one length; types: what ahc_ipc_open reads (ErrNotImplemented names the column
+ * otherwise).  The first batch fixes the schema and writes the Schema message; a later batch that differs in a name, type, temporal
+ * type or dictionary index type is ErrInvalid naming the column, as is a chunked or scalar datum (write chunk by chunk).  A
+ * dictionary-encoded column gets its DictionaryBatch before the first record batch, and a replacement before a batch whose
+ * dictionary is not the identical device buffers.  A sliced column is written as the offset-0 array of its rows.  Every byte of the
+ * stream is defined: the same batches give the same bytes.  After an error the writer (and the session) stay usable.
+ * ahc_ipc_writer_finish writes the end-of-stream marker; *bytes belongs to the writer and is valid until ahc_ipc_writer_close.
+ * ahc_ipc_writer_stats: {plain bytes of all buffers, body bytes written, buffers written as frames, buffers written raw} so far. */
+int ahc_ipc_writer_open(ahc_session* s, const char* options, ahc_ipc_writer** out);
+int ahc_ipc_write_batch(ahc_ipc_writer* w, int ncols, const char* const* names, ahc_datum** columns);
+int ahc_ipc_writer_finish(ahc_ipc_writer* w, const uint8_t** bytes, int64_t* len);
+void ahc_ipc_writer_stats(ahc_ipc_writer* w, int64_t out[4]);
+void ahc_ipc_writer_close(ahc_ipc_writer* w);
+
 /* walks a stream WITHOUT a device: "hex(name):type_id:nullable:hex(logical),…|rows,rows,…" into out (NUL-terminated),
  * or the error text with the status returned */
 int ahc_ipc_inspect(const uint8_t* bytes, int64_t len, char* out, int64_t cap);
