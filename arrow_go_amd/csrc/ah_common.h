@@ -238,20 +238,32 @@ int ah_scratch_reserve(ah_ctx* ctx, size_t nbytes, void** out);
 // A second grow-only arena for entry points that call a scratch user (the scan) while their own temporaries are
 // live: sort, group-by, var-length take.  One reservation per top-level call, carved by the caller; the block is
 // reused by the next call in stream order (no hipMalloc / hipFree — each maps and unmaps the whole range — per call).
-int ah_temp_reserve(ah_ctx* ctx, size_t nbytes, void** out);
-// The carving of such a block: every piece starts on a 256-byte boundary.  A caller sums ah_pad(bytes) of its pieces into the
-// size it reserves and then takes them in the same order.
+// *out_of_memory (nullable) tells a failed hipMalloc — the one failure a caller may answer with a path that needs less — from a failed
+// synchronisation or hipFree, which is the caller's to return.
+int ah_temp_reserve(ah_ctx* ctx, size_t nbytes, void** out, bool* out_of_memory = nullptr);
+// The carving of such a block: every piece starts on a 256-byte boundary.  A caller describes its pieces once (a function of a
+// TempCarver&), runs the description on a carver without a base to measure (take only advances `used`), reserves `used` and runs it
+// again on the block.
 static inline constexpr size_t ah_pad(size_t b) { return (b + 255) & ~(size_t)255; }
 struct TempCarver {
   uint8_t* base = nullptr;
   size_t used = 0;
-  uint8_t* take(size_t b) { uint8_t* q = base + used; used += ah_pad(b); return q; }
+  uint8_t* take(size_t b) { uint8_t* q = base ? base + used : nullptr; used += ah_pad(b); return q; }
+  template <typename T> size_t take(T*& p, size_t count) { p = (T*)take(count * sizeof(T)); return ah_pad(count * sizeof(T)); }   // → the piece's bytes
 };
 // The words of dscalars (ah_ctx: kDsScalars scalar words, then the popcount's partials area) the streaming reductions own.
 constexpr int kDsScalars = 64;
 constexpr int kDsSum = 0;                           // ah_sum_*, ah_count_set_bits: the one result word
 constexpr int kDsFusedSum = 8, kDsFusedCount = 9;   // cmp_filter_sum_*: {sum, count}, read home as two mailbox words
 constexpr int kDsMinMax = 12;                       // min_max: {lo, hi}, ≤ 16 bytes
+// Owners of the other words: 1–3 filter / take / var-length, 4–8 ah_hash.hip, 9–15 scan / cast / expression flags, 20–23 and 28–29
+// ah_groupby.hip, 26–27 ah_sort_msd.hip, 30–36 ah_hash_part.hip, 40–45 ah_comm.hip.
+constexpr int kDsGbDone = 20;                       // partition-first group-by: workgroups of gd_finish_kernel that are through, then …
+constexpr int kDsGbFlags = 21, kDsGbTotal = 22, kDsGbNullId = 23;   // … {flags (ah_partition.h: kPart*), groups, null group}: read home as three words
+constexpr int kDsGbRange = 28;                      // … and [28], [29] the value range of the call (ah_hashing.h)
+constexpr int kDsEncFlags = 30, kDsEncTotal = 31, kDsEncNullId = 32;   // partition-first encode: the same three words
+constexpr int kDsEncLook = 33, kDsEncLookDone = 34;                 // ah_encode_first_look: the count, the workgroups that have finished
+constexpr int kDsEncLargest = 35, kDsEncLargestDone = 36;           // two-cut encode: the largest partition (ms_offs2_kernel), its parents done
 constexpr int kDsPopcountPartials = kDsScalars;     // popcount: one word per workgroup …
 constexpr int kPopcountMaxPartials = 4096;          // … and as many workgroups at the most
 // internal (ah_bitmap.hip): popcount of bits [off, off+nbits) into *total_dev (8 bytes,

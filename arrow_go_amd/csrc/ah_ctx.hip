@@ -245,14 +245,15 @@ int ah_scratch_reserve(ah_ctx* c, size_t nbytes, void** out) {
   return AH_OK;
 }
 
-int ah_temp_reserve(ah_ctx* c, size_t nbytes, void** out) {
+int ah_temp_reserve(ah_ctx* c, size_t nbytes, void** out, bool* out_of_memory) {
+  if (out_of_memory) *out_of_memory = false;
   if (nbytes > c->temp_bytes) {
     AH_HIP(c, hipStreamSynchronize(c->stream));  // the old block may still be in use by enqueued kernels
     if (c->temp) AH_HIP(c, hipFree(c->temp));
     c->temp = nullptr;
     c->temp_bytes = 0;
     size_t want = (nbytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    if (hipMalloc(&c->temp, want) != hipSuccess) { (void)hipGetLastError(); return ah_fail(c, AH_EHIP, "out of device memory (%zu bytes of temporaries)", want); }
+    if (hipMalloc(&c->temp, want) != hipSuccess) { (void)hipGetLastError(); if (out_of_memory) *out_of_memory = true; return ah_fail(c, AH_EHIP, "out of device memory (%zu bytes of temporaries)", want); }
     c->temp_bytes = want;
   }
   *out = c->temp;

@@ -34,7 +34,7 @@
 #include "ah_common.h"
 #include "ah_hashing.h"
 #include "ah_bins.h"
-#include "ah_partition.h"
+#include "ah_part_driver.h"
 #include "ah_msd.h"
 
 namespace {
@@ -1101,11 +1101,42 @@ __global__ __launch_bounds__(1024) void gs_subregions_kernel(const unsigned* __r
   }
 }
 
-// the sort-based path (gs_* kernels).  *used = 1: out_* hold the result.
-static int gs_groupby(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, const void* vals, const uint8_t* vvalid,
-                      int64_t voff, int64_t n, uint64_t* out_keys, void* out_sums, int64_t* out_counts, int64_t* out_first_rows, int64_t* out_ngroups,
-                      int32_t* out_null_group, int* used) {
-  *used = 0;
+// ---- the host drivers ---------------------------------------------------------------------------------------------------------------
+// One hash-sum call as the drivers see it (ah_hash_agg.hip's GroupCall hands it to ah_groupby_partitioned_try), the columns typed as
+// the kernels take them.  A driver takes this plus what is its own and says how it ended (PartOutcome, ah_part_driver.h).
+namespace {
+struct GbCall {
+  ah_ctx* c;
+  bool is_f64;
+  const unsigned long long* keys; const uint8_t* kvalid; int64_t koff;
+  const unsigned long long* vals; const uint8_t* vvalid; int64_t voff;
+  int64_t n;
+  unsigned long long *out_keys, *out_sums;
+  long long *out_counts, *out_first_rows;
+  int64_t* out_ngroups; int32_t* out_null_group;   // host
+  // the call's words of dscalars
+  unsigned* done() const { return (unsigned*)&c->dscalars[kDsGbDone]; }
+  unsigned* flags() const { return (unsigned*)&c->dscalars[kDsGbFlags]; }   // kPart* (ah_partition.h)
+  unsigned long long* total() const { return (unsigned long long*)&c->dscalars[kDsGbTotal]; }
+  int* null_id() const { return (int*)&c->dscalars[kDsGbNullId]; }
+  unsigned long long* range() const { return (unsigned long long*)&c->dscalars[kDsGbRange]; }   // [0], [1]: the value range (ah_hashing.h)
+  // {flags, total, null id} home → the outcome and the two host outputs
+  int finish(bool reserving, PartOutcome* outcome) const { return part_finish(c, kDsGbFlags, reserving, out_ngroups, out_null_group, outcome); }
+};
+// the five planes of a table of `slots` entries; → the bytes of {lo, hi, cnt}, which are adjacent: one fill job zeroes the three
+size_t gb_carve_table(TempCarver& tc, GbTable& t, size_t slots) {
+  tc.take(t.key, slots);
+  size_t sums = tc.take(t.lo, slots); sums += tc.take(t.hi, slots); sums += tc.take(t.cnt, slots);
+  tc.take(t.first, slots);
+  return sums;
+}
+}  // namespace
+
+// the sort-based path (gs_* kernels)
+static int gs_groupby(const GbCall& g, PartOutcome* outcome) {
+  ah_ctx* c = g.c;
+  const int64_t n = g.n;
+  *outcome = PartOutcome::Declined;
   if (n < ((int64_t)1 << 22) || n > ((int64_t)1 << 27)) return AH_OK;   // 2^27 rows = 2^21 buckets of 64 = 1024 parents × 2048
   int lb = 0;
   while (((int64_t)64 << lb) < n) lb++;
@@ -1115,48 +1146,34 @@ static int gs_groupby(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t
   const int64_t ntiles = ah_ceil_div(n, kMsTile), ngrp = ah_ceil_div(ntiles, kGroupTiles), nvt = ((ntiles + nb1 + 7) / 8) * 8;
   const unsigned grid1 = (unsigned)(((ntiles + 7) / 8) * 8);
   const int64_t nwords = ah_ceil_div(n, 64), nrt = rank_tiles(nwords);
-  const size_t need = ah_pad((size_t)n * 8) * 4 + ah_pad((size_t)n * 4) * 3 + ah_pad((size_t)ntiles * nb1 * 4) * 2 + ah_pad((size_t)ngrp * nb1 * 4) + ah_pad((size_t)(nb1 + 1) * 4) +
-                      ah_pad((size_t)nvt * nb2 * 4) * 2 + ah_pad(((size_t)nbuckets + 1) * 4) + ah_pad((size_t)ntiles * 16) + ah_pad((size_t)nwords * 8) + ah_pad((size_t)nwords * 4) +
-                      ah_pad((size_t)nrt * 4) + ah_pad((size_t)nrt * 8);
-  TempCarver tc;
-  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
-  if (rc != AH_OK) { c->err[0] = 0; return AH_OK; }   // these temporaries do not fit: *used stays 0 and the caller's id-based path (a fraction of them) answers
-  unsigned long long* pkeys = (unsigned long long*)tc.take((size_t)n * 8);
-  unsigned long long* pvals = (unsigned long long*)tc.take((size_t)n * 8);
-  unsigned long long* qkeys = (unsigned long long*)tc.take((size_t)n * 8);
-  unsigned long long* qvals = (unsigned long long*)tc.take((size_t)n * 8);
-  unsigned* prows = (unsigned*)tc.take((size_t)n * 4);
-  unsigned* qrows = (unsigned*)tc.take((size_t)n * 4);
-  unsigned* g_cnt = (unsigned*)tc.take((size_t)n * 4);
-  unsigned* cnt1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
-  unsigned* toffs1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
-  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * nb1 * 4);
-  unsigned* pstart = (unsigned*)tc.take((size_t)(nb1 + 1) * 4);
-  unsigned* cnt2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
-  unsigned* toffs2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
-  unsigned* bstart = (unsigned*)tc.take(((size_t)nbuckets + 1) * 4);
-  unsigned long long* tile_max = (unsigned long long*)tc.take((size_t)ntiles * 16);
-  unsigned long long* firsts = (unsigned long long*)tc.take((size_t)nwords * 8);
-  unsigned* wordprefix = (unsigned*)tc.take((size_t)nwords * 4);
-  int* tilecnt = (int*)tc.take((size_t)nrt * 4);
-  int64_t* tileoff = (int64_t*)tc.take((size_t)nrt * 8);
-  unsigned long long* absmax = (unsigned long long*)&c->dscalars[28];   // [28], [29]: the value range (ah_hashing.h)
-  unsigned* oversize = (unsigned*)&c->dscalars[21];
-  unsigned long long* total = (unsigned long long*)&c->dscalars[22];
-  int* null_id = (int*)&c->dscalars[23];
-  AH_HIP(c, hipMemsetAsync(&c->dscalars[20], 0, 3 * sizeof(uint64_t), c->stream));
-  AH_HIP(c, hipMemsetAsync(&c->dscalars[28], 0, 2 * sizeof(uint64_t), c->stream));   // value range
-  AH_HIP(c, hipMemsetAsync(null_id, 0xFF, sizeof(uint64_t), c->stream));
+  unsigned long long *pkeys, *pvals, *qkeys, *qvals, *tile_max, *firsts;
+  unsigned *prows, *qrows, *g_cnt, *cnt1, *toffs1, *gsum, *pstart, *cnt2, *toffs2, *bstart, *wordprefix;
+  int* tilecnt; int64_t* tileoff;
+  bool fits;
+  int rc = part_reserve(c, true, [&](TempCarver& tc) {
+    tc.take(pkeys, n); tc.take(pvals, n); tc.take(qkeys, n); tc.take(qvals, n);
+    tc.take(prows, n); tc.take(qrows, n); tc.take(g_cnt, n);
+    tc.take(cnt1, ntiles * nb1); tc.take(toffs1, ntiles * nb1); tc.take(gsum, ngrp * nb1); tc.take(pstart, nb1 + 1);
+    tc.take(cnt2, nvt * nb2); tc.take(toffs2, nvt * nb2); tc.take(bstart, nbuckets + 1);
+    tc.take(tile_max, 2 * ntiles);
+    tc.take(firsts, nwords); tc.take(wordprefix, nwords); tc.take(tilecnt, nrt); tc.take(tileoff, nrt);
+  }, &fits);
+  if (rc != AH_OK || !fits) return rc;   // these temporaries do not fit: the caller's id-based path (a fraction of them) answers
+  unsigned long long* absmax = g.range();
+  unsigned* oversize = g.flags();   // … and the largest bucket beyond one wave (gs_local_kernel)
+  AH_HIP(c, hipMemsetAsync(g.done(), 0, 3 * sizeof(uint64_t), c->stream));   // done (unused), flags, total
+  AH_HIP(c, hipMemsetAsync(absmax, 0, 2 * sizeof(uint64_t), c->stream));
+  AH_HIP(c, hipMemsetAsync(g.null_id(), 0xFF, sizeof(uint64_t), c->stream));
   AH_HIP(c, hipMemsetAsync(firsts, 0, (size_t)nwords * 8, c->stream));
-  GsColumns col{(const unsigned long long*)keys, kvalid, koff, (const unsigned long long*)vals, vvalid, voff};
+  GsColumns col{g.keys, g.kvalid, g.koff, g.vals, g.vvalid, g.voff};
   // level 1
   tile_hist_kernel<GsDigit<GsColumns>><<<grid1, kThreads, 0, c->stream>>>(GsDigit<GsColumns>{col, lb, lb2, (unsigned)(nb1 - 1)}, n, nullptr, 1, nb1, cnt1);
   AH_LAUNCH_CHECK(c);
   if ((rc = launch_tile_offsets(c, cnt1, nb1, ntiles, n, gsum, toffs1, pstart)) != AH_OK) return rc;
   gs_scatter_kernel<GsColumns><<<grid1, kThreads, 0, c->stream>>>(col, n, nullptr, 1, lb, lb2, (unsigned)(nb1 - 1), nb1, toffs1, pkeys, pvals, prows,
-                                                                  is_f64 ? tile_max : nullptr);
+                                                                  g.is_f64 ? tile_max : nullptr);
   AH_LAUNCH_CHECK(c);
-  if (is_f64) {
+  if (g.is_f64) {
     gb_max_kernel<<<1, 1024, 0, c->stream>>>(tile_max, ntiles, absmax);
     AH_LAUNCH_CHECK(c);
     fx_range_check_kernel<<<1, 1, 0, c->stream>>>(absmax, oversize);   // a wide column goes to the id-based path (per-group scales)
@@ -1175,43 +1192,36 @@ static int gs_groupby(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t
   unsigned* g_first = prows;
   AH_HIP(c, hipMemsetAsync(g_first, 0xFF, (size_t)n * 4, c->stream));
   const unsigned lgrid = (unsigned)ah_ceil_div(nbuckets, 4);
-  if (is_f64) gs_local_kernel<true><<<lgrid, 256, 0, c->stream>>>(qkeys, qvals, qrows, bstart, nbuckets, absmax, g_key, g_sum, g_cnt, g_first, firsts, oversize);
-  else gs_local_kernel<false><<<lgrid, 256, 0, c->stream>>>(qkeys, qvals, qrows, bstart, nbuckets, absmax, g_key, g_sum, g_cnt, g_first, firsts, oversize);
+  with_bool(g.is_f64, [&](auto fx) { gs_local_kernel<fx.value><<<lgrid, 256, 0, c->stream>>>(qkeys, qvals, qrows, bstart, nbuckets, absmax, g_key, g_sum, g_cnt, g_first, firsts, oversize); });
   AH_LAUNCH_CHECK(c);
   // ids = rank of the first rows
   word_prefix_kernel<<<(unsigned)ah_ceil_div(nwords, kBlock), kBlock, 0, c->stream>>>(firsts, nwords, wordprefix, tilecnt);
   AH_LAUNCH_CHECK(c);
-  scan_kernel<<<1, 1024, 0, c->stream>>>(tilecnt, nrt, tileoff, total);
+  scan_kernel<<<1, 1024, 0, c->stream>>>(tilecnt, nrt, tileoff, g.total());
   AH_LAUNCH_CHECK(c);
   const unsigned egrid = ah_stream_grid(c, ah_ceil_div(n, kBlock));
-  if (is_f64) gs_emit_kernel<true><<<egrid, kBlock, 0, c->stream>>>(g_key, g_sum, g_cnt, g_first, n, firsts, wordprefix, tileoff, (unsigned long long*)out_keys,
-                                                                  (unsigned long long*)out_sums, (long long*)out_counts, (long long*)out_first_rows, null_id);
-  else gs_emit_kernel<false><<<egrid, kBlock, 0, c->stream>>>(g_key, g_sum, g_cnt, g_first, n, firsts, wordprefix, tileoff, (unsigned long long*)out_keys,
-                                                            (unsigned long long*)out_sums, (long long*)out_counts, (long long*)out_first_rows, null_id);
+  with_bool(g.is_f64, [&](auto fx) {
+    gs_emit_kernel<fx.value><<<egrid, kBlock, 0, c->stream>>>(g_key, g_sum, g_cnt, g_first, n, firsts, wordprefix, tileoff, g.out_keys, g.out_sums, g.out_counts, g.out_first_rows, g.null_id());
+  });
   AH_LAUNCH_CHECK(c);
-  { int mrc = ah_mailbox_read(c, (const unsigned long long*)&c->dscalars[21], 3, (unsigned long long*)&c->pinned[8]); if (mrc != AH_OK) return mrc; }   // oversize, total, null id
-  if (*(volatile unsigned*)&c->pinned[8]) return AH_OK;   // a bucket beyond one wave (a key with hundreds of rows): the id-based path redoes the call
-  if (out_ngroups) *out_ngroups = (int64_t) * (volatile uint64_t*)&c->pinned[9];
-  if (out_null_group) *out_null_group = *(volatile int32_t*)&c->pinned[10];
-  *used = 1;
-  return AH_OK;
+  return g.finish(false, outcome);   // a bucket beyond one wave (a key with hundreds of rows): the id-based path redoes the call
 }
 
 // 2.1 M … 17 M expected groups: the LDS-table aggregation needs 2048 … 8192 partitions — cut in two levels (the gs_* scatter
 // kernels: 64 × 64 partitions, runs as long as in the one-level cut of 64), then ONE workgroup per partition, tables dumped
-// side by side.  *used = 1: out_* hold the result.
-static int gb2_groupby(ah_ctx* c, int is_f64, int lp, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, const void* vals, const uint8_t* vvalid,
-                       int64_t voff, int64_t n, uint64_t* out_keys, void* out_sums, int64_t* out_counts, int64_t* out_first_rows, int64_t* out_ngroups,
-                       int32_t* out_null_group, int* used, bool reserve2 = true, const unsigned* hist = nullptr, double hist_scale = 0.0) {
-  // reserve2: the second level's scatter reserves its runs in fixed regions, one per final partition (gs_scatter_kernel, RES) — no
-  // histogram of the first level's output, no offsets table (2^26 rows, 8192 partitions: 254 + 98 µs).  Null keys all go to child 0 of
-  // parent 0 and would overflow its region: such columns keep the histogram.
-  if (kvalid || c->opt_groupby_reserve == 0) reserve2 = false;
-  // hist (the 2^21-row sample's [8][1024] row counts, when the caller ran it): the first level is the one-level cut's own reserving
-  // scatter (gb_scatter_kernel<…, RESERVE>: a region per parent and XCD, sized from the sample; 0.48 ms where the two-level machinery's
-  // level-1 kernel takes 0.64–0.72) and the second level tiles those regions
+// side by side.
+// reserve2: the second level's scatter reserves its runs in fixed regions, one per final partition (gs_scatter_kernel, RES) — no
+// histogram of the first level's output, no offsets table (2^26 rows, 8192 partitions: 254 + 98 µs).  Null keys all go to child 0 of
+// parent 0 and would overflow its region: such columns keep the histogram.  A child's region that was too small: Retry.
+// hist (the 2^21-row sample's [8][1024] row counts, when the caller ran it): the first level is the one-level cut's own reserving
+// scatter (gb_scatter_kernel<…, RESERVE>: a region per parent and XCD, sized from the sample; 0.48 ms where the two-level machinery's
+// level-1 kernel takes 0.64–0.72) and the second level tiles those regions
+static int gb2_groupby(const GbCall& g, int lp, bool reserve2, const unsigned* hist, double hist_scale, PartOutcome* outcome) {
+  ah_ctx* c = g.c;
+  const int64_t n = g.n;
+  *outcome = PartOutcome::Declined;
+  if (g.kvalid || c->opt_groupby_reserve == 0) reserve2 = false;
   const bool xreg = reserve2 && hist != nullptr;
-  *used = 0;
   const int lb2 = lp - lp / 2;
   const int nb2 = 1 << lb2, nb1 = 1 << (lp - lb2);
   const int64_t P = (int64_t)1 << lp;
@@ -1225,73 +1235,66 @@ static int gb2_groupby(ah_ctx* c, int is_f64, int lp, const uint64_t* keys, cons
   const int ncoarse = (int)ah_ceil_div(n, (int64_t)1 << cshift);
   if (ncoarse > kRecMaxBins || (1 << fpc_log2) > kRecMaxBins) return AH_OK;   // (beyond 2^30 rows: not this path's)
   const int64_t nfine = (int64_t)ncoarse << fpc_log2;
-  const size_t nrec = (size_t)ncoarse << cshift;                               // record places: every coarse bin whole (≥ n)
-  // the records of the coarse scatter lie over the first level's rows (free once the second level is cut), those of the fine scatter
-  // over the second level's (free once the aggregate pass has read them): 20 of the 32 bytes per place each
-  // first level's record arrays: dense (n rows) behind the offsets table; nb1 regions of cap1 rows (1.125 × the even share + a tile) + kMsTile spare rows otherwise
+  const size_t rec_bytes = ah_pad(((size_t)ncoarse << cshift) * sizeof(GbRec));   // record places: every coarse bin whole (≥ n)
+  // first level's row arrays: dense (n rows) behind the offsets table; nb1 regions of cap1 rows (1.125 × the even share + a tile) + kMsTile spare rows otherwise
   const unsigned cap1 = (unsigned)((((n / nb1) * 9 / 8 + kMsTile) + 15) & ~(int64_t)15);
   const int64_t xcap_rows = n + n / 2 + (int64_t)nb1 * kGbRegions * 96;   // gb_layout_kernel's regions (as in gb_cut_aggregate)
   const int64_t prows_n = xreg ? xcap_rows + kGbTile : (reserve2 ? nb1 * (int64_t)cap1 + kMsTile : n);
-  const size_t plevel = ah_pad((size_t)prows_n * 8) * 2 + ah_pad((size_t)prows_n * 4);
-  const size_t level = plevel > ah_pad(nrec * sizeof(GbRec)) ? plevel : ah_pad(nrec * sizeof(GbRec));   // … and the coarse records lie over them
-  const size_t extra = 0;
-  // second level's record arrays: dense (n rows) behind the offsets table; P regions of cap2 rows (1.25 × the even share) + kMsTile spare rows otherwise
+  // second level's row arrays: dense (n rows) behind the offsets table; P regions of cap2 rows (1.25 × the even share) + kMsTile spare rows otherwise
   const unsigned cap2 = (unsigned)((((n / P) * 5 / 4 + 64) + 15) & ~(int64_t)15);
   const int64_t qrows_n = reserve2 ? P * (int64_t)cap2 + kMsTile : n;
-  const size_t qlevel = ah_pad((size_t)qrows_n * 8) * 2 + ah_pad((size_t)qrows_n * 4);
-  const size_t qblock = qlevel > level + extra ? qlevel : level + extra;
-  const size_t need = (level + extra) + qblock + ah_pad((size_t)ntiles * nb1 * 4) * 2 + ah_pad((size_t)ngrp * nb1 * 4) + ah_pad((size_t)(nb1 + 1) * 4) +
-                      ah_pad((size_t)nvt * nb2 * 4) * 2 + ah_pad(((size_t)P + 1) * 4) + ah_pad((size_t)ntiles * 16) + ah_pad((size_t)kRecMaxBins * 4) + ah_pad((size_t)nfine * 4) +
-                      ah_pad((size_t)nfine * 8) + ah_pad(((size_t)P + 1) * 4) + ah_pad((size_t)(nb1 * kGbRegions + 1) * 4) * 5;
-  TempCarver tc;
-  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
-  if (rc != AH_OK) { c->err[0] = 0; return AH_OK; }   // these temporaries do not fit: *used stays 0 and the caller's id-based path (a fraction of them) answers
-  uint8_t* pbase = tc.take(level);
-  unsigned long long* pkeys = (unsigned long long*)pbase;
-  unsigned long long* pvals = (unsigned long long*)(pbase + ah_pad((size_t)prows_n * 8));
-  unsigned* prows = (unsigned*)(pbase + ah_pad((size_t)prows_n * 8) * 2);
-  uint8_t* qbase = tc.take(qblock);
-  unsigned long long* qkeys = (unsigned long long*)qbase;
-  unsigned long long* qvals = (unsigned long long*)(qbase + ah_pad((size_t)qrows_n * 8));
-  unsigned* qrows = (unsigned*)(qbase + ah_pad((size_t)qrows_n * 8) * 2);
-  GbRec* recs1 = (GbRec*)pkeys;
-  GbRec* recs2 = (GbRec*)qkeys;
-  unsigned* cnt1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
-  unsigned* toffs1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
-  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * nb1 * 4);
-  unsigned* pstart = (unsigned*)tc.take((size_t)(nb1 + 1) * 4);
-  unsigned* cnt2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
-  unsigned* toffs2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
-  unsigned* bstart = (unsigned*)tc.take(((size_t)P + 1) * 4);
-  unsigned long long* tile_max = (unsigned long long*)tc.take((size_t)ntiles * 16);
-  unsigned* ccursor = (unsigned*)tc.take((size_t)kRecMaxBins * 4);
-  unsigned* fcursor = (unsigned*)tc.take((size_t)nfine * 4);
-  int64_t* fprefix = (int64_t*)tc.take((size_t)nfine * 8);
-  unsigned* cursor2 = (unsigned*)tc.take(((size_t)P + 1) * 4);
   const int nsub = nb1 * kGbRegions;   // ≤ 512
-  unsigned* cursor1 = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
-  unsigned* pend = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
-  unsigned* sstart = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
-  unsigned* rstart1 = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
-  unsigned* rcap1 = (unsigned*)tc.take((size_t)(nsub + 1) * 4);
+  // Two blocks, each seen two ways (20 of the 32 bytes per place each):
+  //   p: the first level's rows {keys, values, rows} from the level-1 scatter until the level-2 scatter has read them, then the
+  //      aggregate pass's coarse records recs1 until gbr_split_kernel has read them;
+  //   q: the second level's rows from the level-2 scatter until the aggregate pass has read them, then gbr_split_kernel's fine
+  //      records recs2 until gbr_emit_kernel has read them.
+  struct Level { unsigned long long *keys, *vals; unsigned* rows; GbRec* recs; };
+  auto carve_level = [](TempCarver& tc, Level& l, int64_t rows, size_t at_least) {
+    const size_t kbytes = ah_pad((size_t)rows * 8), as_rows = 2 * kbytes + ah_pad((size_t)rows * 4);
+    uint8_t* base = tc.take(as_rows > at_least ? as_rows : at_least);   // the larger extent once, both views from the one pointer
+    if (!base) return;                                                     // (measuring)
+    l.keys = (unsigned long long*)base;
+    l.vals = (unsigned long long*)(base + kbytes);
+    l.rows = (unsigned*)(base + 2 * kbytes);
+    l.recs = (GbRec*)base;
+  };
+  Level p, q;
+  unsigned long long* tile_max;
+  unsigned *cnt1, *toffs1, *gsum, *pstart, *cnt2, *toffs2, *bstart, *ccursor, *fcursor, *cursor2, *cursor1, *pend, *sstart, *rstart1, *rcap1;
+  int64_t* fprefix;
+  size_t bin_cursor_bytes = 0, part_cursor_bytes = 0;   // {ccursor, fcursor} and {cursor2, cursor1} are adjacent: one fill job each
+  bool fits;
+  int rc = part_reserve(c, true, [&](TempCarver& tc) {
+    const size_t p_at = tc.used;
+    carve_level(tc, p, prows_n, rec_bytes);
+    carve_level(tc, q, qrows_n, tc.used - p_at);   // (at least block p's size)
+    tc.take(cnt1, ntiles * nb1); tc.take(toffs1, ntiles * nb1); tc.take(gsum, ngrp * nb1); tc.take(pstart, nb1 + 1);
+    tc.take(cnt2, nvt * nb2); tc.take(toffs2, nvt * nb2); tc.take(bstart, P + 1);
+    tc.take(tile_max, 2 * ntiles);
+    bin_cursor_bytes = tc.take(ccursor, kRecMaxBins); bin_cursor_bytes += tc.take(fcursor, nfine);
+    tc.take(fprefix, nfine);
+    part_cursor_bytes = tc.take(cursor2, P + 1); part_cursor_bytes += tc.take(cursor1, nsub + 1);   // the children's and the parents' cursors
+    tc.take(pend, nsub + 1); tc.take(sstart, nsub + 1); tc.take(rstart1, nsub + 1); tc.take(rcap1, nsub + 1);
+  }, &fits);
+  if (rc != AH_OK || !fits) return rc;   // these temporaries do not fit: the caller's id-based path (a fraction of them) answers
   GbTable gt{nullptr, nullptr, nullptr, nullptr, nullptr};   // no tables: the groups leave the aggregate pass as records
-  unsigned long long* absmax = (unsigned long long*)&c->dscalars[28];   // [28], [29]: the value range (ah_hashing.h)
-  unsigned* overflow = (unsigned*)&c->dscalars[21];
-  unsigned long long* total = (unsigned long long*)&c->dscalars[22];
-  int* null_id = (int*)&c->dscalars[23];
+  unsigned long long* absmax = g.range();
+  unsigned* overflow = g.flags();
   {
-    GbFill f;   // one launch: the call's scalars and both cursor arrays (adjacent)
+    GbFill f;   // one launch: the call's scalars and both pairs of cursor arrays
     f.njobs = 5;
-    f.p[0] = (uint4*)&c->dscalars[20]; f.n16[0] = 1; f.v[0] = 0u;                 // [20] unused, [21] overflow
-    f.p[1] = (uint4*)&c->dscalars[28]; f.n16[1] = 1; f.v[1] = 0u;                 // [28], [29] value range
-    f.p[2] = (uint4*)ccursor; f.n16[2] = (ah_pad((size_t)kRecMaxBins * 4) + ah_pad((size_t)nfine * 4)) / 16; f.v[2] = 0u;
-    f.p[3] = (uint4*)cursor2; f.n16[3] = (ah_pad(((size_t)P + 1) * 4) + ah_pad((size_t)(nsub + 1) * 4)) / 16; f.v[3] = 0u;   // the children's and the parents' cursors (adjacent)
-    f.p[4] = (uint4*)&c->dscalars[22]; f.n16[4] = 1; f.v[4] = 0u;                 // [22] total, [23] …
-    f.ones = (unsigned long long*)null_id;                                         // … null id: none (the last job's first word: the same thread)
+    f.p[0] = (uint4*)g.done(); f.n16[0] = 1; f.v[0] = 0u;                        // done (unused), flags
+    f.p[1] = (uint4*)absmax; f.n16[1] = 1; f.v[1] = 0u;
+    f.p[2] = (uint4*)ccursor; f.n16[2] = bin_cursor_bytes / 16; f.v[2] = 0u;
+    f.p[3] = (uint4*)cursor2; f.n16[3] = part_cursor_bytes / 16; f.v[3] = 0u;
+    f.p[4] = (uint4*)g.total(); f.n16[4] = 1; f.v[4] = 0u;                       // total, …
+    f.ones = (unsigned long long*)g.null_id();                                   // … null id: none (the last job's first word: the same thread)
     gb_fill_kernel<<<64, 256, 0, c->stream>>>(f);
     AH_LAUNCH_CHECK(c);
   }
-  GsColumns col{(const unsigned long long*)keys, kvalid, koff, (const unsigned long long*)vals, vvalid, voff};
+  GsColumns col{g.keys, g.kvalid, g.koff, g.vals, g.vvalid, g.voff};
+  unsigned long long* tile_max_f64 = g.is_f64 ? tile_max : nullptr;
   const unsigned* l2_start = pstart;
   int l2_parents = nb1, l2_sub8 = 0;
   if (xreg) {
@@ -1299,43 +1302,41 @@ static int gb2_groupby(ah_ctx* c, int is_f64, int lp, const uint64_t* keys, cons
     const int64_t gtiles = ah_ceil_div(n, kGbTile), xrows = ((gtiles + 7) >> 3) * kGbTile;
     gb_layout_kernel<<<1, 1024, 0, c->stream>>>(hist, lb1, n, xrows, hist_scale, xcap_rows, rstart1, rcap1, cursor1, overflow);
     AH_LAUNCH_CHECK(c);
-    gb_scatter_kernel<true, true><<<(unsigned)(((gtiles + 7) / 8) * 8), kThreads, 0, c->stream>>>((const unsigned long long*)keys, kvalid, koff, (const unsigned long long*)vals, vvalid, voff,
-                                                                                               n, lb1, nb1, gtiles, nullptr, pkeys, pvals, prows, is_f64 ? tile_max : nullptr,
-                                                                                               rstart1, rcap1, cursor1, overflow, (unsigned)xcap_rows);
+    gb_scatter_kernel<true, true><<<(unsigned)(((gtiles + 7) / 8) * 8), kThreads, 0, c->stream>>>(g.keys, g.kvalid, g.koff, g.vals, g.vvalid, g.voff, n, lb1, nb1, gtiles, nullptr, p.keys, p.vals, p.rows,
+                                                                                               tile_max_f64, rstart1, rcap1, cursor1, overflow, (unsigned)xcap_rows);
     AH_LAUNCH_CHECK(c);
-    gs_subregions_kernel<<<1, 1024, 0, c->stream>>>(rstart1, rcap1, cursor1, nb1, sstart, pend, overflow, is_f64 ? tile_max : nullptr, gtiles, absmax);
+    gs_subregions_kernel<<<1, 1024, 0, c->stream>>>(rstart1, rcap1, cursor1, nb1, sstart, pend, overflow, tile_max_f64, gtiles, absmax);
     AH_LAUNCH_CHECK(c);
     l2_start = sstart; l2_parents = nsub; l2_sub8 = 1;
   } else if (reserve2) {
     // level 1 reserves too: parent d owns the region [d · cap1, …); its runs come from all eight XCDs, 64 records (512 bytes of keys) at a
     // time — long enough not to share many lines (one cursor per partition only loses against the offsets table from 512 partitions on)
-    gs_scatter_kernel<GsColumns, true><<<grid1, kThreads, 0, c->stream>>>(col, n, nullptr, 1, lp, lb2, (unsigned)(nb1 - 1), nb1, nullptr, pkeys, pvals, prows,
-                                                                        is_f64 ? tile_max : nullptr, cursor1, cap1, (unsigned)(nb1 * (int64_t)cap1), overflow);
+    gs_scatter_kernel<GsColumns, true><<<grid1, kThreads, 0, c->stream>>>(col, n, nullptr, 1, lp, lb2, (unsigned)(nb1 - 1), nb1, nullptr, p.keys, p.vals, p.rows,
+                                                                        tile_max_f64, cursor1, cap1, (unsigned)(nb1 * (int64_t)cap1), overflow);
     AH_LAUNCH_CHECK(c);
-    if (is_f64) {
+    if (g.is_f64) {
       gb_max_kernel<<<1, 1024, 0, c->stream>>>(tile_max, ntiles, absmax);
       AH_LAUNCH_CHECK(c);
     }
-    gs_regions_kernel<<<1, 64, 0, c->stream>>>(cursor1, nb1, cap1, pstart, pend, overflow, is_f64 ? absmax : nullptr);   // nb1 ≤ 64
+    gs_regions_kernel<<<1, 64, 0, c->stream>>>(cursor1, nb1, cap1, pstart, pend, overflow, g.is_f64 ? absmax : nullptr);   // nb1 ≤ 64
     AH_LAUNCH_CHECK(c);
   } else {
-  tile_hist_kernel<GsDigit<GsColumns>><<<grid1, kThreads, 0, c->stream>>>(GsDigit<GsColumns>{col, lp, lb2, (unsigned)(nb1 - 1)}, n, nullptr, 1, nb1, cnt1);
-  AH_LAUNCH_CHECK(c);
-  if ((rc = launch_tile_offsets(c, cnt1, nb1, ntiles, n, gsum, toffs1, pstart)) != AH_OK) return rc;
-  gs_scatter_kernel<GsColumns><<<grid1, kThreads, 0, c->stream>>>(col, n, nullptr, 1, lp, lb2, (unsigned)(nb1 - 1), nb1, toffs1, pkeys, pvals, prows,
-                                                                  is_f64 ? tile_max : nullptr);
-  AH_LAUNCH_CHECK(c);
-  if (is_f64) {
-    gb_max_kernel<<<1, 1024, 0, c->stream>>>(tile_max, ntiles, absmax);
+    tile_hist_kernel<GsDigit<GsColumns>><<<grid1, kThreads, 0, c->stream>>>(GsDigit<GsColumns>{col, lp, lb2, (unsigned)(nb1 - 1)}, n, nullptr, 1, nb1, cnt1);
     AH_LAUNCH_CHECK(c);
-    fx_range_check_kernel<<<1, 1, 0, c->stream>>>(absmax, overflow);   // a wide column goes to the id-based path (per-group scales)
+    if ((rc = launch_tile_offsets(c, cnt1, nb1, ntiles, n, gsum, toffs1, pstart)) != AH_OK) return rc;
+    gs_scatter_kernel<GsColumns><<<grid1, kThreads, 0, c->stream>>>(col, n, nullptr, 1, lp, lb2, (unsigned)(nb1 - 1), nb1, toffs1, p.keys, p.vals, p.rows, tile_max_f64);
     AH_LAUNCH_CHECK(c);
+    if (g.is_f64) {
+      gb_max_kernel<<<1, 1024, 0, c->stream>>>(tile_max, ntiles, absmax);
+      AH_LAUNCH_CHECK(c);
+      fx_range_check_kernel<<<1, 1, 0, c->stream>>>(absmax, overflow);   // a wide column goes to the id-based path (per-group scales)
+      AH_LAUNCH_CHECK(c);
+    }
   }
-  }
-  GsRecords rec{pkeys, pvals, prows};
+  GsRecords rec{p.keys, p.vals, p.rows};
   if (reserve2) {
     const unsigned nvt2 = xreg ? (unsigned)(((ntiles + nsub + 7) / 8) * 8) : (unsigned)nvt;   // every region's last tile may be short
-    gs_scatter_kernel<GsRecords, true, false><<<nvt2, kThreads, 0, c->stream>>>(rec, n, l2_start, l2_parents, lp, 0, (unsigned)(nb2 - 1), nb2, nullptr, qkeys, qvals, qrows, nullptr,
+    gs_scatter_kernel<GsRecords, true, false><<<nvt2, kThreads, 0, c->stream>>>(rec, n, l2_start, l2_parents, lp, 0, (unsigned)(nb2 - 1), nb2, nullptr, q.keys, q.vals, q.rows, nullptr,
                                                                        cursor2, cap2, (unsigned)(P * (int64_t)cap2), overflow, pend, l2_sub8);
     AH_LAUNCH_CHECK(c);
   } else {
@@ -1343,38 +1344,27 @@ static int gb2_groupby(ah_ctx* c, int is_f64, int lp, const uint64_t* keys, cons
     AH_LAUNCH_CHECK(c);
     ms_offs2_kernel<<<(unsigned)nb1, kThreads, 0, c->stream>>>(cnt2, pstart, nb1, nb2, toffs2, bstart, n);
     AH_LAUNCH_CHECK(c);
-    gs_scatter_kernel<GsRecords, false, false><<<(unsigned)nvt, kThreads, 0, c->stream>>>(rec, n, pstart, nb1, lp, 0, (unsigned)(nb2 - 1), nb2, toffs2, qkeys, qvals, qrows, nullptr);
+    gs_scatter_kernel<GsRecords, false, false><<<(unsigned)nvt, kThreads, 0, c->stream>>>(rec, n, pstart, nb1, lp, 0, (unsigned)(nb2 - 1), nb2, toffs2, q.keys, q.vals, q.rows, nullptr);
     AH_LAUNCH_CHECK(c);
   }
   const unsigned* part_rows = reserve2 ? cursor2 : bstart;   // flat aggregate: counts of fixed regions, or the dense starts
   const int64_t part_cap = reserve2 ? (int64_t)cap2 : 0;
-  // aggregate: one workgroup per partition; its groups leave as records in the coarse bin of their first row (over p*: free now)
-  const GbRecOut ro{recs1, ccursor, cshift, ncoarse};
+  // aggregate: one workgroup per partition; its groups leave as records in the coarse bin of their first row (block p: free now)
+  const GbRecOut ro{p.recs, ccursor, cshift, ncoarse};
   const GbStaging nost{nullptr, nullptr, nullptr, nullptr};
-  if (is_f64) gb_aggregate_kernel<true, false, false, false, true><<<(unsigned)P, kThreads, 0, c->stream>>>(qkeys, qvals, qrows, part_rows, 0, gt, absmax, overflow, 1, nullptr, 0, nullptr, 0, 0, part_cap,
-                                                                                                           nullptr, nullptr, 0, nost, nullptr, nullptr, ro);
-  else gb_aggregate_kernel<false, false, false, false, true><<<(unsigned)P, kThreads, 0, c->stream>>>(qkeys, qvals, qrows, part_rows, 0, gt, absmax, overflow, 1, nullptr, 0, nullptr, 0, 0, part_cap,
-                                                                                                     nullptr, nullptr, 0, nost, nullptr, nullptr, ro);
+  with_bool(g.is_f64, [&](auto fx) {
+    gb_aggregate_kernel<fx.value, false, false, false, true><<<(unsigned)P, kThreads, 0, c->stream>>>(q.keys, q.vals, q.rows, part_rows, 0, gt, absmax, overflow, 1, nullptr, 0, nullptr, 0, 0, part_cap, nullptr, nullptr, 0, nost, nullptr, nullptr, ro);
+  });
   AH_LAUNCH_CHECK(c);
-  // coarse → fine bins (over q*: the aggregate pass has read them), ids of each fine bin's first group, the output
+  // coarse → fine bins (block q: the aggregate pass has read it), ids of each fine bin's first group, the output
   const int tiles_per_coarse = (int)(((int64_t)1 << cshift) / kRecTile);
-  gbr_split_kernel<<<(unsigned)(ncoarse * tiles_per_coarse), kThreads, 0, c->stream>>>(recs1, ccursor, cshift, fpc_log2, tiles_per_coarse, recs2, fcursor);
+  gbr_split_kernel<<<(unsigned)(ncoarse * tiles_per_coarse), kThreads, 0, c->stream>>>(p.recs, ccursor, cshift, fpc_log2, tiles_per_coarse, q.recs, fcursor);
   AH_LAUNCH_CHECK(c);
-  scan_kernel<<<1, 1024, 0, c->stream>>>((const int*)fcursor, nfine, fprefix, total);
+  scan_kernel<<<1, 1024, 0, c->stream>>>((const int*)fcursor, nfine, fprefix, g.total());
   AH_LAUNCH_CHECK(c);
-  if (is_f64) gbr_emit_kernel<true><<<(unsigned)nfine, kRecEmitThreads, 0, c->stream>>>(recs2, fcursor, fprefix, absmax, (unsigned long long*)out_keys, (unsigned long long*)out_sums,
-                                                                         (long long*)out_counts, (long long*)out_first_rows, null_id);
-  else gbr_emit_kernel<false><<<(unsigned)nfine, kRecEmitThreads, 0, c->stream>>>(recs2, fcursor, fprefix, absmax, (unsigned long long*)out_keys, (unsigned long long*)out_sums,
-                                                                   (long long*)out_counts, (long long*)out_first_rows, null_id);
+  with_bool(g.is_f64, [&](auto fx) { gbr_emit_kernel<fx.value><<<(unsigned)nfine, kRecEmitThreads, 0, c->stream>>>(q.recs, fcursor, fprefix, absmax, g.out_keys, g.out_sums, g.out_counts, g.out_first_rows, g.null_id()); });
   AH_LAUNCH_CHECK(c);
-  { int mrc = ah_mailbox_read(c, (const unsigned long long*)&c->dscalars[21], 3, (unsigned long long*)&c->pinned[8]); if (mrc != AH_OK) return mrc; }   // overflow, total, null id
-  if (reserve2 && (*(volatile unsigned*)&c->pinned[8] & 4u) && !(*(volatile unsigned*)&c->pinned[8] & 3u))   // a child's region was too small: once more behind a histogram
-    return gb2_groupby(c, is_f64, lp, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows, out_ngroups, out_null_group, used, false);
-  if (*(volatile unsigned*)&c->pinned[8]) return AH_OK;   // a partition outgrew its LDS table: the id-based path redoes the call
-  if (out_ngroups) *out_ngroups = (int64_t) * (volatile uint64_t*)&c->pinned[9];
-  if (out_null_group) *out_null_group = *(volatile int32_t*)&c->pinned[10];
-  *used = 1;
-  return AH_OK;
+  return g.finish(reserve2, outcome);   // Declined: a partition outgrew its LDS table, or a wide column — the id-based path redoes the call
 }
 
 // ≤ 2048 expected groups: no cut — every workgroup aggregates 2^18 consecutive rows of the columns in its LDS table and merges it
@@ -1785,105 +1775,79 @@ __global__ __launch_bounds__(1024) void gd_finish_kernel(GbTable rt, GbTable gt,
 }
 
 // guess_bits (nullable): the largest sampled |value| the caller's quick look saw — the scale guess then needs no sample pass here
-static int gb_direct(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, const void* vals, const uint8_t* vvalid,
-                     int64_t voff, int64_t n, uint64_t* out_keys, void* out_sums, int64_t* out_counts, int64_t* out_first_rows, int64_t* out_ngroups,
-                     int32_t* out_null_group, int* used, const unsigned long long* guess_bits = nullptr, bool lean = false,
+static int gb_direct(const GbCall& g, PartOutcome* outcome, const unsigned long long* guess_bits = nullptr, bool lean = false,
                      const unsigned long long* seed_keys = nullptr, unsigned seed_used = 0) {
-  *used = 0;
+  ah_ctx* c = g.c;
+  const int64_t n = g.n;
+  *outcome = PartOutcome::Declined;
   // a seed table at or beyond the admission limit must never reach gb_lds_slot, whose probe loop relies on empty slots being there
   // (the caller's "≤ 2800 distinct" gate already says so; this is the guard at the place that would hang)
   if (seed_keys && seed_used >= (unsigned)kSoftLimit) { seed_keys = nullptr; seed_used = 0; }
   const int64_t nslots = kGStride;
   const unsigned dgrid = (unsigned)ah_ceil_div(n, (int64_t)1 << kChunkLog2);
-  const size_t stage_rows = seed_keys ? (size_t)dgrid * kLSlots : 0;
-  const size_t need = ah_pad((size_t)nslots * 8) * 3 + ah_pad((size_t)nslots * 4) * 2 + ah_pad((size_t)dgrid * 8) + ah_pad(stage_rows * 8) * 2 + ah_pad(stage_rows * 4) * 2 +
-                      ah_pad((size_t)kLSlots * 8) * 3 + ah_pad((size_t)kLSlots * 4) * 2;
-  TempCarver tc;
-  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
-  if (rc != AH_OK) { c->err[0] = 0; return AH_OK; }   // these temporaries do not fit: *used stays 0 and the caller's id-based path (a fraction of them) answers
-  GbTable gt;
-  gt.key = (unsigned long long*)tc.take((size_t)nslots * 8);
-  gt.lo = (unsigned long long*)tc.take((size_t)nslots * 8);
-  gt.hi = (unsigned long long*)tc.take((size_t)nslots * 8);
-  gt.cnt = (unsigned*)tc.take((size_t)nslots * 4);
-  gt.first = (unsigned*)tc.take((size_t)nslots * 4);
-  unsigned* tile_range = (unsigned*)tc.take((size_t)dgrid * 8);
+  const size_t stage_rows = (size_t)dgrid * kLSlots;
+  GbTable gt, rt{nullptr, nullptr, nullptr, nullptr, nullptr};
   GbStaging st{nullptr, nullptr, nullptr, nullptr};
-  GbTable rt{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (seed_keys) {
-    st.lo = (unsigned long long*)tc.take(stage_rows * 8);
-    st.hi = (unsigned long long*)tc.take(stage_rows * 8);
-    st.cnt = (unsigned*)tc.take(stage_rows * 4);
-    st.first = (unsigned*)tc.take(stage_rows * 4);
-    rt.key = (unsigned long long*)tc.take((size_t)kLSlots * 8);
-    rt.lo = (unsigned long long*)tc.take((size_t)kLSlots * 8);
-    rt.hi = (unsigned long long*)tc.take((size_t)kLSlots * 8);
-    rt.cnt = (unsigned*)tc.take((size_t)kLSlots * 4);
-    rt.first = (unsigned*)tc.take((size_t)kLSlots * 4);
-  }
-  unsigned long long* absmax = (unsigned long long*)&c->dscalars[28];   // [28], [29]: the value range (ah_hashing.h)
-  unsigned* overflow = (unsigned*)&c->dscalars[21];
-  const unsigned long long* k64 = (const unsigned long long*)keys;
-  const unsigned long long* v64 = (const unsigned long long*)vals;
-  const bool guess = is_f64 && c->opt_groupby_scale_guess && n >= ((int64_t)1 << 22);
+  unsigned* tile_range;
+  bool fits;
+  int rc = part_reserve(c, true, [&](TempCarver& tc) {
+    gb_carve_table(tc, gt, nslots);
+    tc.take(tile_range, 2 * (size_t)dgrid);
+    if (seed_keys) {   // the workgroups' results for the seeded slots, and their sum
+      tc.take(st.lo, stage_rows); tc.take(st.hi, stage_rows); tc.take(st.cnt, stage_rows); tc.take(st.first, stage_rows);
+      gb_carve_table(tc, rt, kLSlots);
+    }
+  }, &fits);
+  if (rc != AH_OK || !fits) return rc;   // these temporaries do not fit: the caller's id-based path (a fraction of them) answers
+  unsigned long long* absmax = g.range();
+  unsigned* overflow = g.flags();
+  const bool guess = g.is_f64 && c->opt_groupby_scale_guess && n >= ((int64_t)1 << 22);
   const bool host_guess = guess && guess_bits != nullptr;
-  gd_prep_kernel<<<16, 256, 0, c->stream>>>(gt, nslots, tile_range, (int)(2 * dgrid), (unsigned long long*)&c->dscalars[20], absmax, host_guess ? 1 : 0,
-                                            host_guess ? *guess_bits : 0ull);
+  gd_prep_kernel<<<16, 256, 0, c->stream>>>(gt, nslots, tile_range, (int)(2 * dgrid), (unsigned long long*)g.done(), absmax, host_guess ? 1 : 0, host_guess ? *guess_bits : 0ull);
   AH_LAUNCH_CHECK(c);
-  if (is_f64 && !guess) {   // the fixed-point scale needs the largest finite |value| before the first addend is converted
-    absmax_kernel<<<ah_stream_grid(c, ah_ceil_div(n, (int64_t)kBlock * 8), 2), kBlock, 0, c->stream>>>(v64, vvalid, voff, n, absmax);
+  if (g.is_f64 && !guess) {   // the fixed-point scale needs the largest finite |value| before the first addend is converted
+    absmax_kernel<<<ah_stream_grid(c, ah_ceil_div(n, (int64_t)kBlock * 8), 2), kBlock, 0, c->stream>>>(g.vals, g.vvalid, g.voff, n, absmax);
     AH_LAUNCH_CHECK(c);
     fx_range_check_kernel<<<1, 1, 0, c->stream>>>(absmax, overflow);   // a wide column goes to the id-based path (per-group scales)
     AH_LAUNCH_CHECK(c);
   }
   if (guess && !host_guess) {   // … or a guess from a sample of its own (the caller had no quick look), checked like the host's
     const int64_t stride = (n / kGuessGroups) & ~(int64_t)63;
-    fx_sample_max_kernel<<<kGuessGroups / 4, 256, 0, c->stream>>>(v64, vvalid, voff, n, kGuessGroups, stride, absmax);
+    fx_sample_max_kernel<<<kGuessGroups / 4, 256, 0, c->stream>>>(g.vals, g.vvalid, g.voff, n, kGuessGroups, stride, absmax);
     AH_LAUNCH_CHECK(c);
     fx_guess_kernel<<<1, 1, 0, c->stream>>>(absmax);
     AH_LAUNCH_CHECK(c);
   }
-  const unsigned grid = dgrid;
+  // (guess implies Float64.  LEAN exists for Float64 only: an Int64 call launches <false, true> whatever `lean` says)
   unsigned* trng = guess ? tile_range : nullptr;
-  if (is_f64 && lean) gb_aggregate_kernel<true, true, true><<<grid, kThreads, 0, c->stream>>>(k64, v64, nullptr, nullptr, 1, gt, absmax, overflow, 2, kvalid, koff, vvalid, voff, n, 0, trng, seed_keys, seed_used, st);
-  else if (is_f64) gb_aggregate_kernel<true, true><<<grid, kThreads, 0, c->stream>>>(k64, v64, nullptr, nullptr, 1, gt, absmax, overflow, 2, kvalid, koff, vvalid, voff, n, 0, trng, seed_keys, seed_used, st);
-  else gb_aggregate_kernel<false, true><<<grid, kThreads, 0, c->stream>>>(k64, v64, nullptr, nullptr, 1, gt, absmax, overflow, 2, kvalid, koff, vvalid, voff, n, 0, nullptr, seed_keys, seed_used, st);
+  with_bool(g.is_f64, [&](auto fx) { with_bool(lean, [&](auto ln) {
+    gb_aggregate_kernel<fx.value, true, fx.value && ln.value><<<dgrid, kThreads, 0, c->stream>>>(g.keys, g.vals, nullptr, nullptr, 1, gt, absmax, overflow, 2, g.kvalid, g.koff, g.vvalid, g.voff, n, 0, trng, seed_keys, seed_used, st);
+  }); });
   AH_LAUNCH_CHECK(c);
   if (seed_keys) {   // the seeded slots of all workgroups, slot by slot
-    if (is_f64) gd_reduce_kernel<true><<<(unsigned)ah_ceil_div((int64_t)kLSlots, kRedSlots), 1024, 0, c->stream>>>(st, (int)dgrid, seed_keys, rt);
-    else gd_reduce_kernel<false><<<(unsigned)ah_ceil_div((int64_t)kLSlots, kRedSlots), 1024, 0, c->stream>>>(st, (int)dgrid, seed_keys, rt);
+    with_bool(g.is_f64, [&](auto fx) { gd_reduce_kernel<fx.value><<<(unsigned)ah_ceil_div((int64_t)kLSlots, kRedSlots), 1024, 0, c->stream>>>(st, (int)dgrid, seed_keys, rt); });
     AH_LAUNCH_CHECK(c);
   }
+  // the finish posts {flags, groups, null group} itself (done: zeroed, null id: −1 from gd_prep_kernel)
   unsigned long long* mb;
   unsigned long long seq, w[3];
   if ((rc = ah_mailbox_begin(c, &mb, &seq)) != AH_OK) return rc;
-  unsigned* done = (unsigned*)&c->dscalars[20];   // zeroed by gd_prep_kernel
-  int* null_id = (int*)&c->dscalars[23];           // −1 from gd_prep_kernel
-  if (is_f64) gd_finish_kernel<true><<<kFinBlocks, 1024, 0, c->stream>>>(rt, gt, tile_range, (int)dgrid, guess ? 1 : 0, absmax, overflow, done, null_id, (unsigned long long*)out_keys,
-                                                                        (unsigned long long*)out_sums, (long long*)out_counts, (long long*)out_first_rows, mb, seq);
-  else gd_finish_kernel<false><<<kFinBlocks, 1024, 0, c->stream>>>(rt, gt, tile_range, (int)dgrid, 0, absmax, overflow, done, null_id, (unsigned long long*)out_keys,
-                                                                  (unsigned long long*)out_sums, (long long*)out_counts, (long long*)out_first_rows, mb, seq);
+  with_bool(g.is_f64, [&](auto fx) {
+    gd_finish_kernel<fx.value><<<kFinBlocks, 1024, 0, c->stream>>>(rt, gt, tile_range, (int)dgrid, guess ? 1 : 0, absmax, overflow, g.done(), g.null_id(), g.out_keys, g.out_sums, g.out_counts, g.out_first_rows, mb, seq);
+  });
   AH_LAUNCH_CHECK(c);
-  if ((rc = ah_mailbox_wait(c, seq, 3, w)) != AH_OK) return rc;   // {overflow / redo flags, groups, null group}
-  if ((unsigned)w[0]) return AH_OK;
-  if (out_ngroups) *out_ngroups = (int64_t)w[1];
-  if (out_null_group) *out_null_group = (int32_t)(long long)w[2];
-  *used = 1;
+  if ((rc = ah_mailbox_wait(c, seq, 3, w)) != AH_OK) return rc;
+  *outcome = part_outcome(w, false, g.out_ngroups, g.out_null_group);
   return AH_OK;
 }
 
 // steps 1 … 4 of the partition-first group-by for 2^lp partitions.  hist (nullable): the sample's [8][1024] row counts — the
-// RESERVING scatter is used (no histogram pass; ah_partition.h 1b) and *redo = 4 says a region was too small (the caller runs the
-// call again without hist).  *used = 1: out_* hold the result.
-static int gb_cut_aggregate(ah_ctx* c, int is_f64, int lp, const unsigned* hist, double sample_scale, const uint64_t* keys, const uint8_t* kvalid, int64_t koff,
-                            const void* vals, const uint8_t* vvalid, int64_t voff, int64_t n, uint64_t* out_keys, void* out_sums, int64_t* out_counts,
-                            int64_t* out_first_rows, int64_t* out_ngroups, int32_t* out_null_group, int* used, unsigned* redo) {
-  *used = 0;
-  *redo = 0;
-  unsigned long long* absmax = (unsigned long long*)&c->dscalars[28];   // [28], [29]: the value range (ah_hashing.h)
-  unsigned* overflow = (unsigned*)&c->dscalars[21];
-  unsigned long long* total = (unsigned long long*)&c->dscalars[22];
-  int* null_id = (int*)&c->dscalars[23];
+// RESERVING scatter is used (no histogram pass; ah_partition.h 1b), and Retry says a region was too small or the regions' larger
+// arrays did not fit (the call is run again without hist: part_with_retry).
+static int gb_cut_aggregate(const GbCall& g, int lp, const unsigned* hist, double sample_scale, PartOutcome* outcome) {
+  ah_ctx* c = g.c;
+  const int64_t n = g.n;
+  *outcome = PartOutcome::Declined;
   const bool reserve = hist != nullptr;
   const int P = 1 << lp;
   const int64_t ntiles = ah_ceil_div(n, kGbTile), ngrp = ah_ceil_div(ntiles, kGroupTiles);
@@ -1894,85 +1858,66 @@ static int gb_cut_aggregate(ah_ctx* c, int is_f64, int lp, const unsigned* hist,
   const int64_t cap_rows = reserve ? n + n / 2 + (int64_t)P * kGbRegions * 96 : n;
   const int64_t rec_rows = reserve ? cap_rows + kGbTile : n;
   const int nreg = P * kGbRegions;
-  // ---- temporaries (one reservation)
-  const size_t table = reserve ? 0 : (size_t)P * (size_t)ntiles * 4;
-  const size_t need = ah_pad((size_t)nslots * 8) * 3 + ah_pad((size_t)nslots * 4) * 2 + ah_pad((size_t)nwords * 8) + ah_pad((size_t)nwords * 4) +
-                      ah_pad((size_t)nrt * 4) + ah_pad((size_t)nrt * 8) + ah_pad(table) * 2 + ah_pad((size_t)ngrp * P * 4) + ah_pad((size_t)(P + 1) * 4) +
-                      ah_pad((size_t)rec_rows * 8) * 2 + ah_pad((size_t)rec_rows * 4) + ah_pad((size_t)ntiles * 16) + ah_pad((size_t)(nreg + 1) * 4) * 5;
-  TempCarver tc;
-  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
-  if (rc != AH_OK && reserve) {
-    // the regions want 1.5 n rows of records (≈ 30 B/row) where the dense arrays behind a histogram want n (20 B/row): a call that does
-    // not fit THAT way is tried once more the other way (redo = 4: the caller runs the call again without the sample's histogram)
-    c->err[0] = 0;
-    *redo = 4u;
-    return AH_OK;
-  }
-  if (rc != AH_OK) return rc;
+  const size_t table = reserve ? 0 : (size_t)P * (size_t)ntiles;   // the (tile, partition) counts and offsets: behind a histogram only
   GbTable gt;
-  gt.key = (unsigned long long*)tc.take((size_t)nslots * 8);
-  gt.lo = (unsigned long long*)tc.take((size_t)nslots * 8);
-  gt.hi = (unsigned long long*)tc.take((size_t)nslots * 8);
-  gt.cnt = (unsigned*)tc.take((size_t)nslots * 4);
-  gt.first = (unsigned*)tc.take((size_t)nslots * 4);
-  unsigned long long* firsts = (unsigned long long*)tc.take((size_t)nwords * 8);
-  unsigned* wordprefix = (unsigned*)tc.take((size_t)nwords * 4);
-  int* tilecnt = (int*)tc.take((size_t)nrt * 4);
-  int64_t* tileoff = (int64_t*)tc.take((size_t)nrt * 8);
-  unsigned* cnt_tm = (unsigned*)tc.take(table);
-  unsigned* toffs = (unsigned*)tc.take(table);
-  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * P * 4);
-  unsigned* binstart = (unsigned*)tc.take((size_t)(P + 1) * 4);
-  unsigned long long* pkeys = (unsigned long long*)tc.take((size_t)rec_rows * 8);
-  unsigned long long* pvals = (unsigned long long*)tc.take((size_t)rec_rows * 8);
-  unsigned* prows = (unsigned*)tc.take((size_t)rec_rows * 4);
-  unsigned long long* tile_max = (unsigned long long*)tc.take((size_t)ntiles * 16);
-  unsigned* rstart = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
-  unsigned* rcap = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
-  unsigned* cursor = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
-  unsigned* vstart = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
-  unsigned* delta = (unsigned*)tc.take((size_t)(nreg + 1) * 4);
+  unsigned long long *firsts, *pkeys, *pvals, *tile_max;
+  unsigned *wordprefix, *cnt_tm, *toffs, *gsum, *binstart, *prows, *rstart, *rcap, *cursor, *vstart, *delta;
+  int* tilecnt; int64_t* tileoff;
+  size_t sums_bytes = 0;   // gt.lo, gt.hi, gt.cnt
+  bool fits;
+  // The regions want 1.5 n rows of records (≈ 30 B/row) where the dense arrays behind a histogram want n (20 B/row): a call that
+  // does not fit THAT way is tried once more the other way; one that does not fit behind the histogram either is an error.
+  int rc = part_reserve(c, reserve, [&](TempCarver& tc) {
+    sums_bytes = gb_carve_table(tc, gt, nslots);
+    tc.take(firsts, nwords); tc.take(wordprefix, nwords); tc.take(tilecnt, nrt); tc.take(tileoff, nrt);
+    tc.take(cnt_tm, table); tc.take(toffs, table); tc.take(gsum, ngrp * P); tc.take(binstart, P + 1);
+    tc.take(pkeys, rec_rows); tc.take(pvals, rec_rows); tc.take(prows, rec_rows);
+    tc.take(tile_max, 2 * ntiles);
+    tc.take(rstart, nreg + 1); tc.take(rcap, nreg + 1); tc.take(cursor, nreg + 1); tc.take(vstart, nreg + 1); tc.take(delta, nreg + 1);
+  }, &fits);
+  if (rc != AH_OK) return rc;
+  if (!fits) { *outcome = PartOutcome::Retry; return AH_OK; }
+  unsigned long long* absmax = g.range();
+  unsigned* overflow = g.flags();
   {
-    // everything the call starts from, one launch: empty tables (lo, hi, cnt are adjacent), no first rows, the call's scalars
+    // everything the call starts from, one launch: empty tables, no first rows, the call's scalars
     GbFill f;
     f.njobs = 7;
     f.p[0] = (uint4*)gt.key; f.n16[0] = ah_pad((size_t)nslots * 8) / 16; f.v[0] = 0xFFFFFFFFu;
-    f.p[1] = (uint4*)gt.lo; f.n16[1] = (ah_pad((size_t)nslots * 8) * 2 + ah_pad((size_t)nslots * 4)) / 16; f.v[1] = 0u;
+    f.p[1] = (uint4*)gt.lo; f.n16[1] = sums_bytes / 16; f.v[1] = 0u;
     f.p[2] = (uint4*)gt.first; f.n16[2] = ah_pad((size_t)nslots * 4) / 16; f.v[2] = 0xFFFFFFFFu;
     f.p[3] = (uint4*)firsts; f.n16[3] = ah_pad((size_t)nwords * 8) / 16; f.v[3] = 0u;
-    f.p[4] = (uint4*)&c->dscalars[20]; f.n16[4] = 1; f.v[4] = 0u;                 // [20] unused, [21] overflow / redo flags
-    f.p[5] = (uint4*)&c->dscalars[28]; f.n16[5] = 1; f.v[5] = 0u;                 // [28], [29] value range
-    f.p[6] = (uint4*)&c->dscalars[22]; f.n16[6] = 1; f.v[6] = 0u;                 // [22] total, [23] …
-    f.ones = (unsigned long long*)null_id;                                         // … null id: none
+    f.p[4] = (uint4*)g.done(); f.n16[4] = 1; f.v[4] = 0u;                        // done (unused), flags
+    f.p[5] = (uint4*)absmax; f.n16[5] = 1; f.v[5] = 0u;
+    f.p[6] = (uint4*)g.total(); f.n16[6] = 1; f.v[6] = 0u;                       // total, …
+    f.ones = (unsigned long long*)g.null_id();                                   // … null id: none
     gb_fill_kernel<<<(unsigned)(c->num_cu * 4), 256, 0, c->stream>>>(f);
     AH_LAUNCH_CHECK(c);
   }
-  const unsigned long long* k64 = (const unsigned long long*)keys;
-  const unsigned long long* v64 = (const unsigned long long*)vals;
+  unsigned long long* tile_max_f64 = g.is_f64 ? tile_max : nullptr;
   // ---- 1, 2: cut
   const unsigned tgrid = (unsigned)(((ntiles + 7) / 8) * 8);
   if (reserve) {
     gb_layout_kernel<<<1, 1024, 0, c->stream>>>(hist, lp, n, xrows, sample_scale, cap_rows, rstart, rcap, cursor, overflow);
     AH_LAUNCH_CHECK(c);
-    gb_scatter_kernel<true, true><<<tgrid, kThreads, 0, c->stream>>>(k64, kvalid, koff, v64, vvalid, voff, n, lp, P, ntiles, nullptr, pkeys, pvals, prows,
-                                                                     is_f64 ? tile_max : nullptr, rstart, rcap, cursor, overflow, (unsigned)cap_rows);
+    gb_scatter_kernel<true, true><<<tgrid, kThreads, 0, c->stream>>>(g.keys, g.kvalid, g.koff, g.vals, g.vvalid, g.voff, n, lp, P, ntiles, nullptr, pkeys, pvals, prows,
+                                                                     tile_max_f64, rstart, rcap, cursor, overflow, (unsigned)cap_rows);
     AH_LAUNCH_CHECK(c);
     // the regions as the aggregate pass walks them + the value range (gb_max_kernel and fx_range_check_kernel in one)
-    gb_segments_kernel<<<1, 1024, 0, c->stream>>>(rstart, rcap, cursor, P, n, vstart, delta, binstart, overflow, is_f64 ? tile_max : nullptr, ntiles, absmax);
+    gb_segments_kernel<<<1, 1024, 0, c->stream>>>(rstart, rcap, cursor, P, n, vstart, delta, binstart, overflow, tile_max_f64, ntiles, absmax);
     AH_LAUNCH_CHECK(c);
   } else {
-  gb_hist_kernel<<<tgrid, kGbHistThreads, 0, c->stream>>>(k64, kvalid, koff, n, lp, P, ntiles, cnt_tm);
-  AH_LAUNCH_CHECK(c);
-  if ((rc = launch_tile_offsets(c, cnt_tm, P, ntiles, n, gsum, toffs, binstart)) != AH_OK) return rc;
-  gb_scatter_kernel<true><<<tgrid, kThreads, 0, c->stream>>>(k64, kvalid, koff, v64, vvalid, voff, n, lp, P, ntiles, toffs, pkeys, pvals, prows,
-                                                       is_f64 ? tile_max : nullptr);
-  AH_LAUNCH_CHECK(c);
-  if (is_f64) {   // the fixed-point scale needs the largest finite |value| before the first addend is converted
-    gb_max_kernel<<<1, 1024, 0, c->stream>>>(tile_max, ntiles, absmax);
+    gb_hist_kernel<<<tgrid, kGbHistThreads, 0, c->stream>>>(g.keys, g.kvalid, g.koff, n, lp, P, ntiles, cnt_tm);
     AH_LAUNCH_CHECK(c);
-    fx_range_check_kernel<<<1, 1, 0, c->stream>>>(absmax, overflow);   // a wide column goes to the id-based path (per-group scales)
+    if ((rc = launch_tile_offsets(c, cnt_tm, P, ntiles, n, gsum, toffs, binstart)) != AH_OK) return rc;
+    gb_scatter_kernel<true><<<tgrid, kThreads, 0, c->stream>>>(g.keys, g.kvalid, g.koff, g.vals, g.vvalid, g.voff, n, lp, P, ntiles, toffs, pkeys, pvals, prows, tile_max_f64);
     AH_LAUNCH_CHECK(c);
-  }
+    if (g.is_f64) {   // the fixed-point scale needs the largest finite |value| before the first addend is converted
+      gb_max_kernel<<<1, 1024, 0, c->stream>>>(tile_max, ntiles, absmax);
+      AH_LAUNCH_CHECK(c);
+      fx_range_check_kernel<<<1, 1, 0, c->stream>>>(absmax, overflow);   // a wide column goes to the id-based path (per-group scales)
+      AH_LAUNCH_CHECK(c);
+    }
   }
   // ---- 3: aggregate
   // One workgroup fits a CU: one round of equal shares (≥ 2^17 records each: a table costs its 136 KiB to set up and to write
@@ -1984,45 +1929,42 @@ static int gb_cut_aggregate(ah_ctx* c, int is_f64, int lp, const unsigned* hist,
   const unsigned grid = (unsigned)ah_ceil_div(n, seg_rows);
   // (the row-by-row LEAN mode of the direct path was measured here too, on evenly spread keys: 1.227 ms against 1.217 at 2^16 groups,
   // 1.546 against 1.563 at 2^20 — nothing, although it frees eight registers: this pass is not bound by its instruction count alone)
+  // SEG walks the reserving scatter's regions; LEAN exists for Float64 behind SEG only (option groupby_lean 3).  The trailing arguments
+  // are the kernel's defaults up to the two region tables.
   const GbStaging nost{nullptr, nullptr, nullptr, nullptr};
-  if (reserve) {
-    if (is_f64 && c->opt_groupby_lean == 3) gb_aggregate_kernel<true, false, true, true><<<grid, kThreads, 0, c->stream>>>(pkeys, pvals, prows, binstart, P, gt, absmax, overflow, 0, nullptr, 0, nullptr, 0, 0, seg_rows, nullptr, nullptr, 0, nost, vstart, delta);
-    else if (is_f64) gb_aggregate_kernel<true, false, false, true><<<grid, kThreads, 0, c->stream>>>(pkeys, pvals, prows, binstart, P, gt, absmax, overflow, 0, nullptr, 0, nullptr, 0, 0, seg_rows, nullptr, nullptr, 0, nost, vstart, delta);
-    else gb_aggregate_kernel<false, false, false, true><<<grid, kThreads, 0, c->stream>>>(pkeys, pvals, prows, binstart, P, gt, absmax, overflow, 0, nullptr, 0, nullptr, 0, 0, seg_rows, nullptr, nullptr, 0, nost, vstart, delta);
-  } else {
-    if (is_f64) gb_aggregate_kernel<true><<<grid, kThreads, 0, c->stream>>>(pkeys, pvals, prows, binstart, P, gt, absmax, overflow, 0, nullptr, 0, nullptr, 0, 0, seg_rows);
-    else gb_aggregate_kernel<false><<<grid, kThreads, 0, c->stream>>>(pkeys, pvals, prows, binstart, P, gt, absmax, overflow, 0, nullptr, 0, nullptr, 0, 0, seg_rows);
-  }
+  with_bool(g.is_f64, [&](auto fx) { with_bool(reserve, [&](auto seg) { with_bool(c->opt_groupby_lean == 3, [&](auto ln) {
+    constexpr bool LEAN = fx.value && seg.value && ln.value;
+    gb_aggregate_kernel<fx.value, false, LEAN, seg.value><<<grid, kThreads, 0, c->stream>>>(pkeys, pvals, prows, binstart, P, gt, absmax, overflow, 0, nullptr, 0, nullptr, 0, 0, seg_rows, nullptr, nullptr, 0, nost,
+                                                                                           seg.value ? vstart : nullptr, seg.value ? delta : nullptr);
+  }); }); });
   AH_LAUNCH_CHECK(c);
   // ---- 4: rank the groups by first row, write them out
   gb_mark_kernel<<<ah_stream_grid(c, ah_ceil_div(nslots, kBlock)), kBlock, 0, c->stream>>>(gt.first, nslots, firsts);
   AH_LAUNCH_CHECK(c);
   word_prefix_kernel<<<(unsigned)ah_ceil_div(nwords, kBlock), kBlock, 0, c->stream>>>(firsts, nwords, wordprefix, tilecnt);
   AH_LAUNCH_CHECK(c);
-  scan_kernel<<<1, 1024, 0, c->stream>>>(tilecnt, nrt, tileoff, total);
+  scan_kernel<<<1, 1024, 0, c->stream>>>(tilecnt, nrt, tileoff, g.total());
   AH_LAUNCH_CHECK(c);
   const unsigned egrid = ah_stream_grid(c, ah_ceil_div(nslots, kBlock));
-  if (is_f64) gb_emit_kernel<true><<<egrid, kBlock, 0, c->stream>>>(gt, nslots, firsts, wordprefix, tileoff, absmax, (unsigned long long*)out_keys,
-                                                                  (unsigned long long*)out_sums, (long long*)out_counts, (long long*)out_first_rows, null_id, kGStride, kGSlots);
-  else gb_emit_kernel<false><<<egrid, kBlock, 0, c->stream>>>(gt, nslots, firsts, wordprefix, tileoff, absmax, (unsigned long long*)out_keys,
-                                                            (unsigned long long*)out_sums, (long long*)out_counts, (long long*)out_first_rows, null_id, kGStride, kGSlots);
+  with_bool(g.is_f64, [&](auto fx) {
+    gb_emit_kernel<fx.value><<<egrid, kBlock, 0, c->stream>>>(gt, nslots, firsts, wordprefix, tileoff, absmax, g.out_keys, g.out_sums, g.out_counts, g.out_first_rows, g.null_id(), kGStride, kGSlots);
+  });
   AH_LAUNCH_CHECK(c);
-  { int mrc = ah_mailbox_read(c, (const unsigned long long*)&c->dscalars[21], 3, (unsigned long long*)&c->pinned[8]); if (mrc != AH_OK) return mrc; }   // overflow, total, null id
-  *redo = *(volatile unsigned*)&c->pinned[8];
-  if (*redo) return AH_OK;   // a partition held far more keys than estimated (1), a wide column (2): the caller's path redoes the call; a region too small (4): once more with the histogram
-  if (out_ngroups) *out_ngroups = (int64_t) * (volatile uint64_t*)&c->pinned[9];
-  if (out_null_group) *out_null_group = *(volatile int32_t*)&c->pinned[10];
-  *used = 1;
-  return AH_OK;
+  // Declined: a partition held far more keys than estimated, or a wide column — the caller's path redoes the call
+  return g.finish(reserve, outcome);
 }
 
-// Called by ah_hash_sum_* before the id-based path.  *used = 1: out_* hold the result; 0: not applicable (small input,
-// too many expected groups, or the estimate was so far off that a partition's table overflowed) — the caller runs the
-// id-based path, which accepts anything.
-int ah_groupby_partitioned_try(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, const void* vals,
-                               const uint8_t* vvalid, int64_t voff, int64_t n, uint64_t* out_keys, void* out_sums, int64_t* out_counts,
-                               int64_t* out_first_rows, int64_t* out_ngroups, int32_t* out_null_group, int* used) {
-  *used = 0;
+// Which driver takes the call.  Declined: not applicable (small input, too many expected groups, or the estimate was so far off that
+// a partition's table overflowed).
+static int gb_dispatch(const GbCall& g, PartOutcome* outcome) {
+  ah_ctx* c = g.c;
+  const int64_t n = g.n;
+  const bool is_f64 = g.is_f64;
+  *outcome = PartOutcome::Declined;
+  // a reserving attempt, and once more behind a histogram when its regions were too small
+  auto two_level = [&](int lp2, const unsigned* hist, double scale) {
+    return part_with_retry([&](bool reserving, PartOutcome* o) { return gb2_groupby(g, lp2, reserving, reserving ? hist : nullptr, scale, o); }, outcome);
+  };
   const int mode = c->opt_groupby_partition;   // 0 never, 1 auto, 2: always sort-based, 3 / 4: always the two-level cut with 2^11 / 2^13 partitions, k ≥ 5: always LDS tables in 2^(k − 2) partitions (tests, measurements)
   if (mode == 0 || n >= kMaxRows || n < 1 || (mode == 1 && n < ((int64_t)1 << 21))) return AH_OK;
   // the scratch arena holds what must survive the temporaries' reservation further down: the look's key table + words, the sample's
@@ -2051,7 +1993,7 @@ int ah_groupby_partitioned_try(ah_ctx* c, int is_f64, const uint64_t* keys, cons
     const bool want_hist = c->opt_groupby_reserve != 0;
     AH_HIP(c, hipMemsetAsync(sample_acc, 0, kAccBytes + kHistBytes + kBmBytes, c->stream));
     const unsigned half_grid = (unsigned)ah_ceil_div(sgroups / 2, 16 * kSampleBatches);
-    gb_sample_kernel<<<2 * half_grid, 1024, 0, c->stream>>>((const unsigned long long*)keys, kvalid, koff, n, sgroups, stride, sample_bm, kBits - 1,
+    gb_sample_kernel<<<2 * half_grid, 1024, 0, c->stream>>>(g.keys, g.kvalid, g.koff, n, sgroups, stride, sample_bm, kBits - 1,
                                                             want_hist ? hist_buf : nullptr, xrows);
     AH_LAUNCH_CHECK(c);
     unsigned long long* mb;
@@ -2068,9 +2010,9 @@ int ah_groupby_partitioned_try(ah_ctx* c, int is_f64, const uint64_t* keys, cons
   };
   // ---- 0: how many partitions?
   int lp;
-  if (mode == -2) return gb_direct(c, is_f64, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows, out_ngroups, out_null_group, used);
-  if (mode == 3 || mode == 4) return gb2_groupby(c, is_f64, mode == 3 ? 11 : 13, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows, out_ngroups, out_null_group, used);
-  if (mode == 2) return gs_groupby(c, is_f64, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows, out_ngroups, out_null_group, used);
+  if (mode == -2) return gb_direct(g, outcome);
+  if (mode == 3 || mode == 4) return two_level(mode == 3 ? 11 : 13, nullptr, 0.0);
+  if (mode == 2) return gs_groupby(g, outcome);
   if (mode > 1) {
     lp = mode - 2 < 3 ? 3 : (mode - 2 > 10 ? 10 : mode - 2);
     if (c->opt_groupby_reserve != 0 && sgroups >= 2) {   // a forced partition count (tests, measurements): the sample runs for its histogram alone
@@ -2091,7 +2033,7 @@ int ah_groupby_partitioned_try(ah_ctx* c, int is_f64, const uint64_t* keys, cons
       AH_HIP(c, hipMemsetAsync(seedbuf, 0xFF, (size_t)kSlots * 8 + 64, c->stream));   // the empty table and the look's words (all "−1")
       if ((qrc = ah_mailbox_begin(c, &mb, &seq)) != AH_OK) return qrc;
       const int64_t qstride = ((n / kQlGroups) & ~(int64_t)(kQlRun - 1)) ? ((n / kQlGroups) & ~(int64_t)(kQlRun - 1)) : kQlRun;
-      gq_quicklook_kernel<<<kQlBlocks, 1024, 0, c->stream>>>((const unsigned long long*)keys, kvalid, koff, (const unsigned long long*)vals, vvalid, voff, n, qstride,
+      gq_quicklook_kernel<<<kQlBlocks, 1024, 0, c->stream>>>(g.keys, g.kvalid, g.koff, g.vals, g.vvalid, g.voff, n, qstride,
                                                              (unsigned long long*)seedbuf, (unsigned*)((uint8_t*)seedbuf + (size_t)kSlots * 8), mb, seq);
       AH_LAUNCH_CHECK(c);
       if ((qrc = ah_mailbox_wait(c, seq, 5, w)) != AH_OK) return qrc;
@@ -2108,8 +2050,7 @@ int ah_groupby_partitioned_try(ah_ctx* c, int is_f64, const uint64_t* keys, cons
         const unsigned pairs = (unsigned)(w[2] >> 32), rep = (unsigned)w[2];
         const bool lean = c->opt_groupby_lean != 0 && (c->opt_groupby_lean == 2 || (pairs >= 256 && rep * 8u < pairs));
         const bool seed = c->opt_groupby_seed != 0;
-        return gb_direct(c, is_f64, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows, out_ngroups, out_null_group, used, &w[1], lean,
-                         seed ? (const unsigned long long*)seedbuf : nullptr, (unsigned)w[3]);
+        return gb_direct(g, outcome, &w[1], lean, seed ? (const unsigned long long*)seedbuf : nullptr, (unsigned)w[3]);
       }
       // (The look's own two points — a 2^16-bit linear-counting bitmap read after half of the sample groups and after all — were
       // tried as the estimate for up to ≈ 10^5 groups too, sparing the 2^21-row sample below: evenly drawn keys came out within 2 %,
@@ -2127,7 +2068,7 @@ int ah_groupby_partitioned_try(ah_ctx* c, int is_f64, const uint64_t* keys, cons
     if (rc != AH_OK) return rc;
     const double dh = distinct(set_half, sampled / 2), ds = distinct(set_full, sampled);
     est = gb_extrapolate(ds, sampled, (double)n);
-    if (est <= 2048.0 && is_f64) return gb_direct(c, is_f64, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows, out_ngroups, out_null_group, used);
+    if (est <= 2048.0 && is_f64) return gb_direct(g, outcome);
     // Keys drawn evenly from C values give a curve that the second half of the sample must follow; a heavy-tailed column
     // (Zipf) keeps bringing new keys long after that curve has flattened, and its full distinct count is several times the
     // even-draw extrapolation — give those columns 4× the partitions rather than let the LDS tables overflow into the
@@ -2150,9 +2091,9 @@ int ah_groupby_partitioned_try(ah_ctx* c, int is_f64, const uint64_t* keys, cons
       if (est <= 8192.0 * kpp_many) {   // 17 M: 8192 partitions of ≤ 2100 expected keys (2^24 groups in 2^26 rows: 5.3 ms this way, 6.3 ms sort-based)
         int lp2 = 11;
         while (lp2 < 13 && est / (double)(1 << lp2) > 1280.0) lp2++;   // (2100 here: 2^22 groups 3 % slower, 2^23 3 % faster)
-        return gb2_groupby(c, is_f64, lp2, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows, out_ngroups, out_null_group, used, true, sample_hist, sample_scale);
+        return two_level(lp2, sample_hist, sample_scale);
       }
-      return gs_groupby(c, is_f64, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows, out_ngroups, out_null_group, used);
+      return gs_groupby(g, outcome);
     }
     if (heavy_tail) est *= 4.0;   // up to 1024 partitions (the loop below stops there)
     lp = 3;                                            // ≤ 1280 expected keys per partition (LDS table: 3584), a few partitions at least
@@ -2164,11 +2105,21 @@ int ah_groupby_partitioned_try(ah_ctx* c, int is_f64, const uint64_t* keys, cons
   }
   // the reserving scatter (ah_partition.h 1b) first when the sample left its histogram; a region that turned out too small: once more
   // with the histogram pass
-  unsigned redo = 0;
-  int rc = gb_cut_aggregate(c, is_f64, lp, sample_hist, sample_scale, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows,
-                            out_ngroups, out_null_group, used, &redo);
-  if (rc == AH_OK && !*used && sample_hist && redo == 4u)
-    rc = gb_cut_aggregate(c, is_f64, lp, nullptr, 0.0, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_sums, out_counts, out_first_rows, out_ngroups,
-                          out_null_group, used, &redo);
+  return part_with_retry([&](bool reserving, PartOutcome* o) {
+    const unsigned* hist = reserving ? sample_hist : nullptr;
+    return gb_cut_aggregate(g, lp, hist, hist ? sample_scale : 0.0, o);
+  }, outcome);
+}
+
+// Called by ah_hash_sum_* before the id-based path.  *used = 1: out_* hold the result; 0: the caller runs the id-based path, which
+// accepts anything.
+int ah_groupby_partitioned_try(ah_ctx* c, int is_f64, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, const void* vals,
+                               const uint8_t* vvalid, int64_t voff, int64_t n, uint64_t* out_keys, void* out_sums, int64_t* out_counts,
+                               int64_t* out_first_rows, int64_t* out_ngroups, int32_t* out_null_group, int* used) {
+  const GbCall g{c, is_f64 != 0, (const unsigned long long*)keys, kvalid, koff, (const unsigned long long*)vals, vvalid, voff, n, (unsigned long long*)out_keys,
+                 (unsigned long long*)out_sums, (long long*)out_counts, (long long*)out_first_rows, out_ngroups, out_null_group};
+  PartOutcome outcome = PartOutcome::Declined;
+  const int rc = gb_dispatch(g, &outcome);
+  *used = rc == AH_OK && outcome == PartOutcome::Done;
   return rc;
 }

@@ -32,7 +32,7 @@
 #include "ah_common.h"
 #include "ah_hashing.h"
 #include "ah_bins.h"
-#include "ah_partition.h"
+#include "ah_part_driver.h"
 #include "ah_msd.h"
 
 namespace {
@@ -777,65 +777,123 @@ __global__ __launch_bounds__(kThreads) void enc_look_kernel(const unsigned long 
 }  // namespace
 // distinct valid keys among the first `rows` (≤ 2^16) rows → *distinct.  One launch and a polled wait.
 int ah_encode_first_look(ah_ctx* c, const uint64_t* keys, const uint8_t* valid, int64_t off, int64_t rows, uint64_t* distinct) {
-  unsigned long long* acc = (unsigned long long*)&c->dscalars[33];   // [33] the count, [34] the workgroups that have finished: zero on entry, zeroed again by the last workgroup
+  unsigned long long* acc = (unsigned long long*)&c->dscalars[kDsEncLook];   // the count and (kDsEncLookDone) the workgroups that have finished: zero on entry, zeroed again by the last workgroup
   unsigned long long *mb, seq, w;
   int rc = ah_mailbox_begin(c, &mb, &seq);
   if (rc != AH_OK) return rc;
-  enc_look_kernel<<<kLookWgs, kThreads, 0, c->stream>>>((const unsigned long long*)keys, valid, off, rows, acc, (unsigned*)&c->dscalars[34], mb, seq);
+  enc_look_kernel<<<kLookWgs, kThreads, 0, c->stream>>>((const unsigned long long*)keys, valid, off, rows, acc, (unsigned*)&c->dscalars[kDsEncLookDone], mb, seq);
   AH_LAUNCH_CHECK(c);
   if ((rc = ah_mailbox_wait(c, seq, 1, &w)) != AH_OK) return rc;
   *distinct = (uint64_t)w;
   return AH_OK;
 }
 
+// ---- the host drivers ---------------------------------------------------------------------------------------------------------------
+namespace {
+// One unique / dictionary_encode call as the two drivers see it (the exported signatures' common tuple)
+struct EncCall {
+  ah_ctx* c;
+  const unsigned long long* keys; const uint8_t* valid; int64_t off, n;
+  int encode_nulls, lp, slots;
+  int32_t* out_ids; uint64_t* out_dict; int64_t* out_first_rows;
+  int64_t* out_ndict; int32_t* out_null_id;   // host
+  // the call's words of dscalars
+  unsigned* flags() const { return (unsigned*)&c->dscalars[kDsEncFlags]; }   // kPartOverflow: a partition held more keys than its table admits
+  unsigned long long* total() const { return (unsigned long long*)&c->dscalars[kDsEncTotal]; }
+  int* null_id() const { return (int*)&c->dscalars[kDsEncNullId]; }
+};
+// `slots` (kESlots or kESlots2: the drivers have checked) as a compile-time constant: f(std::integral_constant<int, slots>{})
+template <class F>
+void with_slots(int slots, F&& f) {
+  if (slots == kESlots2) f(std::integral_constant<int, kESlots2>{});
+  else f(std::integral_constant<int, kESlots>{});
+}
+
+// What both drivers do behind their cut — the partitions' tables, the first-occurrence bitmap and its ranks, the dictionary, the
+// records' ids — and the temporaries of that part.
+struct EncTables {
+  int64_t nslots, nwords, nrt;
+  unsigned long long *tab_key, *firsts;
+  unsigned *tab_first, *wordprefix; unsigned short* rec_slot; int* tilecnt; int64_t* tileoff;
+  uint8_t* fbytes;   // first occurrences marked by plain byte stores, packed into `firsts` by one pass; null: atomicOr on the bitmap's words
+  EncTables(const EncCall& e, int64_t P) : nslots(P * (e.slots + 8)), nwords(ah_ceil_div(e.n, 64)), nrt(rank_tiles(nwords)) {}
+  void carve(TempCarver& tc, int64_t n, bool byte_map) {
+    tc.take(rec_slot, n); tc.take(tab_key, nslots); tc.take(tab_first, nslots); tc.take(firsts, nwords);
+    fbytes = byte_map ? tc.take((size_t)nwords * 64) : nullptr;
+    tc.take(wordprefix, nwords); tc.take(tilecnt, nrt); tc.take(tileoff, nrt);
+  }
+  // the call's scalars and the map the first occurrences are marked in: one launch where three memsets were (≈ 4 µs of gap each)
+  int fill(const EncCall& e) const {
+    GbFill f;
+    f.njobs = 2;
+    f.p[0] = (uint4*)e.flags(); f.n16[0] = 1; f.v[0] = 0u;                       // flags, total
+    f.ones = (unsigned long long*)e.null_id();                                   // null id: none
+    if (fbytes) { f.p[1] = (uint4*)fbytes; f.n16[1] = (size_t)nwords * 4; }   // the byte map (the bitmap is then written whole)
+    else { f.p[1] = (uint4*)firsts; f.n16[1] = ah_pad((size_t)nwords * 8) / 16; }
+    f.v[1] = 0u;
+    gb_fill_kernel<<<(unsigned)(e.c->num_cu * 2), 256, 0, e.c->stream>>>(f);
+    AH_LAUNCH_CHECK(e.c);
+    return AH_OK;
+  }
+  // tables (one workgroup per final partition), ranks, the dictionary and — when ids are wanted — every record's id in rec_id
+  int run(const EncCall& e, int64_t P, const unsigned long long* pkeys, const unsigned* prows, const unsigned* binstart, bool batch, bool compact, int* rec_id) const {
+    ah_ctx* c = e.c;
+    unsigned long long* tab_key_out = compact ? nullptr : tab_key;
+    with_slots(e.slots, [&](auto s) { with_bool(batch, [&](auto b) {
+      enc_table_kernel<s.value, b.value><<<(unsigned)P, kThreads, 0, c->stream>>>(pkeys, prows, binstart, e.encode_nulls, tab_key_out, tab_first, e.out_ids ? rec_slot : nullptr, firsts, e.flags(), fbytes);
+    }); });
+    AH_LAUNCH_CHECK(c);
+    if (fbytes) {
+      enc_bytes_to_bits_kernel<<<(unsigned)ah_ceil_div(nwords, kBlock), kBlock, 0, c->stream>>>(fbytes, nwords, firsts);
+      AH_LAUNCH_CHECK(c);
+    }
+    word_prefix_kernel<<<(unsigned)ah_ceil_div(nwords, kBlock), kBlock, 0, c->stream>>>(firsts, nwords, wordprefix, tilecnt);
+    AH_LAUNCH_CHECK(c);
+    scan_kernel<<<1, 1024, 0, c->stream>>>(tilecnt, nrt, tileoff, e.total());
+    AH_LAUNCH_CHECK(c);
+    const int rc = enc_emit(c, compact, e.out_ids != nullptr, tab_key, tab_first, nslots, firsts, wordprefix, tileoff, (const uint64_t*)e.keys, e.n, e.out_dict, e.out_first_rows, e.null_id(), e.slots);
+    if (rc != AH_OK || !e.out_ids) return rc;
+    const int rsplit = P >= c->opt_encode_resolve_wgs ? 1 : (int)(c->opt_encode_resolve_wgs / P);   // ≥ 1024 workgroups: one per partition leaves a CU 16 waves
+    with_slots(e.slots, [&](auto s) { enc_resolve_kernel<s.value><<<(unsigned)(P * rsplit), kThreads, 0, c->stream>>>(rec_slot, tab_first, binstart, rec_id, rsplit); });
+    AH_LAUNCH_CHECK(c);
+    return AH_OK;
+  }
+};
+// {flags, total, null id} home → *used and the two host outputs.  A set flag: the global-table path redoes the call.
+int enc_finish(const EncCall& e, int* used) {
+  PartOutcome outcome;
+  const int rc = part_finish(e.c, kDsEncFlags, false, e.out_ndict, e.out_null_id, &outcome);
+  if (rc == AH_OK) *used = outcome == PartOutcome::Done;
+  return rc;
+}
+}  // namespace
+
 int ah_encode_partitioned_try(ah_ctx* c, const uint64_t* keys, const uint8_t* valid, int64_t off, int64_t n, int encode_nulls, int lp, int slots,
                               int32_t* out_ids, uint64_t* out_dict, int64_t* out_first_rows, int64_t* out_ndict, int32_t* out_null_id, int* used) {
   *used = 0;
   if (n < 1 || n >= kMaxRows || lp < 3 || lp > 10 || (slots != kESlots && slots != kESlots2)) return AH_OK;
+  const EncCall e{c, (const unsigned long long*)keys, valid, off, n, encode_nulls, lp, slots, out_ids, out_dict, out_first_rows, out_ndict, out_null_id};
   const int P = 1 << lp;
   const int64_t ntiles = ah_ceil_div(n, kGbTile), ngrp = ah_ceil_div(ntiles, kGroupTiles);
-  const int64_t nslots = (int64_t)P * (slots + 8);
-  const int64_t nwords = ah_ceil_div(n, 64), nrt = rank_tiles(nwords);
-  const size_t table = (size_t)P * (size_t)ntiles * 4;
-  const size_t need = ah_pad(table) * 2 + ah_pad((size_t)ngrp * P * 4) + ah_pad((size_t)(P + 1) * 4) + ah_pad((size_t)n * 8) + ah_pad((size_t)n * 4) + ah_pad((size_t)n * 2) +
-                      ah_pad((size_t)nslots * 8) + ah_pad((size_t)nslots * 4) + ah_pad((size_t)nwords * 8) + ah_pad((size_t)nwords * 4) + ah_pad((size_t)nrt * 4) + ah_pad((size_t)nrt * 8) + ah_pad((size_t)nwords * 64);
-  TempCarver tc;
-  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
+  // (the byte map from 1024 partitions on — ≈ 4·10^6 keys: below, the map's fill and packing cost what the atomics cost)
+  const bool byte_map = c->opt_encode_byte_map == 2 || (c->opt_encode_byte_map == 1 && lp >= 10);
+  EncTables t(e, P);
+  unsigned *cnt_tm, *toffs, *gsum, *binstart, *prows;
+  uint8_t* kbase = nullptr;   // the records' keys from the scatter until the table pass has given every record its slot, then their ids
+  bool fits;
+  int rc = part_reserve(c, false, [&](TempCarver& tc) {
+    tc.take(cnt_tm, (size_t)P * ntiles); tc.take(toffs, (size_t)P * ntiles); tc.take(gsum, ngrp * P); tc.take(binstart, P + 1);
+    kbase = tc.take((size_t)n * 8);
+    tc.take(prows, n);
+    t.carve(tc, n, byte_map);
+  }, &fits);
   if (rc != AH_OK) return rc;
-  unsigned* cnt_tm = (unsigned*)tc.take(table);
-  unsigned* toffs = (unsigned*)tc.take(table);
-  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * P * 4);
-  unsigned* binstart = (unsigned*)tc.take((size_t)(P + 1) * 4);
-  unsigned long long* pkeys = (unsigned long long*)tc.take((size_t)n * 8);
-  unsigned* prows = (unsigned*)tc.take((size_t)n * 4);
-  unsigned short* rec_slot = (unsigned short*)tc.take((size_t)n * 2);
-  unsigned long long* tab_key = (unsigned long long*)tc.take((size_t)nslots * 8);
-  unsigned* tab_first = (unsigned*)tc.take((size_t)nslots * 4);
-  unsigned long long* firsts = (unsigned long long*)tc.take((size_t)nwords * 8);
-  // (from 1024 partitions on — ≈ 4·10^6 keys: below, the map's fill and packing cost what the atomics cost)
-  uint8_t* fbytes = (c->opt_encode_byte_map == 2 || (c->opt_encode_byte_map == 1 && lp >= 10)) ? (uint8_t*)tc.take((size_t)nwords * 64) : nullptr;
-  unsigned* wordprefix = (unsigned*)tc.take((size_t)nwords * 4);
-  int* tilecnt = (int*)tc.take((size_t)nrt * 4);
-  int64_t* tileoff = (int64_t*)tc.take((size_t)nrt * 8);
-  int* rec_id = (int*)pkeys;   // the keys are not needed once every record knows its slot
-  unsigned* overflow = (unsigned*)&c->dscalars[30];
-  unsigned long long* total = (unsigned long long*)&c->dscalars[31];
-  int* null_id = (int*)&c->dscalars[32];
-  {
-    GbFill f;   // one launch where three memsets were (≈ 4 µs of gap each)
-    f.njobs = 2;
-    f.p[0] = (uint4*)&c->dscalars[30]; f.n16[0] = 1; f.v[0] = 0u;                 // [30] overflow, [31] total
-    f.ones = (unsigned long long*)null_id;                                         // [32] null id: none
-    if (fbytes) { f.p[1] = (uint4*)fbytes; f.n16[1] = (size_t)nwords * 4; }   // the byte map (the bitmap is then written whole)
-    else { f.p[1] = (uint4*)firsts; f.n16[1] = ah_pad((size_t)nwords * 8) / 16; }
-    f.v[1] = 0u;
-    gb_fill_kernel<<<(unsigned)(c->num_cu * 2), 256, 0, c->stream>>>(f);
-    AH_LAUNCH_CHECK(c);
-  }
-  const unsigned long long* k64 = (const unsigned long long*)keys;
+  unsigned long long* pkeys = (unsigned long long*)kbase;
+  int* rec_id = (int*)kbase;
+  if ((rc = t.fill(e)) != AH_OK) return rc;
   // ---- 1, 2: cut
   const unsigned tgrid = (unsigned)(((ntiles + 7) / 8) * 8);
-  gb_hist_kernel<<<tgrid, kGbHistThreads, 0, c->stream>>>(k64, valid, off, n, lp, P, ntiles, cnt_tm);
+  gb_hist_kernel<<<tgrid, kGbHistThreads, 0, c->stream>>>(e.keys, valid, off, n, lp, P, ntiles, cnt_tm);
   AH_LAUNCH_CHECK(c);
   // one workgroup per partition is only as fast as the largest partition: the sizes are looked at before the tables are built — through
   // the mailbox, posted by the prefix kernel itself and read while the offsets and the scatter are already running (a copy of
@@ -844,109 +902,58 @@ int ah_encode_partitioned_try(ah_ctx* c, const uint64_t* keys, const uint8_t* va
   unsigned long long *mb, seq, largest = 0;
   if ((rc = ah_mailbox_begin(c, &mb, &seq)) != AH_OK) return rc;
   if ((rc = launch_tile_offsets(c, cnt_tm, P, ntiles, n, gsum, toffs, binstart, mb, seq)) != AH_OK) return rc;
-  gb_scatter_kernel<false><<<tgrid, kThreads, 0, c->stream>>>(k64, valid, off, nullptr, nullptr, 0, n, lp, P, ntiles, toffs, pkeys, nullptr, prows, nullptr);
+  gb_scatter_kernel<false><<<tgrid, kThreads, 0, c->stream>>>(e.keys, valid, off, nullptr, nullptr, 0, n, lp, P, ntiles, toffs, pkeys, nullptr, prows, nullptr);
   AH_LAUNCH_CHECK(c);
   if ((rc = ah_mailbox_wait(c, seq, 1, &largest)) != AH_OK) return rc;
   if ((int64_t)largest * P > 3 * n && largest > (1u << 16)) return AH_OK;
-  // ---- 3: tables
+  // ---- 3, 4, 5: tables, ranks, ids per record
   // (measured at 2^26 rows: from 2^22 keys on — 1024 partitions — the compaction wins; below, the slots' few scattered stores are cheaper than its pass)
   const bool compact = c->opt_encode_dict_compact >= 2 || (c->opt_encode_dict_compact == 1 && lp >= 10);
-  unsigned long long* tab_key_out = compact ? nullptr : tab_key;
-  if (slots == kESlots2) { if (c->opt_encode_table_batch) enc_table_kernel<kESlots2, true><<<(unsigned)P, kThreads, 0, c->stream>>>(pkeys, prows, binstart, encode_nulls, tab_key_out, tab_first, out_ids ? rec_slot : nullptr, firsts, overflow, fbytes); else enc_table_kernel<kESlots2, false><<<(unsigned)P, kThreads, 0, c->stream>>>(pkeys, prows, binstart, encode_nulls, tab_key_out, tab_first, out_ids ? rec_slot : nullptr, firsts, overflow, fbytes); }
-  else { if (c->opt_encode_table_batch) enc_table_kernel<kESlots, true><<<(unsigned)P, kThreads, 0, c->stream>>>(pkeys, prows, binstart, encode_nulls, tab_key_out, tab_first, out_ids ? rec_slot : nullptr, firsts, overflow, fbytes); else enc_table_kernel<kESlots, false><<<(unsigned)P, kThreads, 0, c->stream>>>(pkeys, prows, binstart, encode_nulls, tab_key_out, tab_first, out_ids ? rec_slot : nullptr, firsts, overflow, fbytes); }
-  AH_LAUNCH_CHECK(c);
-  // ---- 4: rank
-  if (fbytes) {
-    enc_bytes_to_bits_kernel<<<(unsigned)ah_ceil_div(nwords, kBlock), kBlock, 0, c->stream>>>(fbytes, nwords, firsts);
-    AH_LAUNCH_CHECK(c);
-  }
-  word_prefix_kernel<<<(unsigned)ah_ceil_div(nwords, kBlock), kBlock, 0, c->stream>>>(firsts, nwords, wordprefix, tilecnt);
-  AH_LAUNCH_CHECK(c);
-  scan_kernel<<<1, 1024, 0, c->stream>>>(tilecnt, nrt, tileoff, total);
-  AH_LAUNCH_CHECK(c);
-  if ((rc = enc_emit(c, compact, out_ids != nullptr, tab_key, tab_first, nslots, firsts, wordprefix, tileoff, (const uint64_t*)k64, n, (uint64_t*)out_dict,
-                     (int64_t*)out_first_rows, null_id, slots)) != AH_OK) return rc;
-  if (out_ids) {
-    // ---- 5, 6: ids per record, then per row
-    const int rsplit = P >= c->opt_encode_resolve_wgs ? 1 : (int)(c->opt_encode_resolve_wgs / P);   // ≥ 1024 workgroups: one per partition leaves a CU 16 waves
-    if (slots == kESlots2) enc_resolve_kernel<kESlots2><<<(unsigned)(P * rsplit), kThreads, 0, c->stream>>>(rec_slot, tab_first, binstart, rec_id, rsplit);
-    else enc_resolve_kernel<kESlots><<<(unsigned)(P * rsplit), kThreads, 0, c->stream>>>(rec_slot, tab_first, binstart, rec_id, rsplit);
-    AH_LAUNCH_CHECK(c);
+  if ((rc = t.run(e, P, pkeys, prows, binstart, c->opt_encode_table_batch != 0, compact, rec_id)) != AH_OK) return rc;
+  if (out_ids) {   // ---- 6: ids per row
     launch_enc_unpermute(c, rec_id, prows, cnt_tm, toffs, P, ntiles, n, out_ids);
     AH_LAUNCH_CHECK(c);
   }
-  if ((rc = ah_mailbox_read(c, (const unsigned long long*)&c->dscalars[30], 3, (unsigned long long*)&c->pinned[8])) != AH_OK) return rc;   // overflow, total, null id
-  if (*(volatile unsigned*)&c->pinned[8]) return AH_OK;   // a partition held more keys than its table admits: the global-table path redoes the call
-  if (out_ndict) *out_ndict = (int64_t) * (volatile uint64_t*)&c->pinned[9];
-  if (out_null_id) *out_null_id = *(volatile int32_t*)&c->pinned[10];
-  *used = 1;
-  return AH_OK;
+  return enc_finish(e, used);
 }
-
 
 // Two cuts: 64 parents × 2^(lp − 6) partitions (lp = 11 … 13), for ≈ 4.5 … 36 M expected keys.  Same contract as above.
 int ah_encode_partitioned2_try(ah_ctx* c, const uint64_t* keys, const uint8_t* valid, int64_t off, int64_t n, int encode_nulls, int lp, int slots,
                                int32_t* out_ids, uint64_t* out_dict, int64_t* out_first_rows, int64_t* out_ndict, int32_t* out_null_id, int* used) {
   *used = 0;
   if (n < ((int64_t)1 << 20) || n >= kMaxRows || lp < 7 || lp > 13 || (slots != kESlots && slots != kESlots2)) return AH_OK;
+  const EncCall e{c, (const unsigned long long*)keys, valid, off, n, encode_nulls, lp, slots, out_ids, out_dict, out_first_rows, out_ndict, out_null_id};
   constexpr int lb1 = 6, nb1 = 1 << lb1;
   const int lb2 = lp - lb1, nb2 = 1 << lb2;
   const int64_t P = (int64_t)1 << lp;
   const int64_t ntiles = ah_ceil_div(n, kGbTile), ngrp = ah_ceil_div(ntiles, kGroupTiles), nvt = ((ntiles + nb1 + 7) / 8) * 8;
-  const int64_t nslots = P * (slots + 8);
-  const int64_t nwords = ah_ceil_div(n, 64), nrt = rank_tiles(nwords);
-  const size_t need = ah_pad((size_t)ntiles * nb1 * 4) * 2 + ah_pad((size_t)ngrp * nb1 * 4) + ah_pad((size_t)(nb1 + 1) * 4) + ah_pad((size_t)nvt * nb2 * 4) * 2 + ah_pad(((size_t)P + 1) * 4) +
-                      ah_pad((size_t)n * 8) * 2 + ah_pad((size_t)n * 4) * 2 + ah_pad((size_t)n * 2) * 2 + ah_pad((size_t)nslots * 8) + ah_pad((size_t)nslots * 4) +
-                      ah_pad((size_t)nwords * 8) + ah_pad((size_t)nwords * 4) + ah_pad((size_t)nrt * 4) + ah_pad((size_t)nrt * 8) + ah_pad((size_t)nwords * 64) + ah_pad((size_t)nvt * sizeof(TileRange));
-  TempCarver tc;
-  int rc = ah_temp_reserve(c, need, (void**)&tc.base);
+  EncTables t(e, P);
+  unsigned *cnt1, *toffs1, *gsum, *pstart, *cnt2, *toffs2, *bstart, *prows1, *prows2;
+  unsigned short* pj2;
+  TileRange* tile_table;
+  // each level's keys, then its records' ids: level 1's are dead after the level-2 scatter, level 2's once every record knows its slot
+  uint8_t *kbase1 = nullptr, *kbase2 = nullptr;
+  bool fits;
+  int rc = part_reserve(c, false, [&](TempCarver& tc) {
+    tc.take(cnt1, ntiles * nb1); tc.take(toffs1, ntiles * nb1); tc.take(gsum, ngrp * nb1); tc.take(pstart, nb1 + 1);
+    tc.take(cnt2, nvt * nb2); tc.take(toffs2, nvt * nb2); tc.take(bstart, P + 1);
+    kbase1 = tc.take((size_t)n * 8); kbase2 = tc.take((size_t)n * 8);
+    tc.take(prows1, n); tc.take(prows2, n); tc.take(pj2, n);
+    t.carve(tc, n, c->opt_encode_byte_map != 0);
+    tc.take(tile_table, nvt);
+  }, &fits);
   if (rc != AH_OK) return rc;
-  unsigned* cnt1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
-  unsigned* toffs1 = (unsigned*)tc.take((size_t)ntiles * nb1 * 4);
-  unsigned* gsum = (unsigned*)tc.take((size_t)ngrp * nb1 * 4);
-  unsigned* pstart = (unsigned*)tc.take((size_t)(nb1 + 1) * 4);
-  unsigned* cnt2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
-  unsigned* toffs2 = (unsigned*)tc.take((size_t)nvt * nb2 * 4);
-  unsigned* bstart = (unsigned*)tc.take(((size_t)P + 1) * 4);
-  unsigned long long* pkeys1 = (unsigned long long*)tc.take((size_t)n * 8);
-  unsigned long long* pkeys2 = (unsigned long long*)tc.take((size_t)n * 8);
-  unsigned* prows1 = (unsigned*)tc.take((size_t)n * 4);
-  unsigned* prows2 = (unsigned*)tc.take((size_t)n * 4);
-  unsigned short* pj2 = (unsigned short*)tc.take((size_t)n * 2);
-  unsigned short* rec_slot = (unsigned short*)tc.take((size_t)n * 2);
-  unsigned long long* tab_key = (unsigned long long*)tc.take((size_t)nslots * 8);
-  unsigned* tab_first = (unsigned*)tc.take((size_t)nslots * 4);
-  unsigned long long* firsts = (unsigned long long*)tc.take((size_t)nwords * 8);
-  uint8_t* fbytes = c->opt_encode_byte_map ? (uint8_t*)tc.take((size_t)nwords * 64) : nullptr;
-  unsigned* wordprefix = (unsigned*)tc.take((size_t)nwords * 4);
-  int* tilecnt = (int*)tc.take((size_t)nrt * 4);
-  int64_t* tileoff = (int64_t*)tc.take((size_t)nrt * 8);
-  int* rec_id2 = (int*)pkeys2;   // level-2 keys are dead once every record knows its slot
-  int* rec_id1 = (int*)pkeys1;   // level-1 keys are dead after the level-2 scatter
-  unsigned* overflow = (unsigned*)&c->dscalars[30];
-  unsigned long long* total = (unsigned long long*)&c->dscalars[31];
-  int* null_id = (int*)&c->dscalars[32];
-  {
-    GbFill f;   // one launch where three memsets were (≈ 4 µs of gap each)
-    f.njobs = 2;
-    f.p[0] = (uint4*)&c->dscalars[30]; f.n16[0] = 1; f.v[0] = 0u;                 // [30] overflow, [31] total
-    f.ones = (unsigned long long*)null_id;                                         // [32] null id: none
-    if (fbytes) { f.p[1] = (uint4*)fbytes; f.n16[1] = (size_t)nwords * 4; }   // the byte map (the bitmap is then written whole)
-    else { f.p[1] = (uint4*)firsts; f.n16[1] = ah_pad((size_t)nwords * 8) / 16; }
-    f.v[1] = 0u;
-    gb_fill_kernel<<<(unsigned)(c->num_cu * 2), 256, 0, c->stream>>>(f);
-    AH_LAUNCH_CHECK(c);
-  }
-  const unsigned long long* k64 = (const unsigned long long*)keys;
+  unsigned long long *pkeys1 = (unsigned long long*)kbase1, *pkeys2 = (unsigned long long*)kbase2;
+  int *rec_id1 = (int*)kbase1, *rec_id2 = (int*)kbase2;
+  if ((rc = t.fill(e)) != AH_OK) return rc;
   // ---- level 1: 64 parents by the top 6 bits of the key hash
   const unsigned tgrid = (unsigned)(((ntiles + 7) / 8) * 8);
-  gb_hist_kernel<<<tgrid, kGbHistThreads, 0, c->stream>>>(k64, valid, off, n, lb1, nb1, ntiles, cnt1);
+  gb_hist_kernel<<<tgrid, kGbHistThreads, 0, c->stream>>>(e.keys, valid, off, n, lb1, nb1, ntiles, cnt1);
   AH_LAUNCH_CHECK(c);
   if ((rc = launch_tile_offsets(c, cnt1, nb1, ntiles, n, gsum, toffs1, pstart)) != AH_OK) return rc;
-  gb_scatter_kernel<false><<<tgrid, kThreads, 0, c->stream>>>(k64, valid, off, nullptr, nullptr, 0, n, lb1, nb1, ntiles, toffs1, pkeys1, nullptr, prows1, nullptr);
+  gb_scatter_kernel<false><<<tgrid, kThreads, 0, c->stream>>>(e.keys, valid, off, nullptr, nullptr, 0, n, lb1, nb1, ntiles, toffs1, pkeys1, nullptr, prows1, nullptr);
   AH_LAUNCH_CHECK(c);
   // ---- level 2: every parent into 2^lb2 partitions
-  TileRange* tile_table = (TileRange*)tc.take((size_t)nvt * sizeof(TileRange));
   ms_tile_table_kernel<<<(unsigned)ah_ceil_div(nvt, kThreads), kThreads, 0, c->stream>>>(pstart, nullptr, nb1, (unsigned)nvt, tile_table);
   AH_LAUNCH_CHECK(c);
   tile_hist_kernel<E2Digit><<<(unsigned)nvt, kThreads, 0, c->stream>>>(E2Digit{pkeys1, prows1, lp, (unsigned)(nb2 - 1)}, n, pstart, nb1, nb2, cnt2, tile_table);
@@ -954,33 +961,15 @@ int ah_encode_partitioned2_try(ah_ctx* c, const uint64_t* keys, const uint8_t* v
   // (the partitions' balance: posted by the offsets kernel, read while the scatter runs — see ah_encode_partitioned_try)
   unsigned long long *mb, seq, largest = 0;
   if ((rc = ah_mailbox_begin(c, &mb, &seq)) != AH_OK) return rc;
-  ms_offs2_kernel<<<(unsigned)nb1, kThreads, 0, c->stream>>>(cnt2, pstart, nb1, nb2, toffs2, bstart, n, (unsigned*)&c->dscalars[35], (unsigned*)&c->dscalars[36], mb, seq);
+  ms_offs2_kernel<<<(unsigned)nb1, kThreads, 0, c->stream>>>(cnt2, pstart, nb1, nb2, toffs2, bstart, n, (unsigned*)&c->dscalars[kDsEncLargest], (unsigned*)&c->dscalars[kDsEncLargestDone], mb, seq);
   AH_LAUNCH_CHECK(c);
   e2_scatter_kernel<<<(unsigned)nvt, kThreads, 0, c->stream>>>(pkeys1, prows1, n, pstart, nb1, lp, (unsigned)(nb2 - 1), nb2, toffs2, pkeys2, prows2, pj2);
   AH_LAUNCH_CHECK(c);
   if ((rc = ah_mailbox_wait(c, seq, 1, &largest)) != AH_OK) return rc;
   if ((int64_t)largest * P > 3 * n && largest > (1u << 16)) return AH_OK;   // a key that owns a large share of the rows: the other path
-  // ---- tables, ranks, ids: as in the one-level path, one workgroup per final partition
-  const bool compact = c->opt_encode_dict_compact >= 1;
-  unsigned long long* tab_key_out = compact ? nullptr : tab_key;
-  if (slots == kESlots2) enc_table_kernel<kESlots2, false><<<(unsigned)P, kThreads, 0, c->stream>>>(pkeys2, prows2, bstart, encode_nulls, tab_key_out, tab_first, out_ids ? rec_slot : nullptr, firsts, overflow, fbytes);   // small partitions: the batched probe's registers cost more than its waits
-  else enc_table_kernel<kESlots, false><<<(unsigned)P, kThreads, 0, c->stream>>>(pkeys2, prows2, bstart, encode_nulls, tab_key_out, tab_first, out_ids ? rec_slot : nullptr, firsts, overflow, fbytes);   // small partitions: the batched probe's registers cost more than its waits
-  AH_LAUNCH_CHECK(c);
-  if (fbytes) {
-    enc_bytes_to_bits_kernel<<<(unsigned)ah_ceil_div(nwords, kBlock), kBlock, 0, c->stream>>>(fbytes, nwords, firsts);
-    AH_LAUNCH_CHECK(c);
-  }
-  word_prefix_kernel<<<(unsigned)ah_ceil_div(nwords, kBlock), kBlock, 0, c->stream>>>(firsts, nwords, wordprefix, tilecnt);
-  AH_LAUNCH_CHECK(c);
-  scan_kernel<<<1, 1024, 0, c->stream>>>(tilecnt, nrt, tileoff, total);
-  AH_LAUNCH_CHECK(c);
-  if ((rc = enc_emit(c, compact, out_ids != nullptr, tab_key, tab_first, nslots, firsts, wordprefix, tileoff, (const uint64_t*)k64, n, (uint64_t*)out_dict,
-                     (int64_t*)out_first_rows, null_id, slots)) != AH_OK) return rc;
-  if (out_ids) {
-    const int rsplit = P >= c->opt_encode_resolve_wgs ? 1 : (int)(c->opt_encode_resolve_wgs / P);   // ≥ 1024 workgroups: one per partition leaves a CU 16 waves
-    if (slots == kESlots2) enc_resolve_kernel<kESlots2><<<(unsigned)(P * rsplit), kThreads, 0, c->stream>>>(rec_slot, tab_first, bstart, rec_id2, rsplit);
-    else enc_resolve_kernel<kESlots><<<(unsigned)(P * rsplit), kThreads, 0, c->stream>>>(rec_slot, tab_first, bstart, rec_id2, rsplit);
-    AH_LAUNCH_CHECK(c);
+  // ---- tables, ranks, ids per record: as in the one-level path (small partitions: the batched probe's registers cost more than its waits)
+  if ((rc = t.run(e, P, pkeys2, prows2, bstart, false, c->opt_encode_dict_compact >= 1, rec_id2)) != AH_OK) return rc;
+  if (out_ids) {   // ---- ids home: virtual tile by virtual tile into level-1 order, then tile by tile into row order
     if (c->opt_encode_unperm2_group >= 2 && nb1 <= 64 && nb2 <= 128)
       e2_unpermute_group_kernel<4><<<(unsigned)(ah_ceil_div(ntiles + nb1, 4) + nb1), kThreads, 0, c->stream>>>(rec_id2, pj2, cnt2, toffs2, n, pstart, nb1, nb2, rec_id1);
     else
@@ -989,10 +978,5 @@ int ah_encode_partitioned2_try(ah_ctx* c, const uint64_t* keys, const uint8_t* v
     launch_enc_unpermute(c, rec_id1, prows1, cnt1, toffs1, nb1, ntiles, n, out_ids);
     AH_LAUNCH_CHECK(c);
   }
-  if ((rc = ah_mailbox_read(c, (const unsigned long long*)&c->dscalars[30], 3, (unsigned long long*)&c->pinned[8])) != AH_OK) return rc;   // overflow, total, null id
-  if (*(volatile unsigned*)&c->pinned[8]) return AH_OK;
-  if (out_ndict) *out_ndict = (int64_t) * (volatile uint64_t*)&c->pinned[9];
-  if (out_null_id) *out_null_id = *(volatile int32_t*)&c->pinned[10];
-  *used = 1;
-  return AH_OK;
+  return enc_finish(e, used);
 }

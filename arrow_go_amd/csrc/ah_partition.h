@@ -13,6 +13,11 @@ constexpr int kGbRows = kGbTile / kThreads;          // 4 per thread in the scat
 constexpr int kGbHistThreads = 256, kGbHistRows = kGbTile / kGbHistThreads;
 constexpr unsigned kKeyNull = 0x80000000u, kValNull = 0x40000000u, kRowMask = 0x1fffffffu;
 constexpr int64_t kMaxRows = (int64_t)1 << 29;
+// The flag word of a call (dscalars[kDsGbFlags] / [kDsEncFlags]; "overflow" or "redo" in the kernels' parameter lists), as the host reads it.
+// Any set bit voids the attempt.  (The sort-based group-by keeps its largest oversize bucket in the same word: as void as any.)
+constexpr unsigned kPartOverflow = 1u;      // a table or a partition held more keys than it admits (aggregate / table kernels)
+constexpr unsigned kPartWide = 2u;          // Float64: the value range is too wide for one fixed-point scale, or beyond the guess (fx_range_check_kernel and kin)
+constexpr unsigned kPartRegionSmall = 4u;   // reserving scatter: a region was too small (gb_layout / gb_scatter / gb_segments, gs_scatter / gs_regions / gs_subregions)
 
 // Any well-mixed hash will do: results depend on key EQUALITY and row order only.  (hashInt's low bits are fine, but
 // its bits above 12 depend on ever fewer key bits, and the partition number must not.)
