@@ -175,6 +175,12 @@ _SIGS = {
     "ah_hash_min_max_i64": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _pi64, _pi32],
     "ah_hash_min_max_u64": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _pi64, _pi32],
     "ah_hash_min_max_f64": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _pi64, _pi32],
+    "ah_group_ids": [_vp, _int, _vp, _i64, _vp, _vp, _pi64],
+    "ah_group_sum_i64": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp],
+    "ah_group_sum_f64": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp],
+    "ah_group_min_max_i64": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "ah_group_min_max_u64": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "ah_group_min_max_f64": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "ah_lz4_decompress_blocks": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _pi64],
     "ah_lz4_compress_blocks": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "ah_ipc_pack_body": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64],

@@ -44,6 +44,8 @@ struct ah_ctx {
   size_t scratch_bytes;
   void* temp;              // second grow-only arena: the temporaries of sort / group-by / var-length take (see ah_temp_reserve)
   size_t temp_bytes;
+  void* pack;              // third grow-only block: the packed key column of ah_group_ids (see ah_pack_reserve)
+  size_t pack_bytes;
   // small pinned staging block for *_host results (64 x 8 bytes)
   uint64_t* pinned;
   // small device block for scalar results / flags (64 x 8 bytes) followed by a
@@ -211,6 +213,12 @@ int ah_encode_partitioned_try(ah_ctx* ctx, const uint64_t* keys, const uint8_t* 
 // nulls encoded (the null key is a group) on the global-table path only (the partition-first encode would take the temp arena the caller's ids live in)
 int ah_encode_u64_groups(ah_ctx* ctx, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, int64_t n, int32_t* ids, uint64_t* out_keys,
                          int64_t* out_first_rows, int64_t* out_ngroups, int32_t* out_null_group);
+// internal (ah_hash.hip): the dense first-seen ids and first rows of ah_group_ids (ah_group_keys.hip) — over one column of 8-byte words (a
+// null is a group; every route of the encode, partition-first included: the caller holds nothing in the scratch or temp arena) and
+// over a checked tuple of 2 … 8 columns (the global table with the TupleKeys policy)
+int ah_encode_u64_first_seen(ah_ctx* ctx, const uint64_t* keys, const uint8_t* valid, int64_t off, int64_t n, int32_t* ids, int64_t* out_first_rows,
+                             int64_t* out_ngroups);
+int ah_encode_tuple_first_seen(ah_ctx* ctx, int ncols, const ah_group_key* keys, int64_t n, int32_t* ids, int64_t* out_first_rows, int64_t* out_ngroups);
 // … and by two cuts, 64 parents × 2^(lp − 6) partitions (lp = 11 … 13) with LDS tables of `slots` = 4096 or 8192 entries
 // distinct valid keys among the first `rows` (≤ 2^16) rows, counted exactly without a table in HBM (ah_hash_part.hip): one launch, one polled wait
 int ah_encode_first_look(ah_ctx* ctx, const uint64_t* keys, const uint8_t* valid, int64_t off, int64_t rows, uint64_t* distinct);
@@ -241,6 +249,10 @@ int ah_scratch_reserve(ah_ctx* ctx, size_t nbytes, void** out);
 // *out_of_memory (nullable) tells a failed hipMalloc — the one failure a caller may answer with a path that needs less — from a failed
 // synchronisation or hipFree, which is the caller's to return.
 int ah_temp_reserve(ah_ctx* ctx, size_t nbytes, void** out, bool* out_of_memory = nullptr);
+// A third grow-only block for ONE temporary that must outlive a whole encode: the packed key column of ah_group_ids.  The encode it
+// is handed to takes the scratch arena for its table and — on the partition-first route — the temp arena for its cut, and either
+// reservation may grow, which frees the old block: a column carved from one of them could be gone before it is read.
+int ah_pack_reserve(ah_ctx* ctx, size_t nbytes, void** out);
 // The carving of such a block: every piece starts on a 256-byte boundary.  A caller describes its pieces once (a function of a
 // TempCarver&), runs the description on a carver without a base to measure (take only advances `used`), reserves `used` and runs it
 // again on the block.

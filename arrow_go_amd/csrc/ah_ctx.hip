@@ -114,6 +114,7 @@ AH_EXPORT void ah_ctx_destroy(ah_ctx* c) {
   if (c->fcache.buf) (void)hipFree(c->fcache.buf);
   if (c->scan_recs) (void)hipFree(c->scan_recs);
   if (c->temp) (void)hipFree(c->temp);
+  if (c->pack) (void)hipFree(c->pack);
   (void)hipEventDestroy(c->ev_copy);
   (void)hipEventDestroy(c->ev_compute);
   (void)hipEventDestroy(c->t0);
@@ -257,6 +258,20 @@ int ah_temp_reserve(ah_ctx* c, size_t nbytes, void** out, bool* out_of_memory) {
     c->temp_bytes = want;
   }
   *out = c->temp;
+  return AH_OK;
+}
+
+int ah_pack_reserve(ah_ctx* c, size_t nbytes, void** out) {
+  if (nbytes > c->pack_bytes) {
+    AH_HIP(c, hipStreamSynchronize(c->stream));  // the old block may still be in use by enqueued kernels
+    if (c->pack) AH_HIP(c, hipFree(c->pack));
+    c->pack = nullptr;
+    c->pack_bytes = 0;
+    size_t want = (nbytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+    if (hipMalloc(&c->pack, want) != hipSuccess) { (void)hipGetLastError(); return ah_fail(c, AH_EHIP, "out of device memory (%zu bytes of packed keys)", want); }
+    c->pack_bytes = want;
+  }
+  *out = c->pack;
   return AH_OK;
 }
 

@@ -89,6 +89,80 @@ struct ByteKeys {
   }
 };
 
+// A key that is a TUPLE of columns (ah_group_ids, ah_group_keys.hip; no reference analogue — DESIGN.md §3.2).  The slot word is
+// {hash bits 63..32 | a row that holds the tuple}, as for ByteKeys; no row is materialised: load() hashes the row's columns where
+// they lie and same() compares them column by column — null flags first (two nulls are equal, the payload under a null is never
+// read), lengths before bytes.  NC is a compile-time bound (2, 4 or 8; unused entries are kColNone), so col[] is indexed
+// statically and stays in scalar registers.
+enum : int { kColNone = 0, kColFixed = 1, kColBits = 2, kColVar4 = 4, kColVar8 = 8 };
+struct KeyCol {
+  const void* offsets;   // kColVar4 / 8: the offsets entry of row 0 of the call
+  const uint8_t* data;   // kColVar*: the data buffer; kColFixed: the slot of row 0 of the call; kColBits: the bitmap (bit off + i)
+  const uint8_t* valid;  // nullable; bit off + i
+  int64_t off;
+  int kind, w;           // w: bytes per slot of a kColFixed column
+};
+constexpr uint64_t kNullColHash = 0xA0761D6478BD642Full, kTrueColHash = 0xE7037ED1A0B428DBull, kFalseColHash = 0x8EBC6AF09C88C6E3ull;
+
+__device__ __forceinline__ void col_row(const KeyCol& k, int64_t i, const uint8_t** p, int64_t* len) {
+  if (k.kind == kColVar4) row_at<4>(ByteRows{k.offsets, k.data, 0}, i, p, len);
+  else if (k.kind == kColVar8) row_at<8>(ByteRows{k.offsets, k.data, 0}, i, p, len);
+  else row_at<0>(ByteRows{nullptr, k.data, k.w}, i, p, len);
+}
+
+template <int NC>
+struct TupleKeys {
+  KeyCol col[NC];
+  static constexpr bool kLdsTable = false;
+  __device__ __forceinline__ bool load(int64_t i, unsigned long long* word, uint64_t* h) const {
+    uint64_t acc = 0x9E3779B97F4A7C15ull;
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+      const KeyCol& k = col[c];
+      if (k.kind == kColNone) continue;
+      uint64_t hc;
+      if (!ah_bit(k.valid, k.off + i)) {
+        hc = kNullColHash;
+      } else if (k.kind == kColBits) {
+        hc = ah_bit(k.data, k.off + i) ? kTrueColHash : kFalseColHash;
+      } else {
+        const uint8_t* p;
+        int64_t len;
+        col_row(k, i, &p, &len);
+        hc = hash_bytes(p, len);
+      }
+      acc = (acc ^ hc) * 0xFF51AFD7ED558CCDull;   // order matters: ("ab", "c") and ("c", "ab") start their probes apart
+      acc ^= acc >> 32;
+    }
+    *h = acc;
+    *word = (acc & 0xFFFFFFFF00000000ull) | (unsigned long long)(unsigned)i;  // never all-ones: i < 2^32 − 1
+    return true;
+  }
+  __device__ __forceinline__ bool same(unsigned long long cur, unsigned long long word, int64_t i) const {
+    if ((cur ^ word) >> 32) return false;
+    const int64_t r = (int64_t)(unsigned)cur;
+    if (r == i) return true;
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+      const KeyCol& k = col[c];
+      if (k.kind == kColNone) continue;
+      const int vi = ah_bit(k.valid, k.off + i), vr = ah_bit(k.valid, k.off + r);
+      if (vi != vr) return false;
+      if (!vi) continue;
+      if (k.kind == kColBits) {
+        if (ah_bit(k.data, k.off + i) != ah_bit(k.data, k.off + r)) return false;
+      } else {
+        const uint8_t *p, *q;
+        int64_t len, qlen;
+        col_row(k, i, &p, &len);
+        col_row(k, r, &q, &qlen);
+        if (len != qlen || !equal_bytes(p, q, len)) return false;
+      }
+    }
+    return true;
+  }
+};
+
 // dictionary of fixed-width keys: entry id = the value at its first row (the null entry: zeros, like a fresh builder slot)
 __global__ __launch_bounds__(kBlock) void fixed_dict_kernel(const uint8_t* __restrict__ data, int w, const long long* __restrict__ first_rows, int64_t ndict,
                                                              int null_id, uint8_t* __restrict__ dict) {
@@ -802,6 +876,42 @@ int ah_encode_u64_groups(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid,
   if (rc != AH_OK) return rc;
   *out_ngroups = res.ndict;
   *out_null_group = res.null_id;
+  return AH_OK;
+}
+
+// the ids of ah_group_ids (ah_group_keys.hip) over ONE column of 8-byte words — a key column as it is, or the packed column of a
+// narrow tuple: nulls are a group, and every route is open (LDS tables, first look, partition-first) — the caller keeps nothing in
+// the scratch or temp arena
+int ah_encode_u64_first_seen(ah_ctx* c, const uint64_t* keys, const uint8_t* valid, int64_t off, int64_t n, int32_t* ids, int64_t* out_first_rows,
+                             int64_t* out_ngroups) {
+  EncodeResult res;
+  int rc = encode_core(c, U64Keys{(const unsigned long long*)keys}, valid, off, n, /*encode_nulls=*/1, ids, nullptr, &res, out_first_rows);
+  if (rc != AH_OK) return rc;
+  *out_ngroups = res.ndict;
+  return AH_OK;
+}
+
+// … and over a tuple of columns the caller has checked (2 … 8 of them): the global table with TupleKeys.  A null is a value of its
+// column, so the table sees no validity of its own.
+int ah_encode_tuple_first_seen(ah_ctx* c, int ncols, const ah_group_key* keys, int64_t n, int32_t* ids, int64_t* out_first_rows, int64_t* out_ngroups) {
+  KeyCol cols[8];
+  for (int j = 0; j < 8; j++) {
+    cols[j] = KeyCol{nullptr, nullptr, nullptr, 0, kColNone, 0};
+    if (j >= ncols) continue;
+    const ah_group_key& k = keys[j];
+    if (k.offset_width == 4) cols[j] = KeyCol{(const int32_t*)k.offsets + k.off, k.data, k.valid, k.off, kColVar4, 0};
+    else if (k.offset_width == 8) cols[j] = KeyCol{(const long long*)k.offsets + k.off, k.data, k.valid, k.off, kColVar8, 0};
+    else if (k.bits) cols[j] = KeyCol{nullptr, k.data, k.valid, k.off, kColBits, 0};
+    else cols[j] = KeyCol{nullptr, k.data + k.off * (int64_t)k.byte_width, k.valid, k.off, kColFixed, k.byte_width};
+  }
+  EncodeResult res;
+  int rc;
+  auto run = [&](auto keys_of) { rc = encode_core(c, keys_of, nullptr, 0, n, /*encode_nulls=*/1, ids, nullptr, &res, out_first_rows); };
+  if (ncols <= 2) { TupleKeys<2> t; for (int j = 0; j < 2; j++) t.col[j] = cols[j]; run(t); }
+  else if (ncols <= 4) { TupleKeys<4> t; for (int j = 0; j < 4; j++) t.col[j] = cols[j]; run(t); }
+  else { TupleKeys<8> t; for (int j = 0; j < 8; j++) t.col[j] = cols[j]; run(t); }
+  if (rc != AH_OK) return rc;
+  *out_ngroups = res.ndict;
   return AH_OK;
 }
 

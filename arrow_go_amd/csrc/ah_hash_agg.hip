@@ -354,7 +354,103 @@ struct GroupCall {
   }
 };
 
-template <bool F64>   // values: Int64 / Uint64 bit patterns (wrapping sum) or doubles
+// ---- the aggregates as functions of (ids, ngroups): what ah_hash_* run behind their encode and ah_group_* run on the caller's ids -------
+// The temporaries of a sum, `bytes()` of the temp arena from `base` on: above 4096 groups the partitioned (value, id) pairs with their
+// histograms, sized for the two-pass partition; doubles: 128-bit fixed-point accumulators + flag word per group (room for max_groups)
+// and the absmax words.
+template <bool F64>
+struct SumTemps {
+  size_t pv, pi, ph, part_bytes, fxw, fxf;
+  SumTemps(int64_t n, int64_t max_groups) {
+    const int64_t nb = ah_ceil_div(n, 2048);
+    pv = (size_t)n * 8; pi = ah_pad((size_t)n * 4); ph = (size_t)256 * nb * 4;
+    part_bytes = 2 * (pv + pi) + 2 * ph + 256;
+    // (a wide Float64 column keeps one scale word per group there: more than the pairs only when the caller's groups outnumber its rows)
+    if (F64 && part_bytes < ah_pad((size_t)max_groups * 8)) part_bytes = ah_pad((size_t)max_groups * 8);
+    fxw = F64 ? ah_pad((size_t)max_groups * 8) : 0; fxf = F64 ? ah_pad((size_t)max_groups * 4) : 0;
+  }
+  size_t bytes() const { return part_bytes + 2 * fxw + fxf + 256; }
+  // doubles: the accumulators' places, and the largest finite |x| of the call enqueued (it does not need the ids)
+  int begin(ah_ctx* c, uint8_t* base, const void* vals, const uint8_t* vvalid, int64_t voff, int64_t n, FxAcc* fx) const {
+    *fx = FxAcc{nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (!F64) return AH_OK;
+    uint8_t* fxbase = base + part_bytes;
+    *fx = FxAcc{(unsigned long long*)fxbase, (unsigned long long*)(fxbase + fxw), (unsigned*)(fxbase + 2 * fxw),
+                (const unsigned long long*)(fxbase + 2 * fxw + fxf), nullptr};
+    AH_HIP(c, hipMemsetAsync((void*)fx->absmax, 0, 16, c->stream));
+    absmax_kernel<<<ah_stream_grid(c, ah_ceil_div(n, (int64_t)kBlock * 8), 2), kBlock, 0, c->stream>>>((const unsigned long long*)vals, vvalid, voff, n,
+                                                                                                        (unsigned long long*)fx->absmax);
+    AH_LAUNCH_CHECK(c);
+    return AH_OK;
+  }
+};
+
+template <bool F64>   // values: Int64 / Uint64 bit patterns (wrapping sum) or doubles; `part`: the temporaries, t.begin() has run
+int sum_over_ids(ah_ctx* c, const int32_t* ids, int64_t ng, const void* vals, const uint8_t* vvalid, int64_t voff, int64_t n, void* out_sums,
+                 int64_t* out_counts, const SumTemps<F64>& t, uint8_t* part, FxAcc fx) {
+  int rc;
+  const size_t pv = t.pv, pi = t.pi, ph = t.ph;
+  AH_HIP(c, hipMemsetAsync(out_sums, 0, (size_t)ng * 8, c->stream));
+  AH_HIP(c, hipMemsetAsync(out_counts, 0, (size_t)ng * sizeof(int64_t), c->stream));
+  bool wide = false;
+  if (F64) {
+    AH_HIP(c, hipMemsetAsync(fx.lo, 0, (size_t)ng * 8, c->stream));
+    AH_HIP(c, hipMemsetAsync(fx.hi, 0, (size_t)ng * 8, c->stream));
+    AH_HIP(c, hipMemsetAsync(fx.flags, 0, (size_t)ng * 4, c->stream));
+    // one scale for the call, or one per group?  (ah_hashing.h: a column spanning more than 42 binades)
+    AH_HIP(c, hipMemcpyAsync(&c->pinned[2], fx.absmax, 16, hipMemcpyDeviceToHost, c->stream));
+    AH_HIP(c, hipStreamSynchronize(c->stream));
+    wide = fx_wide(*(volatile uint64_t*)&c->pinned[2], *(volatile uint64_t*)&c->pinned[3]);
+    if (wide) {
+      unsigned long long* gmax = (unsigned long long*)part;   // the partition temporaries are idle on this route
+      AH_HIP(c, hipMemsetAsync(gmax, 0, (size_t)ng * 8, c->stream));
+      if ((rc = group_agg(c, ids, vals, vvalid, voff, n, nullptr, ng, AbsMax{gmax})) != AH_OK) return rc;
+      fx.gmax = gmax;
+    }
+  }
+  auto aggregate = [&](auto agg) -> int {
+    if (ng <= kLdsGroups || !c->opt_hash_sum_partition || wide || ng > kPartitionMaxGroups)
+      return group_agg(c, ids, vals, vvalid, voff, n, out_counts, ng, agg);
+    const int passes = ng <= kPartitionOnePass ? 1 : 2;
+    unsigned long long* pvals = (unsigned long long*)part;
+    unsigned* pids = (unsigned*)(part + pv);
+    unsigned* hist = (unsigned*)(part + pv + pi);
+    unsigned* offs = (unsigned*)(part + pv + pi + ph);
+    unsigned long long* avals = passes == 2 ? (unsigned long long*)(part + pv + pi + 2 * ph) : nullptr;
+    unsigned* aids = passes == 2 ? (unsigned*)((uint8_t*)avals + pv) : nullptr;
+    int prc = ah_partition_by_group(c, ids, (const unsigned long long*)vals, vvalid, voff, n, kBucketShift, passes, hist, offs, avals, aids, pvals, pids);
+    if (prc != AH_OK) return prc;
+    bucket_sum_kernel<<<(unsigned)ah_ceil_div(n, kChunkRows), kBlock, 0, c->stream>>>(pvals, pids, n, (unsigned long long*)out_counts, agg);
+    AH_LAUNCH_CHECK(c);
+    return AH_OK;
+  };
+  if constexpr (F64) {
+    if ((rc = aggregate(SumF64{fx, 0})) != AH_OK) return rc;
+    if (ng > 0) {
+      fx_finalize_kernel<<<(unsigned)ah_ceil_div(ng, kBlock), kBlock, 0, c->stream>>>(fx, ng, (double*)out_sums);
+      AH_LAUNCH_CHECK(c);
+    }
+  } else {
+    if ((rc = aggregate(SumI64{(unsigned long long*)out_sums})) != AH_OK) return rc;
+  }
+  return AH_OK;
+}
+
+template <int KIND>
+int min_max_over_ids(ah_ctx* c, const int32_t* ids, int64_t ng, const void* vals, const uint8_t* vvalid, int64_t voff, int64_t n, void* out_mins,
+                     void* out_maxs, int64_t* out_counts) {
+  if (ng <= 0) return AH_OK;
+  unsigned long long *mins = (unsigned long long*)out_mins, *maxs = (unsigned long long*)out_maxs, *counts = (unsigned long long*)out_counts;
+  const unsigned gblocks = (unsigned)ah_ceil_div(ng, kBlock);
+  min_max_init_kernel<<<gblocks, kBlock, 0, c->stream>>>(mins, maxs, counts, ng);
+  AH_LAUNCH_CHECK(c);
+  if (int rc = group_agg(c, ids, vals, vvalid, voff, n, counts, ng, MinMax<KIND>{mins, maxs})) return rc;
+  min_max_finish_kernel<KIND><<<gblocks, kBlock, 0, c->stream>>>(mins, maxs, counts, ng);
+  AH_LAUNCH_CHECK(c);
+  return AH_OK;
+}
+
+template <bool F64>
 int hash_sum(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t koff, const void* vals, const uint8_t* vvalid,
              int64_t voff, int64_t n, uint64_t* out_keys, void* out_sums, int64_t* out_counts, int64_t* out_first_rows,
              int64_t* out_ngroups_host, int32_t* out_null_group_host) {
@@ -370,70 +466,11 @@ int hash_sum(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t kof
     if (rc != AH_OK) return rc;
     if (used) return call.report();
   }
-  // temporaries behind the ids: above 4096 groups the partitioned (value, id) pairs with their histograms, sized for the two-pass
-  // partition; doubles: 128-bit fixed-point accumulators + flag word per group (≤ n + 1 groups) and the absmax words
-  const int64_t nb = ah_ceil_div(n, 2048);
-  const size_t pv = (size_t)n * 8, pi = ah_pad((size_t)n * 4), ph = (size_t)256 * nb * 4;
-  const size_t part_bytes = 2 * (pv + pi) + 2 * ph + 256;
-  const size_t fxw = F64 ? ah_pad((size_t)(n + 1) * 8) : 0, fxf = F64 ? ah_pad((size_t)(n + 1) * 4) : 0;
-  FxAcc fx{nullptr, nullptr, nullptr, nullptr, nullptr};
-  rc = call.groups(part_bytes + 2 * fxw + fxf + 256, [&]() -> int {
-    if (!F64) return AH_OK;
-    uint8_t* fxbase = call.extra + part_bytes;
-    fx = FxAcc{(unsigned long long*)fxbase, (unsigned long long*)(fxbase + fxw), (unsigned*)(fxbase + 2 * fxw),
-               (const unsigned long long*)(fxbase + 2 * fxw + fxf), nullptr};
-    AH_HIP(c, hipMemsetAsync((void*)fx.absmax, 0, 16, c->stream));
-    absmax_kernel<<<ah_stream_grid(c, ah_ceil_div(n, (int64_t)kBlock * 8), 2), kBlock, 0, c->stream>>>((const unsigned long long*)vals, vvalid, voff, n,
-                                                                                                        (unsigned long long*)fx.absmax);
-    AH_LAUNCH_CHECK(c);
-    return AH_OK;
-  });
+  const SumTemps<F64> t(n, n + 1);   // ≤ n + 1 groups
+  FxAcc fx;
+  rc = call.groups(t.bytes(), [&]() -> int { return t.begin(c, call.extra, vals, vvalid, voff, n, &fx); });
   if (rc != AH_OK) return rc;
-  const int64_t ng = call.ngroups;
-  uint8_t* part = call.extra;
-  AH_HIP(c, hipMemsetAsync(out_sums, 0, (size_t)ng * 8, c->stream));
-  AH_HIP(c, hipMemsetAsync(out_counts, 0, (size_t)ng * sizeof(int64_t), c->stream));
-  bool wide = false;
-  if (F64) {
-    AH_HIP(c, hipMemsetAsync(fx.lo, 0, (size_t)ng * 8, c->stream));
-    AH_HIP(c, hipMemsetAsync(fx.hi, 0, (size_t)ng * 8, c->stream));
-    AH_HIP(c, hipMemsetAsync(fx.flags, 0, (size_t)ng * 4, c->stream));
-    // one scale for the call, or one per group?  (ah_hashing.h: a column spanning more than 42 binades)
-    AH_HIP(c, hipMemcpyAsync(&c->pinned[2], fx.absmax, 16, hipMemcpyDeviceToHost, c->stream));
-    AH_HIP(c, hipStreamSynchronize(c->stream));
-    wide = fx_wide(*(volatile uint64_t*)&c->pinned[2], *(volatile uint64_t*)&c->pinned[3]);
-    if (wide) {
-      unsigned long long* gmax = (unsigned long long*)part;   // the partition temporaries are idle on this route
-      AH_HIP(c, hipMemsetAsync(gmax, 0, (size_t)ng * 8, c->stream));
-      if ((rc = group_agg(c, call.ids, vals, vvalid, voff, n, nullptr, ng, AbsMax{gmax})) != AH_OK) return rc;
-      fx.gmax = gmax;
-    }
-  }
-  auto aggregate = [&](auto agg) -> int {
-    if (ng <= kLdsGroups || !c->opt_hash_sum_partition || wide || ng > kPartitionMaxGroups)
-      return group_agg(c, call.ids, vals, vvalid, voff, n, out_counts, ng, agg);
-    const int passes = ng <= kPartitionOnePass ? 1 : 2;
-    unsigned long long* pvals = (unsigned long long*)part;
-    unsigned* pids = (unsigned*)(part + pv);
-    unsigned* hist = (unsigned*)(part + pv + pi);
-    unsigned* offs = (unsigned*)(part + pv + pi + ph);
-    unsigned long long* avals = passes == 2 ? (unsigned long long*)(part + pv + pi + 2 * ph) : nullptr;
-    unsigned* aids = passes == 2 ? (unsigned*)((uint8_t*)avals + pv) : nullptr;
-    int prc = ah_partition_by_group(c, call.ids, (const unsigned long long*)vals, vvalid, voff, n, kBucketShift, passes, hist, offs, avals, aids, pvals, pids);
-    if (prc != AH_OK) return prc;
-    bucket_sum_kernel<<<(unsigned)ah_ceil_div(n, kChunkRows), kBlock, 0, c->stream>>>(pvals, pids, n, (unsigned long long*)out_counts, agg);
-    AH_LAUNCH_CHECK(c);
-    return AH_OK;
-  };
-  if constexpr (F64) {
-    if ((rc = aggregate(SumF64{fx, 0})) != AH_OK) return rc;
-    if (ng > 0) {
-      fx_finalize_kernel<<<(unsigned)ah_ceil_div(ng, kBlock), kBlock, 0, c->stream>>>(fx, ng, (double*)out_sums);
-      AH_LAUNCH_CHECK(c);
-    }
-  } else {
-    if ((rc = aggregate(SumI64{(unsigned long long*)out_sums})) != AH_OK) return rc;
-  }
+  if ((rc = sum_over_ids<F64>(c, call.ids, call.ngroups, vals, vvalid, voff, n, out_sums, out_counts, t, call.extra, fx)) != AH_OK) return rc;
   return call.report();
 }
 
@@ -447,17 +484,49 @@ int hash_min_max(ah_ctx* c, const uint64_t* keys, const uint8_t* kvalid, int64_t
   int rc = call.check(voff, keys && vals && out_keys && out_mins && out_maxs && out_counts, &empty);
   if (rc != AH_OK || empty) return rc;
   if ((rc = call.groups(0, [] { return AH_OK; })) != AH_OK) return rc;
-  const int64_t ng = call.ngroups;
-  if (ng > 0) {
-    unsigned long long *mins = (unsigned long long*)out_mins, *maxs = (unsigned long long*)out_maxs, *counts = (unsigned long long*)out_counts;
-    const unsigned gblocks = (unsigned)ah_ceil_div(ng, kBlock);
-    min_max_init_kernel<<<gblocks, kBlock, 0, c->stream>>>(mins, maxs, counts, ng);
-    AH_LAUNCH_CHECK(c);
-    if ((rc = group_agg(c, call.ids, vals, vvalid, voff, n, counts, ng, MinMax<KIND>{mins, maxs})) != AH_OK) return rc;
-    min_max_finish_kernel<KIND><<<gblocks, kBlock, 0, c->stream>>>(mins, maxs, counts, ng);
-    AH_LAUNCH_CHECK(c);
-  }
+  if ((rc = min_max_over_ids<KIND>(c, call.ids, call.ngroups, vals, vvalid, voff, n, out_mins, out_maxs, out_counts)) != AH_OK) return rc;
   return call.report();
+}
+
+// ---- the same aggregates over the caller's ids (ah_group_*): 0 ≤ ids[i] < ngroups is the caller's word (group_agg_kernel leaves a row
+// that breaks it out, the partitioned sum above 4096 groups trusts it)
+int group_check(ah_ctx* c, const char* who, int64_t ngroups, int64_t voff, int64_t n, bool buffers, bool* nothing) {
+  *nothing = true;
+  if (n < 0 || voff < 0 || ngroups < 0) return ah_fail(c, AH_EINVALID, "%s: negative length/offset", who);
+  if (ngroups > 0x7fffffffll) return ah_fail(c, AH_EINVALID, "%s: more than 2^31 - 1 groups", who);
+  if (n > ((int64_t)1 << 30)) return ah_fail(c, AH_ENOTIMPL, "%s: more than 2^30 rows per call", who);
+  if (ngroups == 0) return AH_OK;
+  if (!buffers) return ah_fail(c, AH_EINVALID, "%s: null buffer", who);
+  *nothing = false;
+  return AH_OK;
+}
+
+template <bool F64>
+int group_sum(ah_ctx* c, const int32_t* ids, int64_t ngroups, const void* vals, const uint8_t* vvalid, int64_t voff, int64_t n, void* out_sums,
+              int64_t* out_counts) {
+  bool nothing;
+  int rc = group_check(c, "group_sum", ngroups, voff, n, out_sums && out_counts && (n == 0 || (ids && vals)), &nothing);
+  if (rc != AH_OK || nothing) return rc;
+  if (n == 0) {   // no rows: every group is empty
+    AH_HIP(c, hipMemsetAsync(out_sums, 0, (size_t)ngroups * 8, c->stream));
+    AH_HIP(c, hipMemsetAsync(out_counts, 0, (size_t)ngroups * sizeof(int64_t), c->stream));
+    return AH_OK;
+  }
+  const SumTemps<F64> t(n, ngroups);
+  void* arena = nullptr;
+  if ((rc = ah_temp_reserve(c, t.bytes(), &arena)) != AH_OK) return rc;
+  FxAcc fx;
+  if ((rc = t.begin(c, (uint8_t*)arena, vals, vvalid, voff, n, &fx)) != AH_OK) return rc;
+  return sum_over_ids<F64>(c, ids, ngroups, vals, vvalid, voff, n, out_sums, out_counts, t, (uint8_t*)arena, fx);
+}
+
+template <int KIND>
+int group_min_max(ah_ctx* c, const int32_t* ids, int64_t ngroups, const void* vals, const uint8_t* vvalid, int64_t voff, int64_t n, void* out_mins,
+                  void* out_maxs, int64_t* out_counts) {
+  bool nothing;
+  int rc = group_check(c, "group_min_max", ngroups, voff, n, out_mins && out_maxs && out_counts && (n == 0 || (ids && vals)), &nothing);
+  if (rc != AH_OK || nothing) return rc;
+  return min_max_over_ids<KIND>(c, ids, ngroups, vals, vvalid, voff, n, out_mins, out_maxs, out_counts);
 }
 
 }  // namespace
@@ -503,4 +572,34 @@ AH_EXPORT int ah_hash_min_max_f64(ah_ctx* c, const uint64_t* keys, const uint8_t
   AH_ENTER(c);
   return hash_min_max<kF64>(c, keys, kvalid, koff, vals, vvalid, voff, n, out_keys, out_mins, out_maxs, out_counts, out_first_rows,
                             out_ngroups_host, out_null_group_host);
+}
+
+AH_EXPORT int ah_group_sum_i64(ah_ctx* c, const int32_t* ids, int64_t ngroups, const int64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                               int64_t* out_sums, int64_t* out_counts) {
+  AH_ENTER(c);
+  return group_sum<false>(c, ids, ngroups, vals, vvalid, voff, n, out_sums, out_counts);
+}
+
+AH_EXPORT int ah_group_sum_f64(ah_ctx* c, const int32_t* ids, int64_t ngroups, const double* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                               double* out_sums, int64_t* out_counts) {
+  AH_ENTER(c);
+  return group_sum<true>(c, ids, ngroups, vals, vvalid, voff, n, out_sums, out_counts);
+}
+
+AH_EXPORT int ah_group_min_max_i64(ah_ctx* c, const int32_t* ids, int64_t ngroups, const int64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                                   int64_t* out_mins, int64_t* out_maxs, int64_t* out_counts) {
+  AH_ENTER(c);
+  return group_min_max<kI64>(c, ids, ngroups, vals, vvalid, voff, n, out_mins, out_maxs, out_counts);
+}
+
+AH_EXPORT int ah_group_min_max_u64(ah_ctx* c, const int32_t* ids, int64_t ngroups, const uint64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                                   uint64_t* out_mins, uint64_t* out_maxs, int64_t* out_counts) {
+  AH_ENTER(c);
+  return group_min_max<kU64>(c, ids, ngroups, vals, vvalid, voff, n, out_mins, out_maxs, out_counts);
+}
+
+AH_EXPORT int ah_group_min_max_f64(ah_ctx* c, const int32_t* ids, int64_t ngroups, const double* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                                   double* out_mins, double* out_maxs, int64_t* out_counts) {
+  AH_ENTER(c);
+  return group_min_max<kF64>(c, ids, ngroups, vals, vvalid, voff, n, out_mins, out_maxs, out_counts);
 }

@@ -31,6 +31,12 @@ class SortKey(C.Structure):
                 ("off", C.c_int64), ("descending", C.c_int), ("nulls_at_start", C.c_int)]
 
 
+class GroupKey(C.Structure):
+    """ah_group_key (include/arrowhip.h)"""
+    _fields_ = [("offset_width", C.c_int), ("byte_width", C.c_int), ("bits", C.c_int), ("offsets", C.c_void_p), ("data", C.c_void_p),
+                ("valid", C.c_void_p), ("off", C.c_int64)]
+
+
 class DeviceBuffer:
     """A device allocation owned by a Context (ah_buf_alloc / ah_buf_free)."""
 
@@ -719,6 +725,33 @@ class Context:
         check(self.handle, fns[kind](self.handle, _ptr(keys), _ptr(kvalid), koff, _ptr(vals), _ptr(vvalid), voff, n, _ptr(out_keys),
                                      _ptr(out_mins), _ptr(out_maxs), _ptr(out_counts), _ptr(out_first_rows), C.byref(ng), C.byref(nid)))
         return ng.value, nid.value
+
+    def group_ids(self, keys, n: int, out_ids, out_first_rows) -> int:
+        """dense first-seen group ids of a tuple of 1 … 8 key columns; keys: [(offset_width, byte_width, bits, offsets, data, valid, off),
+        …] — offset_width 4 / 8: String / Binary (Large…), byte_width 1 … 4096: fixed slots, bits 1: Boolean; row i is element off + i
+        of every buffer (ah_group_key, include/arrowhip.h).  A null is a value of its column.  out_ids: n int32, out_first_rows: int64,
+        n + 1 entries of room.  Returns the number of groups."""
+        arr = (GroupKey * max(len(keys), 1))()
+        for s, (ow, bw, bits, offsets, data, valid, off) in zip(arr, keys):
+            s.offset_width, s.byte_width, s.bits, s.offsets, s.data, s.valid, s.off = ow, bw, int(bits), _ptr(offsets), _ptr(data), _ptr(valid), off
+        ng = C.c_int64()
+        check(self.handle, lib.ah_group_ids(self.handle, len(keys), arr, n, _ptr(out_ids), _ptr(out_first_rows), C.byref(ng)))
+        return ng.value
+
+    def group_sum(self, kind: str, ids, ngroups: int, vals, vvalid, voff: int, n: int, out_sums, out_counts) -> None:
+        """hash_sum's sums and counts over caller-supplied dense ids (0 <= ids[i] < ngroups: not checked); kind: "i64" (wrapping) or "f64" (the fixed-point sum)"""
+        fns = {"i64": lib.ah_group_sum_i64, "f64": lib.ah_group_sum_f64}
+        if kind not in fns:
+            raise ValueError(f"group_sum: kind must be one of 'i64', 'f64', not {kind!r}")
+        check(self.handle, fns[kind](self.handle, _ptr(ids), ngroups, _ptr(vals), _ptr(vvalid), voff, n, _ptr(out_sums), _ptr(out_counts)))
+
+    def group_min_max(self, kind: str, ids, ngroups: int, vals, vvalid, voff: int, n: int, out_mins, out_maxs, out_counts) -> None:
+        """hash_min_max's minima, maxima and counts over caller-supplied dense ids (0 <= ids[i] < ngroups: not checked)"""
+        fns = {"i64": lib.ah_group_min_max_i64, "u64": lib.ah_group_min_max_u64, "f64": lib.ah_group_min_max_f64}
+        if kind not in fns:
+            raise ValueError(f"group_min_max: kind must be one of 'i64', 'u64', 'f64', not {kind!r}")
+        check(self.handle, fns[kind](self.handle, _ptr(ids), ngroups, _ptr(vals), _ptr(vvalid), voff, n, _ptr(out_mins), _ptr(out_maxs),
+                                     _ptr(out_counts)))
 
     def lz4_decompress_blocks(self, src, src_bytes: int, dst, dst_bytes: int, blocks):
         """independent LZ4 blocks of the device bytes `src` inflated into the device bytes `dst`; blocks: rows of {src_off, src_len

@@ -196,6 +196,69 @@ func (x *Context) HashMinMaxFloat64(keys, kvalid unsafe.Pointer, koff int64, val
 	return int64(ng), int32(nid), x.err(st)
 }
 
+// GroupKey is one key column of GroupIDs (ah_group_key): a String / Binary / LargeString / LargeBinary column (OffsetWidth 4 or 8,
+// Offsets the offsets buffer, Data the data buffer), a fixed-width column (ByteWidth 1 … 4096 bytes per slot of Data: numeric,
+// FixedSizeBinary, Decimal128 / 256) or a Boolean column (Bits, Data the bitmap).  Row i of the call is element Off + i of every
+// buffer and bit Off + i of Valid.
+type GroupKey struct {
+	OffsetWidth int
+	ByteWidth   int
+	Bits        bool
+	Offsets     unsafe.Pointer
+	Data        unsafe.Pointer
+	Valid       unsafe.Pointer
+	Off         int64
+}
+
+// GroupIDs: the dense first-seen group ids of a tuple of 1 … 8 key columns, and the first row of every group (ah_group_ids).  Rows
+// are in one group when every column is null in both or valid with equal bytes in both; a null is one more value of its column.
+// The key table is built in C memory, as in SortIndicesMulti.
+func (x *Context) GroupIDs(keys []GroupKey, n int64, outIDs, outFirstRows unsafe.Pointer) (ngroups int64, err error) {
+	k := len(keys)
+	if k == 0 {
+		return 0, fmt.Errorf("%w: arrowhip: GroupIDs wants at least one key", arrow.ErrInvalid)
+	}
+	var one C.ah_group_key
+	tbl := C.malloc(C.size_t(k) * C.size_t(unsafe.Sizeof(one)))
+	defer C.free(tbl)
+	ks := unsafe.Slice((*C.ah_group_key)(tbl), k)
+	for i, key := range keys {
+		ks[i].offset_width, ks[i].byte_width, ks[i].bits = C.int(key.OffsetWidth), C.int(key.ByteWidth), boolInt(key.Bits)
+		ks[i].offsets, ks[i].data, ks[i].valid, ks[i].off = key.Offsets, (*C.uint8_t)(key.Data), (*C.uint8_t)(key.Valid), C.int64_t(key.Off)
+	}
+	var ng C.int64_t
+	st := C.ah_group_ids(x.c, C.int(k), (*C.ah_group_key)(tbl), C.int64_t(n), (*C.int32_t)(outIDs), (*C.int64_t)(outFirstRows), &ng)
+	return int64(ng), x.err(st)
+}
+
+// GroupSumInt64 / GroupSumFloat64: the sums and counts of HashSumInt64 / HashSumFloat64 over caller-supplied dense group ids
+// (GroupIDs or an encoder with nulls encoded): 0 <= ids[i] < ngroups, which is not checked.
+func (x *Context) GroupSumInt64(ids unsafe.Pointer, ngroups int64, vals, vvalid unsafe.Pointer, voff, n int64, outSums, outCounts unsafe.Pointer) error {
+	return x.err(C.ah_group_sum_i64(x.c, (*C.int32_t)(ids), C.int64_t(ngroups), (*C.int64_t)(vals), (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		(*C.int64_t)(outSums), (*C.int64_t)(outCounts)))
+}
+
+func (x *Context) GroupSumFloat64(ids unsafe.Pointer, ngroups int64, vals, vvalid unsafe.Pointer, voff, n int64, outSums, outCounts unsafe.Pointer) error {
+	return x.err(C.ah_group_sum_f64(x.c, (*C.int32_t)(ids), C.int64_t(ngroups), (*C.double)(vals), (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		(*C.double)(outSums), (*C.int64_t)(outCounts)))
+}
+
+// GroupMinMaxInt64 / Uint64 / Float64: the minima, maxima and counts of HashMinMax* over caller-supplied dense group ids.
+func (x *Context) GroupMinMaxInt64(ids unsafe.Pointer, ngroups int64, vals, vvalid unsafe.Pointer, voff, n int64, outMins, outMaxs, outCounts unsafe.Pointer) error {
+	return x.err(C.ah_group_min_max_i64(x.c, (*C.int32_t)(ids), C.int64_t(ngroups), (*C.int64_t)(vals), (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		(*C.int64_t)(outMins), (*C.int64_t)(outMaxs), (*C.int64_t)(outCounts)))
+}
+
+func (x *Context) GroupMinMaxUint64(ids unsafe.Pointer, ngroups int64, vals, vvalid unsafe.Pointer, voff, n int64, outMins, outMaxs, outCounts unsafe.Pointer) error {
+	return x.err(C.ah_group_min_max_u64(x.c, (*C.int32_t)(ids), C.int64_t(ngroups), (*C.uint64_t)(vals), (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		(*C.uint64_t)(outMins), (*C.uint64_t)(outMaxs), (*C.int64_t)(outCounts)))
+}
+
+func (x *Context) GroupMinMaxFloat64(ids unsafe.Pointer, ngroups int64, vals, vvalid unsafe.Pointer, voff, n int64, outMins, outMaxs, outCounts unsafe.Pointer) error {
+	return x.err(C.ah_group_min_max_f64(x.c, (*C.int32_t)(ids), C.int64_t(ngroups), (*C.double)(vals), (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		(*C.double)(outMins), (*C.double)(outMaxs), (*C.int64_t)(outCounts)))
+}
+
 // Lz4DecompressBlocks: independent LZ4 blocks of the device bytes src inflated into the device bytes dst (ah_lz4_decompress_blocks).
 // blocks holds 4 values per block {srcOff, srcLen (bit 62: stored), dstOff, dstLen ≤ 65536}, dstOff ascending; status receives one
 // byte per block (0 ok, 1 corrupt, 2 produced != dstLen) and nbad is the number of blocks with a status — those leave unspecified

@@ -496,6 +496,51 @@ int ah_hash_min_max_f64(ah_ctx* ctx, const uint64_t* keys, const uint8_t* kvalid
                         uint64_t* out_keys, double* out_mins, double* out_maxs, int64_t* out_counts,
                         int64_t* out_first_rows, int64_t* out_ngroups_host, int32_t* out_null_group_host);
 
+/* One key column of ah_group_ids; row i of the call is element off + i of every buffer and bit off + i of `valid` (nullable).
+ * offset_width 4 / 8: String / Binary / LargeString / LargeBinary (offsets = the offsets buffer, data = the data buffer, which
+ * may be null when every value is empty); offset_width 0 and byte_width 1 ... 4096: fixed slots of that many bytes in `data`
+ * (numeric columns, FixedSizeBinary, Decimal128 / 256); bits = 1 (offset_width and byte_width 0): Boolean, bit off + i of `data`. */
+typedef struct ah_group_key {
+  int offset_width;
+  int byte_width;
+  int bits;
+  const void* offsets;
+  const uint8_t* data;
+  const uint8_t* valid;
+  int64_t off;
+} ah_group_key;
+/* Dense group ids of a TUPLE of key columns (NEW — no reference analogue; definition in DESIGN.md §3.2).  Rows i and j are in one
+ * group iff, for every column, both are null or both are valid with equal bytes (var-length columns: equal length and equal
+ * bytes).  The payload under a null is never looked at.  Keys are bytes: -0.0 and +0.0 are two keys, NaNs with different payloads
+ * are different keys — as the 8-byte entry points treat their words.  A null is one more value of its column, so (null, "a"),
+ * (null, "b"), (1, null) and (null, null) are four groups; there is no "null group" output.  out_ids[i] (n int32) = the group of
+ * row i, dense, in first-seen order; out_first_rows[g] (int64, n + 1 entries of room) = the first row of group g — the groups' key
+ * values are each key column gathered at these rows (ah_take_*).  *out_ngroups_host = the number of groups.
+ * 1 <= nkeys <= 8; n <= 2^30.  The descriptor array is host memory, the buffers are device memory.  Synchronises.  n == 0: no
+ * groups, nothing touched.  With nkeys == 1 ids, first rows and count are those of ah_hash_u64_encode / ah_hash_binary_encode /
+ * ah_hash_fixed_encode with encode_nulls = 1 on that column (for 8-byte, var-length and other fixed columns the call IS that
+ * encoder).  Tuples of fixed-width and Boolean columns whose value bits plus one bit per column with a validity buffer are <= 64
+ * are packed into one 8-byte word per row and take the 8-byte encoder with all of its routes; every other tuple is hashed and
+ * compared column by column where it lies. */
+int ah_group_ids(ah_ctx* ctx, int nkeys, const ah_group_key* keys, int64_t n, int32_t* out_ids, int64_t* out_first_rows,
+                 int64_t* out_ngroups_host);
+/* The aggregates of ah_hash_sum_* / ah_hash_min_max_* over CALLER-SUPPLIED dense group ids (ah_group_ids, or one of the encoders
+ * with encode_nulls = 1).  PRECONDITION: 0 <= ids[i] < ngroups for every row i; the ids are not checked, and the behaviour with an
+ * id outside that range is undefined.  Sum, count,
+ * minimum, maximum, the NaN rules and the count-0 rule are exactly those of ah_hash_sum_* / ah_hash_min_max_*, and so are the bytes:
+ * out_sums / out_mins / out_maxs / out_counts hold ngroups entries each, all of them written (a group without valid values: zeros).
+ * ngroups < 2^31, n <= 2^30; ngroups == 0: nothing touched. */
+int ah_group_sum_i64(ah_ctx* ctx, const int32_t* ids, int64_t ngroups, const int64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                     int64_t* out_sums, int64_t* out_counts);
+int ah_group_sum_f64(ah_ctx* ctx, const int32_t* ids, int64_t ngroups, const double* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                     double* out_sums, int64_t* out_counts);
+int ah_group_min_max_i64(ah_ctx* ctx, const int32_t* ids, int64_t ngroups, const int64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                         int64_t* out_mins, int64_t* out_maxs, int64_t* out_counts);
+int ah_group_min_max_u64(ah_ctx* ctx, const int32_t* ids, int64_t ngroups, const uint64_t* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                         uint64_t* out_mins, uint64_t* out_maxs, int64_t* out_counts);
+int ah_group_min_max_f64(ah_ctx* ctx, const int32_t* ids, int64_t ngroups, const double* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
+                         double* out_mins, double* out_maxs, int64_t* out_counts);
+
 /* ---- LZ4 blocks inflated in HBM (NEW — no reference analogue: the reference inflates IPC bodies on the host, arrow/ipc/
  * compression.go:25-72; definition in DESIGN.md §3.8) ----------------------------------------------------------------
  * src / dst: device memory.  blocks_host: 4 int64 per block {src_off, src_len, dst_off, dst_len}; src_len bit 62 set = stored block
