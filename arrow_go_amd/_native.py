@@ -181,6 +181,10 @@ _SIGS = {
     "ah_group_min_max_i64": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "ah_group_min_max_u64": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "ah_group_min_max_f64": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "ah_group_count": [_vp, _vp, _i64, _vp, _i64, _i64, _vp],
+    "ah_group_sum_typed": [_vp, _int, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp],
+    "ah_group_min_max_typed": [_vp, _int, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "ah_group_mean": [_vp, _int, _vp, _vp, _i64, _vp],
     "ah_lz4_decompress_blocks": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _pi64],
     "ah_lz4_compress_blocks": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "ah_ipc_pack_body": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64],

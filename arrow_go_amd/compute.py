@@ -591,6 +591,25 @@ class Session:
                 if d.value not in borrowed_handles:  # DeviceArray arguments stay owned by their wrappers
                     lib.ahc_datum_release(d)
 
+    def group_by(self, batch, keys, aggregates, keep_on_device: bool = False):
+        """call_function("group_by", [batch], "keys=…;aggregates=…"): the groups of the record batch's key columns in first-seen order,
+        the key columns first, then one column per aggregate named "<column>_<function>" (or "count_all").  aggregates: (column,
+        function) pairs as pyarrow's Table.group_by(keys).aggregate(...) takes them — function one of sum, mean, min, max, count —
+        and ([], "count_all").  Column names must not contain ',', ':', ';' or '='."""
+        keys = [keys] if isinstance(keys, str) else list(keys)
+        items = []
+        for col, fn in aggregates:
+            if fn == "count_all":
+                if col not in ([], (), None, ""):
+                    raise ValueError(f"group_by: count_all takes no column, not {col!r}")
+                items.append("count_all")
+            else:
+                items.append(f"{fn}:{col}")
+        for name in keys + [i.split(":", 1)[1] for i in items if ":" in i]:
+            if any(ch in name for ch in ",:;="):
+                raise ValueError(f"group_by: column name {name!r} cannot be written into an options string")
+        return self.call_function("group_by", [batch], "keys=%s;aggregates=%s" % (",".join(keys), ",".join(items)), keep_on_device=keep_on_device)
+
     # -- ipc.NewReader / Reader.Next, with the record-batch bodies landing in HBM
     def read_ipc(self, buf):
         """Iterate the record batches of an Arrow IPC *stream* (bytes / pyarrow.Buffer / mmap): yields

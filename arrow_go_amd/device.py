@@ -753,6 +753,25 @@ class Context:
         check(self.handle, fns[kind](self.handle, _ptr(ids), ngroups, _ptr(vals), _ptr(vvalid), voff, n, _ptr(out_mins), _ptr(out_maxs),
                                      _ptr(out_counts)))
 
+    def group_count(self, ids, ngroups: int, vvalid, voff: int, n: int, out_counts) -> None:
+        """rows of every group whose validity bit is set (vvalid None: every row) into out_counts (ngroups int64); reads no values"""
+        check(self.handle, lib.ah_group_count(self.handle, _ptr(ids), ngroups, _ptr(vvalid), voff, n, _ptr(out_counts)))
+
+    def group_sum_typed(self, type_id: int, ids, ngroups: int, vals, vvalid, voff: int, n: int, out_sums, out_counts) -> None:
+        """group_sum for a value column of any numeric type id (AH_INT8 ... AH_FLOAT64), read at its own width: out_sums holds ngroups
+        8-byte sums — wrapping Int64 (signed), wrapping UInt64 (unsigned), Float64 (floats) — with the bytes of group_sum on the cast column"""
+        check(self.handle, lib.ah_group_sum_typed(self.handle, type_id, _ptr(ids), ngroups, _ptr(vals), _ptr(vvalid), voff, n, _ptr(out_sums),
+                                                  _ptr(out_counts)))
+
+    def group_min_max_typed(self, type_id: int, ids, ngroups: int, vals, vvalid, voff: int, n: int, out_mins, out_maxs, out_counts) -> None:
+        """group_min_max for a value column of any numeric type id; out_mins / out_maxs hold ngroups values of the input type"""
+        check(self.handle, lib.ah_group_min_max_typed(self.handle, type_id, _ptr(ids), ngroups, _ptr(vals), _ptr(vvalid), voff, n, _ptr(out_mins),
+                                                      _ptr(out_maxs), _ptr(out_counts)))
+
+    def group_mean(self, sum_type: int, sums, counts, ngroups: int, out_means) -> None:
+        """out_means[g] = float64(sums[g]) / float64(counts[g]), 0.0 where the count is 0; sum_type: AH_INT64, AH_UINT64 or AH_FLOAT64"""
+        check(self.handle, lib.ah_group_mean(self.handle, sum_type, _ptr(sums), _ptr(counts), ngroups, _ptr(out_means)))
+
     def lz4_decompress_blocks(self, src, src_bytes: int, dst, dst_bytes: int, blocks):
         """independent LZ4 blocks of the device bytes `src` inflated into the device bytes `dst`; blocks: rows of {src_off, src_len
         (bit 62: stored), dst_off, dst_len <= 65536}, dst_off ascending.  Returns the status byte of every block as a numpy array

@@ -316,6 +316,15 @@ enum RoundMode { RoundDown = 0, RoundUp, RoundTowardsZero, RoundTowardsInfinity,
                  RoundHalfTowardsInfinity, RoundHalfToEven, RoundHalfToOdd };
 struct RoundOptions : FunctionOptions { int64_t NDigits = 0; RoundMode Mode = RoundHalfToEven; const char* TypeName() const override { return "RoundOptions"; } };
 struct RoundToMultipleOptions : FunctionOptions { ScalarPtr Multiple; RoundMode Mode = RoundHalfToEven; const char* TypeName() const override { return "RoundToMultipleOptions"; } };
+// group_by (no reference analogue — arrow-go has no hash aggregate): the key columns and the aggregates by column NAME,
+// as pyarrow's Table.group_by(keys).aggregate([(column, function), …]) writes them.  Function: sum, mean, min, max, count, count_all
+// (count_all has no column).
+struct GroupByAggregate { std::string Function, Column; };
+struct GroupByOptions : FunctionOptions {
+  std::vector<std::string> Keys;
+  std::vector<GroupByAggregate> Aggregates;
+  const char* TypeName() const override { return "GroupByOptions"; }
+};
 struct CompareFilterSumOptions : FunctionOptions { int cmpop = AH_CMP_GT; const char* TypeName() const override { return "CompareFilterSumOptions"; } };
 
 // compute.Datum (datum.go:35-40): array or scalar
@@ -508,6 +517,7 @@ Status CastDatum(ExecCtx* ctx, const Datum& in, const CastOptions& opts, Datum* 
 void RegisterVectorSelection(FunctionRegistry* reg);
 void RegisterVectorHash(FunctionRegistry* reg);
 void RegisterFusedExtensions(FunctionRegistry* reg);
+void RegisterGroupBy(FunctionRegistry* reg);
 
 // ---- compute.Expression (arrow/compute/expression.go:59-78,596-620) and its executor
 // (arrow/compute/exprs/exec.go:440-700 ExecuteScalarExpression / executeScalarBatch) --------

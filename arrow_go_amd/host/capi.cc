@@ -328,6 +328,7 @@ AHC_EXPORT int ahc_datum_info(ahc_datum* d, int* kind, int* type_id, int64_t* le
 //   sort_keys=<col>:<asc|desc>:<at_end|at_start>,…                                                (SortOptions, several keys)
 //   ndigits=<n>   round_mode=down|up|towards_zero|towards_infinity|half_down|half_up|half_towards_zero|half_towards_infinity|
 //   half_to_even|half_to_odd   multiple=<type>:<value>                                            (RoundOptions / RoundToMultipleOptions)
+//   keys=<name>,…   aggregates=<sum|mean|min|max|count>:<name>,…,count_all                          (GroupByOptions)
 //   skip_nulls=0|1   start=<type>:<value>|null:<type>   (e.g. start=int64:10, start=double:1.5, start=null:int32)
 struct ParsedOptions {
   compute::FilterOptions filter;
@@ -339,6 +340,7 @@ struct ParsedOptions {
   compute::SortOptions sort;
   compute::RoundOptions round;
   compute::RoundToMultipleOptions round_multiple;
+  compute::GroupByOptions group_by;
   const compute::FunctionOptions* pick = nullptr;
 };
 static const struct { const char* name; Type id; } kTypeNames[] = {
@@ -429,6 +431,21 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
           q = e + 1;
         }
         p->pick = &p->sort;
+      }
+      if (k == "keys" || k == "aggregates") {   // group_by: names split at ',', an aggregate at its first ':' ("sum:v"; "count_all" has no column)
+        size_t q = 0;
+        while (q <= v.size()) {
+          size_t e = v.find(',', q);
+          if (e == std::string::npos) e = v.size();
+          std::string item = v.substr(q, e - q);
+          if (k == "keys") { if (!item.empty() || e < v.size()) p->group_by.Keys.push_back(item); }
+          else if (!item.empty()) {
+            size_t c = item.find(':');
+            p->group_by.Aggregates.push_back({item.substr(0, c), c == std::string::npos ? std::string() : item.substr(c + 1)});
+          }
+          q = e + 1;
+        }
+        p->pick = &p->group_by;
       }
       if (k == "order" || k == "null_placement") {
         if (p->sort.Keys.empty()) p->sort.Keys.push_back(compute::SortKey());

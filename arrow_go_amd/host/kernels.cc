@@ -1901,6 +1901,198 @@ void RegisterVectorCumulative(FunctionRegistry* reg) {
   }
 }
 
+// ---- group_by (no reference analogue: arrow-go has no hash aggregate) --------------------------------------------
+// One RecordDatum in, one out: the key columns gathered at every group's first row, then one column per aggregate, rows = groups in
+// first-seen order.  ah_group_ids runs once per call; per value column the typed aggregates of ah_group_agg.hip run once each and
+// are shared by the aggregates that name the column (sum + mean + count: one ah_group_sum_typed, one ah_group_mean).
+namespace {
+
+struct GroupByColumnWork {   // what the aggregates naming one value column need, and what has been computed for it
+  bool sum = false, min_max = false, count = false;
+  BufferPtr sums, mins, maxs, means, counts, validity;
+  int64_t nulls = 0;   // groups without a valid value
+};
+
+Status GroupByImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Datum>& args, Datum* out) {
+  const GroupByOptions* opts = dynamic_cast<const GroupByOptions*>(o);
+  if (args[0].kind != DatumKind::Record) return Status::Make(StatusCode::Invalid, "group_by: the argument must be a record batch");
+  if (!opts || opts->Keys.empty()) return Status::Make(StatusCode::Invalid, "group_by: no keys (keys=<column>,...)");
+  if (opts->Keys.size() > 8) return Status::Make(StatusCode::Invalid, "group_by: more than 8 keys (" + std::to_string(opts->Keys.size()) + ")");
+  Session* s = ctx->session;
+  const Datum& batch = args[0];
+  const int64_t n = batch.num_rows;
+  auto column = [&](const std::string& name) -> int {
+    for (size_t i = 0; i < batch.names.size(); i++) if (batch.names[i] == name) return (int)i;
+    return -1;
+  };
+  auto no_kernel = [](const std::string& what, const ArrayData& a) {
+    return Status::Make(StatusCode::NotImplemented, "function 'group_by' has no kernel matching input types (" + what + ": " +
+                                                        (a.logical.empty() ? std::string(a.type->name) : a.logical) + ")");
+  };
+  for (auto& c : batch.chunks)
+    if (c->on_host) return Status::Make(StatusCode::NotImplemented, "group_by: host-resident columns are not taken; upload the batch first");
+  // the keys, as ah_group_ids describes them
+  std::vector<int> key_cols;
+  std::vector<ah_group_key> gkeys;
+  for (auto& name : opts->Keys) {
+    const int ci = column(name);
+    if (ci < 0) return Status::Make(StatusCode::Invalid, "group_by: unknown key column '" + name + "'");
+    const ArrayData& a = *batch.chunks[ci];
+    const Type id = a.type->id;
+    // a dictionary's indices are not its values: two indices may name equal values
+    if (id == Type::DICTIONARY) return Status::Make(StatusCode::NotImplemented, "group_by: dictionary-typed key column '" + name + "'; decode it first");
+    ah_group_key k{};
+    auto dptr = [&](int i) -> const uint8_t* { return a.buffers[i] ? (const uint8_t*)a.buffers[i]->dptr : nullptr; };
+    if (id == Type::BOOL) { k.bits = 1; k.data = dptr(1); }
+    else if (IsBaseBinary(id)) { k.offset_width = a.type->bit_width / 8; k.offsets = dptr(1); k.data = dptr(2); }
+    else if (IsNumeric(id) || IsFixedWidthBinary(id)) { k.byte_width = a.type->bit_width / 8; k.data = dptr(1); }
+    else return no_kernel("key", a);
+    k.valid = a.null_count != 0 ? dptr(0) : nullptr;
+    k.off = a.offset;
+    key_cols.push_back(ci);
+    gkeys.push_back(k);
+  }
+  // the aggregates: names and types checked before anything runs
+  std::map<int, GroupByColumnWork> work;
+  bool count_all = false;
+  for (auto& ag : opts->Aggregates) {
+    const std::string& f = ag.Function;
+    if (f == "count_all") {
+      if (!ag.Column.empty()) return Status::Make(StatusCode::Invalid, "group_by: count_all takes no column, got '" + ag.Column + "'");
+      count_all = true;
+      continue;
+    }
+    if (f != "sum" && f != "mean" && f != "min" && f != "max" && f != "count")
+      return Status::Make(StatusCode::Invalid, "group_by: unknown aggregate '" + f + "'");
+    const int ci = column(ag.Column);
+    if (ci < 0) return Status::Make(StatusCode::Invalid, "group_by: unknown column '" + ag.Column + "' of aggregate '" + f + "'");
+    const ArrayData& a = *batch.chunks[ci];
+    GroupByColumnWork& w = work[ci];
+    if (f == "count") { w.count = true; continue; }
+    if (!IsNumeric(a.type->id) || ((f == "sum" || f == "mean") && !a.logical.empty())) return no_kernel(f, a);
+    if (f == "sum" || f == "mean") w.sum = true; else w.min_max = true;
+  }
+  // ids and first rows, once
+  BufferPtr ids, first_rows;
+  AHC_RETURN_NOT_OK(s->Allocate((n > 0 ? n : 1) * 4, &ids, /*zero_all=*/false));
+  AHC_RETURN_NOT_OK(s->Allocate((n + 1) * 8, &first_rows, /*zero_all=*/false));
+  int64_t ng = 0;
+  if (n > 0) AHC_RETURN_NOT_OK(s->FromStatus(ah_group_ids(s->ctx(), (int)gkeys.size(), gkeys.data(), n, (int32_t*)ids->dptr, (int64_t*)first_rows->dptr, &ng)));
+  std::vector<std::string> names;
+  std::vector<ArrayDataPtr> cols;
+  {
+    auto idx = std::make_shared<ArrayData>();
+    idx->type = GetDataType(Type::INT64);
+    idx->length = ng;
+    idx->null_count = 0;
+    idx->buffers[1] = first_rows;
+    static const TakeOptions kNoBoundsCheck = [] { TakeOptions t; t.BoundsCheck = false; return t; }();
+    for (size_t i = 0; i < key_cols.size(); i++) {
+      Datum col;
+      AHC_RETURN_NOT_OK(CallFunction(ctx, "array_take", &kNoBoundsCheck, {Datum::Of(batch.chunks[key_cols[i]]), Datum::Of(idx)}, &col));
+      names.push_back(opts->Keys[i]);
+      cols.push_back(col.array);
+    }
+  }
+  const int64_t room = ng > 0 ? ng : 1;
+  const int32_t* idp = (const int32_t*)ids->dptr;
+  for (auto& kv : work) {
+    const ArrayData& a = *batch.chunks[kv.first];
+    GroupByColumnWork& w = kv.second;
+    const uint8_t* vvalid = a.buffers[0] && a.null_count != 0 ? (const uint8_t*)a.buffers[0]->dptr : nullptr;
+    const int width = w.sum || w.min_max ? a.type->bit_width / 8 : 0;
+    const uint8_t* vals = width && a.buffers[1] ? (const uint8_t*)a.buffers[1]->dptr + a.offset * width : nullptr;
+    AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.counts, /*zero_all=*/false));
+    if (w.sum) {
+      AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.sums, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.means, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_group_sum_typed(s->ctx(), (int)a.type->id, idp, ng, vals, vvalid, a.offset, n, w.sums->dptr, (int64_t*)w.counts->dptr)));
+    }
+    if (w.min_max) {
+      AHC_RETURN_NOT_OK(s->Allocate(room * width, &w.mins, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->Allocate(room * width, &w.maxs, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_group_min_max_typed(s->ctx(), (int)a.type->id, idp, ng, vals, vvalid, a.offset, n, w.mins->dptr, w.maxs->dptr,
+                                                             (int64_t*)w.counts->dptr)));
+    }
+    if (!w.sum && !w.min_max)
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_group_count(s->ctx(), idp, ng, vvalid, a.offset, n, (int64_t*)w.counts->dptr)));
+    // a group holds at least one row, so only a column with nulls can leave a group without a valid value: validity = counts != 0
+    if (vvalid && ng > 0 && (w.sum || w.min_max)) {
+      auto counts = std::make_shared<ArrayData>();
+      counts->type = GetDataType(Type::INT64);
+      counts->length = ng;
+      counts->null_count = 0;
+      counts->buffers[1] = w.counts;
+      auto zero = std::make_shared<Scalar>();
+      zero->type = counts->type;
+      zero->valid = true;
+      Datum bits;
+      AHC_RETURN_NOT_OK(CallFunction(ctx, "not_equal", nullptr, {Datum::Of(counts), Datum::Of(zero)}, &bits));
+      ArraySpan span;
+      span.type = GetDataType(Type::BOOL);
+      span.len = ng;
+      span.offset = bits.array->offset;
+      span.buffers[0].WrapBuffer(bits.array->buffers[1]);
+      AHC_RETURN_NOT_OK(span.UpdateNullCount(s, &w.nulls));
+      if (w.nulls) {
+        if (bits.array->offset != 0) return Status::Make(StatusCode::Invalid, "group_by: the comparison returned a sliced bitmap");
+        w.validity = bits.array->buffers[1];
+      }
+    }
+  }
+  BufferPtr all_counts;
+  if (count_all) {
+    AHC_RETURN_NOT_OK(s->Allocate(room * 8, &all_counts, /*zero_all=*/false));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_group_count(s->ctx(), idp, ng, nullptr, 0, n, (int64_t*)all_counts->dptr)));
+  }
+  for (auto& ag : opts->Aggregates) {
+    auto col = std::make_shared<ArrayData>();
+    col->length = ng;
+    col->null_count = 0;
+    const std::string& f = ag.Function;
+    if (f == "count_all") {
+      col->type = GetDataType(Type::INT64);
+      col->buffers[1] = all_counts;
+      names.push_back("count_all");
+      cols.push_back(col);
+      continue;
+    }
+    const int ci = column(ag.Column);
+    const ArrayData& a = *batch.chunks[ci];
+    GroupByColumnWork& w = work[ci];
+    if (f == "count") {
+      col->type = GetDataType(Type::INT64);
+      col->buffers[1] = w.counts;
+    } else {
+      col->null_count = w.nulls;
+      col->buffers[0] = w.validity;
+      if (f == "sum") {
+        col->type = GetDataType(IsFloating(a.type->id) ? Type::FLOAT64 : IsSignedInteger(a.type->id) ? Type::INT64 : Type::UINT64);
+        col->buffers[1] = w.sums;
+      } else if (f == "mean") {
+        const int sum_type = IsFloating(a.type->id) ? AH_FLOAT64 : IsSignedInteger(a.type->id) ? AH_INT64 : AH_UINT64;
+        AHC_RETURN_NOT_OK(s->FromStatus(ah_group_mean(s->ctx(), sum_type, w.sums->dptr, (const int64_t*)w.counts->dptr, ng, (double*)w.means->dptr)));
+        col->type = GetDataType(Type::FLOAT64);
+        col->buffers[1] = w.means;
+      } else {
+        col->type = a.type;
+        col->logical = a.logical;
+        col->buffers[1] = f == "min" ? w.mins : w.maxs;
+      }
+    }
+    names.push_back(ag.Column + "_" + f);
+    cols.push_back(col);
+  }
+  *out = Datum::OfRecord(std::move(names), std::move(cols), ng);
+  return Status::OK();
+}
+
+}  // namespace
+
+void RegisterGroupBy(FunctionRegistry* reg) {
+  reg->AddFunction(std::make_shared<MetaFunction>("group_by", Arity{1, false}, nullptr, GroupByImpl), false);
+}
+
 // ---- fused extension (no reference analogue) --------------------------------
 // "greater_filter_sum"(x, scalar) etc.: Σ x over valid slots with x OP scalar, as a 1-element
 // array of x's type — what "greater" → "filter" → math.Sum computes in three calls.

@@ -259,6 +259,32 @@ func (x *Context) GroupMinMaxFloat64(ids unsafe.Pointer, ngroups int64, vals, vv
 		(*C.double)(outMins), (*C.double)(outMaxs), (*C.int64_t)(outCounts)))
 }
 
+// GroupCount: the number of rows of every group whose validity bit is set (vvalid nil: every row) over caller-supplied dense group
+// ids (ah_group_count).  Reads the ids and the validity bits only; outCounts holds ngroups int64.
+func (x *Context) GroupCount(ids unsafe.Pointer, ngroups int64, vvalid unsafe.Pointer, voff, n int64, outCounts unsafe.Pointer) error {
+	return x.err(C.ah_group_count(x.c, (*C.int32_t)(ids), C.int64_t(ngroups), (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n), (*C.int64_t)(outCounts)))
+}
+
+// GroupSumTyped: GroupSumInt64 / GroupSumFloat64 for a value column of any numeric type id, read at its own width (ah_group_sum_typed).
+// outSums holds ngroups 8-byte sums: wrapping Int64 for signed, wrapping Uint64 for unsigned, Float64 for floating-point values.
+func (x *Context) GroupSumTyped(typeID arrow.Type, ids unsafe.Pointer, ngroups int64, vals, vvalid unsafe.Pointer, voff, n int64, outSums, outCounts unsafe.Pointer) error {
+	return x.err(C.ah_group_sum_typed(x.c, C.int(typeID), (*C.int32_t)(ids), C.int64_t(ngroups), vals, (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		outSums, (*C.int64_t)(outCounts)))
+}
+
+// GroupMinMaxTyped: GroupMinMax* for a value column of any numeric type id (ah_group_min_max_typed); outMins / outMaxs hold ngroups
+// values of the input type.
+func (x *Context) GroupMinMaxTyped(typeID arrow.Type, ids unsafe.Pointer, ngroups int64, vals, vvalid unsafe.Pointer, voff, n int64, outMins, outMaxs, outCounts unsafe.Pointer) error {
+	return x.err(C.ah_group_min_max_typed(x.c, C.int(typeID), (*C.int32_t)(ids), C.int64_t(ngroups), vals, (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		outMins, outMaxs, (*C.int64_t)(outCounts)))
+}
+
+// GroupMean: outMeans[g] = float64(sums[g]) / float64(counts[g]), 0 where the count is 0 (ah_group_mean); sumType says how the sums
+// are read: arrow.INT64, arrow.UINT64 or arrow.FLOAT64.
+func (x *Context) GroupMean(sumType arrow.Type, sums, counts unsafe.Pointer, ngroups int64, outMeans unsafe.Pointer) error {
+	return x.err(C.ah_group_mean(x.c, C.int(sumType), sums, (*C.int64_t)(counts), C.int64_t(ngroups), (*C.double)(outMeans)))
+}
+
 // Lz4DecompressBlocks: independent LZ4 blocks of the device bytes src inflated into the device bytes dst (ah_lz4_decompress_blocks).
 // blocks holds 4 values per block {srcOff, srcLen (bit 62: stored), dstOff, dstLen ≤ 65536}, dstOff ascending; status receives one
 // byte per block (0 ok, 1 corrupt, 2 produced != dstLen) and nbad is the number of blocks with a status — those leave unspecified

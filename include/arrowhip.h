@@ -540,6 +540,26 @@ int ah_group_min_max_u64(ah_ctx* ctx, const int32_t* ids, int64_t ngroups, const
                          uint64_t* out_mins, uint64_t* out_maxs, int64_t* out_counts);
 int ah_group_min_max_f64(ah_ctx* ctx, const int32_t* ids, int64_t ngroups, const double* vals, const uint8_t* vvalid, int64_t voff, int64_t n,
                          double* out_mins, double* out_maxs, int64_t* out_counts);
+/* The same aggregates for a value column of ANY numeric width (NEW — DESIGN.md §3.2), over the same caller-supplied ids with the same
+ * precondition and limits (a row whose id is outside [0, ngroups) touches nothing).  `type`: AH_INT8 ... AH_INT64, AH_UINT8 ...
+ * AH_UINT64, AH_FLOAT32, AH_FLOAT64.  Values are loaded at their own width from `vals` (element-aligned) and widened in registers:
+ * no 8-byte copy of the column is written.  THE BYTES are those of the 64-bit call on the column cast to Int64 (signed), to UInt64
+ * bit patterns (unsigned) or to Float64 (floats):
+ *   ah_group_sum_typed      out_sums (ngroups x 8 bytes): wrapping Int64 / wrapping UInt64 / the reproducible, correctly rounded
+ *                           Float64 sum with its wide-column route and its non-finite rules (ah_group_sum_i64 / _f64).
+ *   ah_group_min_max_typed  out_mins / out_maxs (ngroups entries of the INPUT type): the 64-bit result narrowed back, which is exact;
+ *                           NaNs counted but ignored, -0 < +0, an all-NaN group = the type's canonical quiet NaN, count 0 = zero bytes.
+ *   ah_group_count          out_counts[g] (int64) = rows of group g whose validity bit is set (vvalid == NULL: every row).  Reads
+ *                           the ids and the validity bits only.
+ *   ah_group_mean           out_means[g] = (double)sums[g] / (double)counts[g] (IEEE), 0.0 where counts[g] == 0 — the caller derives
+ *                           the validity from the counts.  sum_type: AH_INT64, AH_UINT64 or AH_FLOAT64, how `sums` is read.
+ * out_counts is int64, ngroups entries.  n == 0: every group is empty.  ngroups == 0: nothing touched. */
+int ah_group_count(ah_ctx* ctx, const int32_t* ids, int64_t ngroups, const uint8_t* vvalid, int64_t voff, int64_t n, int64_t* out_counts);
+int ah_group_sum_typed(ah_ctx* ctx, int type, const int32_t* ids, int64_t ngroups, const void* vals, const uint8_t* vvalid, int64_t voff,
+                       int64_t n, void* out_sums, int64_t* out_counts);
+int ah_group_min_max_typed(ah_ctx* ctx, int type, const int32_t* ids, int64_t ngroups, const void* vals, const uint8_t* vvalid,
+                           int64_t voff, int64_t n, void* out_mins, void* out_maxs, int64_t* out_counts);
+int ah_group_mean(ah_ctx* ctx, int sum_type, const void* sums, const int64_t* counts, int64_t ngroups, double* out_means);
 
 /* ---- LZ4 blocks inflated in HBM (NEW — no reference analogue: the reference inflates IPC bodies on the host, arrow/ipc/
  * compression.go:25-72; definition in DESIGN.md §3.8) ----------------------------------------------------------------
