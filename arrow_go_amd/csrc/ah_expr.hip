@@ -14,11 +14,20 @@
 // NullHandling = NullIntersection (validity = AND of the operands' validity), unchecked
 // kernels compute every slot (null payloads included), checked integer kernels write 0 under
 // nulls and fail with "overflow" by the reference's carry test, compares produce bits,
-// and/or/xor/and_not/invert are the plain (non-Kleene) bitmap ops.  What a call computes is
-// not restated here: the generated source includes ah_elementwise.h — the text the per-call
-// kernels are compiled from, handed to hiprtc as a named header — and calls apply_unary /
-// apply_binary / apply of it; only float + − × and the comparisons are infix.  Float
-// contraction is disabled (-ffp-contract=off): a*b+c rounds twice, like two kernels.
+// and/or/xor/and_not/invert are the plain (non-Kleene) bitmap ops.  What one call computes in
+// one slot is not restated here: the generated source includes ah_elementwise.h — the text
+// the per-call kernels are compiled from, handed to hiprtc as a named header — and calls
+// apply_unary / apply_binary / apply of it; only float + − × and the comparisons are infix.
+// That shared text carries the slot's value and error bits, no more.  This file's own are the
+// skeleton (the wave-uniform chunk loop with its inactive unrolled steps, load_bits64,
+// store_word, the ballots), the slot rule of the checked ops (which slots report, which hold
+// 0 — restated in Generate(), and only for lanes that hold a row), the AH_X_CAST nodes, the
+// literals as 8-byte kernel arguments and the hiprtc option list; for these "bit for bit" is
+// a claim that tests hold up, not a construction: tests/test_expressions_ranges.py runs both
+// routes against the independent model of tests/expr_model.py (itself held against the CPU
+// oracle by tests/test_expr_model_host.py) over full value ranges.  Float contraction is
+// disabled (-ffp-contract=off, repeated here from the Makefile): a*b+c rounds twice, like
+// two kernels.
 // No implicit casts: the operands of a call must have the same type (→ AH_ENOTIMPL).
 #include <hip/hiprtc.h>
 
@@ -193,7 +202,9 @@ int Generate(ah_ctx* c, const ah_expr_node* nodes, int n_nodes, const int* col_t
           std::string t = "t" + std::to_string(tmp), e1 = "e" + std::to_string(tmp);
           body += "        unsigned " + e1 + " = 0;\n";
           body += "        const " + T + " " + t + " = apply<" + T + ", " + x + ">(" + a.v + ", " + b.v + ", " + e1 + ");\n";
-          body += (base == 2 ? "        " : "        if (" + ok + ") ") + "err |= " + e1 + ";\n";   // multiply: every slot
+          // multiply: every slot that holds a row, null or not — never a lane past the last row or one of an inactive unrolled
+          // step: there the columns read 0 but the literals keep their values, and their product alone may overflow
+          body += "        if (" + (base == 2 ? std::string("inb") : ok) + ") err |= " + e1 + ";\n";
           ex = base == 2 ? t : "(" + ok + ") ? " + t + " : (" + T + ")0";
         } else if (IsInt(a.type)) {
           const char* opc = base == 0 ? "OP_ADD" : base == 1 ? "OP_SUB" : "OP_MUL";
