@@ -610,6 +610,23 @@ class Session:
                 raise ValueError(f"group_by: column name {name!r} cannot be written into an options string")
         return self.call_function("group_by", [batch], "keys=%s;aggregates=%s" % (",".join(keys), ",".join(items)), keep_on_device=keep_on_device)
 
+    def hash_join(self, left, right, keys, right_keys=None, join_type: str = "inner", keep_on_device: bool = False):
+        """call_function("hash_join", [left, right], "left_keys=…;right_keys=…;type=…"): the two record batches joined on their key
+        columns (right_keys None: the same names as `keys`).  join_type: inner, left_outer, left_semi or left_anti.  Rows: the left rows
+        in order, each with its right matches in order (left_outer: an unmatched left row once, nulls on the right); columns: every left
+        column, then the right columns that are not keys (semi / anti: the left columns only).  Keys are equal when their bytes are; a
+        null key matches nothing.  Column names must not contain ',', ';' or '='."""
+        keys = [keys] if isinstance(keys, str) else list(keys)
+        rkeys = None if right_keys is None else ([right_keys] if isinstance(right_keys, str) else list(right_keys))
+        for name in keys + (rkeys or []) + [join_type]:
+            if any(ch in name for ch in ",;="):
+                raise ValueError(f"hash_join: {name!r} cannot be written into an options string")
+        options = "left_keys=%s" % ",".join(keys)
+        if rkeys is not None:
+            options += ";right_keys=%s" % ",".join(rkeys)
+        options += ";type=%s" % join_type
+        return self.call_function("hash_join", [left, right], options, keep_on_device=keep_on_device)
+
     # -- ipc.NewReader / Reader.Next, with the record-batch bodies landing in HBM
     def read_ipc(self, buf):
         """Iterate the record batches of an Arrow IPC *stream* (bytes / pyarrow.Buffer / mmap): yields

@@ -772,6 +772,34 @@ class Context:
         """out_means[g] = float64(sums[g]) / float64(counts[g]), 0.0 where the count is 0; sum_type: AH_INT64, AH_UINT64 or AH_FLOAT64"""
         check(self.handle, lib.ah_group_mean(self.handle, sum_type, _ptr(sums), _ptr(counts), ngroups, _ptr(out_means)))
 
+    # ---- hash join over dense group ids (ah_join.hip): ids int32, row numbers / starts / offsets int64, validity = bit off + row -----------
+    def join_build(self, build_ids, build_valid, voff: int, n_build: int, ngroups: int, out_starts, out_rows) -> None:
+        """out_starts[g] .. out_starts[g + 1] (ngroups + 1 entries) delimit, in out_rows (n_build entries of room), the valid build rows
+        of group g in ascending row order"""
+        check(self.handle, lib.ah_join_build(self.handle, _ptr(build_ids), _ptr(build_valid), voff, n_build, ngroups, _ptr(out_starts), _ptr(out_rows)))
+
+    def join_count(self, probe_ids, probe_valid, poff: int, n_probe: int, starts, emit_unmatched: bool, out_offsets) -> int:
+        """out_offsets (n_probe + 1 entries) = the exclusive scan of every probe row's match count (at least 1 with emit_unmatched);
+        returns the total, the rows of the join's result"""
+        total = C.c_int64()
+        check(self.handle, lib.ah_join_count(self.handle, _ptr(probe_ids), _ptr(probe_valid), poff, n_probe, _ptr(starts), int(bool(emit_unmatched)),
+                                             _ptr(out_offsets), C.byref(total)))
+        return total.value
+
+    def join_expand(self, probe_ids, probe_valid, poff: int, n_probe: int, starts, rows, offsets, total: int, emit_unmatched: bool,
+                    out_probe_rows, out_build_rows, out_build_valid=None) -> int:
+        """the probe row and the build row of every output slot (`total` int64 entries each); with emit_unmatched also the validity
+        bitmap of the build rows, and the number of its clear bits is returned (0 without)"""
+        nulls = C.c_int64()
+        check(self.handle, lib.ah_join_expand(self.handle, _ptr(probe_ids), _ptr(probe_valid), poff, n_probe, _ptr(starts), _ptr(rows), _ptr(offsets),
+                                              total, int(bool(emit_unmatched)), _ptr(out_probe_rows), _ptr(out_build_rows), _ptr(out_build_valid),
+                                              C.byref(nulls)))
+        return nulls.value
+
+    def join_match_bits(self, probe_ids, probe_valid, poff: int, n_probe: int, starts, out_bits) -> None:
+        """bit i of out_bits = probe row i is valid and its group holds a build row (the mask of a semi join)"""
+        check(self.handle, lib.ah_join_match_bits(self.handle, _ptr(probe_ids), _ptr(probe_valid), poff, n_probe, _ptr(starts), _ptr(out_bits)))
+
     def lz4_decompress_blocks(self, src, src_bytes: int, dst, dst_bytes: int, blocks):
         """independent LZ4 blocks of the device bytes `src` inflated into the device bytes `dst`; blocks: rows of {src_off, src_len
         (bit 62: stored), dst_off, dst_len <= 65536}, dst_off ascending.  Returns the status byte of every block as a numpy array

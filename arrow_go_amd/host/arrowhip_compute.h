@@ -325,6 +325,13 @@ struct GroupByOptions : FunctionOptions {
   std::vector<GroupByAggregate> Aggregates;
   const char* TypeName() const override { return "GroupByOptions"; }
 };
+// hash_join (no reference analogue — arrow-go has no join): the key columns of both record batches by NAME, position by
+// position.  RightKeys empty = the left names.  JoinType: inner (also ""), left_outer, left_semi, left_anti.
+struct HashJoinOptions : FunctionOptions {
+  std::vector<std::string> LeftKeys, RightKeys;
+  std::string JoinType;
+  const char* TypeName() const override { return "HashJoinOptions"; }
+};
 struct CompareFilterSumOptions : FunctionOptions { int cmpop = AH_CMP_GT; const char* TypeName() const override { return "CompareFilterSumOptions"; } };
 
 // compute.Datum (datum.go:35-40): array or scalar
@@ -518,6 +525,7 @@ void RegisterVectorSelection(FunctionRegistry* reg);
 void RegisterVectorHash(FunctionRegistry* reg);
 void RegisterFusedExtensions(FunctionRegistry* reg);
 void RegisterGroupBy(FunctionRegistry* reg);
+void RegisterHashJoin(FunctionRegistry* reg);
 
 // ---- compute.Expression (arrow/compute/expression.go:59-78,596-620) and its executor
 // (arrow/compute/exprs/exec.go:440-700 ExecuteScalarExpression / executeScalarBatch) --------

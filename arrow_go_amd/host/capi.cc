@@ -329,6 +329,7 @@ AHC_EXPORT int ahc_datum_info(ahc_datum* d, int* kind, int* type_id, int64_t* le
 //   ndigits=<n>   round_mode=down|up|towards_zero|towards_infinity|half_down|half_up|half_towards_zero|half_towards_infinity|
 //   half_to_even|half_to_odd   multiple=<type>:<value>                                            (RoundOptions / RoundToMultipleOptions)
 //   keys=<name>,…   aggregates=<sum|mean|min|max|count>:<name>,…,count_all                          (GroupByOptions)
+//   left_keys=<name>,…   right_keys=<name>,…   type=inner|left_outer|left_semi|left_anti            (HashJoinOptions)
 //   skip_nulls=0|1   start=<type>:<value>|null:<type>   (e.g. start=int64:10, start=double:1.5, start=null:int32)
 struct ParsedOptions {
   compute::FilterOptions filter;
@@ -341,6 +342,7 @@ struct ParsedOptions {
   compute::RoundOptions round;
   compute::RoundToMultipleOptions round_multiple;
   compute::GroupByOptions group_by;
+  compute::HashJoinOptions hash_join;
   const compute::FunctionOptions* pick = nullptr;
 };
 static const struct { const char* name; Type id; } kTypeNames[] = {
@@ -447,6 +449,19 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
         }
         p->pick = &p->group_by;
       }
+      if (k == "left_keys" || k == "right_keys") {   // hash_join: names split at ',' as the group_by keys are
+        std::vector<std::string>& names = k == "left_keys" ? p->hash_join.LeftKeys : p->hash_join.RightKeys;
+        size_t q = 0;
+        while (q <= v.size()) {
+          size_t e = v.find(',', q);
+          if (e == std::string::npos) e = v.size();
+          std::string item = v.substr(q, e - q);
+          if (!item.empty() || e < v.size()) names.push_back(item);
+          q = e + 1;
+        }
+        p->pick = &p->hash_join;
+      }
+      if (k == "type") { p->hash_join.JoinType = v; p->pick = &p->hash_join; }
       if (k == "order" || k == "null_placement") {
         if (p->sort.Keys.empty()) p->sort.Keys.push_back(compute::SortKey());
         if (k == "order") p->sort.Keys[0].Order = v == "descending" ? compute::SortOrderDescending : compute::SortOrderAscending;

@@ -289,7 +289,7 @@ static std::string TypesToString(const std::vector<const DataType*>& types) {
 static Status ArgTypes(const std::vector<Datum>& args, std::vector<const DataType*>* types) {
   for (auto& a : args) {
     if (a.kind == DatumKind::None) return Status::Make(StatusCode::Invalid, "invalid datum");
-    if (a.kind == DatumKind::Record) return Status::Make(StatusCode::NotImplemented, "record batch arguments are only understood by filter, take, sort_indices, sort and group_by");
+    if (a.kind == DatumKind::Record) return Status::Make(StatusCode::NotImplemented, "record batch arguments are only understood by filter, take, sort_indices, sort, group_by and hash_join");
     types->push_back(a.type());
   }
   return Status::OK();
@@ -780,6 +780,7 @@ FunctionRegistry* GetFunctionRegistry() {
     RegisterVectorSort(r);
     RegisterFusedExtensions(r);
     RegisterGroupBy(r);
+    RegisterHashJoin(r);
     return r;
   }();
   return reg;

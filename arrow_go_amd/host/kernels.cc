@@ -9,6 +9,7 @@
 #include <cmath>
 #include "arrowhip_compute.h"
 
+#include <algorithm>
 #include <cstring>
 
 namespace arrowhip {
@@ -2091,6 +2092,212 @@ Status GroupByImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Dat
 
 void RegisterGroupBy(FunctionRegistry* reg) {
   reg->AddFunction(std::make_shared<MetaFunction>("group_by", Arity{1, false}, nullptr, GroupByImpl), false);
+}
+
+// ---- hash_join (no reference analogue: arrow-go has no join) ------------------------------------------------------
+// Two RecordDatums in, one out.  The key columns of both sides are laid end to end, position by position, and ONE ah_group_ids call
+// gives every row of both sides a dense id in one id space: equal key tuples ARE equal ids (the equality of ah_group_ids: bytes).  A
+// null is one more value to ah_group_ids, so each side also carries a row-validity bitmap — the AND of its key columns' validity —
+// and a row under a cleared bit matches nothing.  The right side becomes a CSR by id (ah_join_build); the left side is counted and
+// expanded into two index vectors (ah_join_count, ah_join_expand), or into a mask (ah_join_match_bits) for the semi / anti joins;
+// every output column is an array_take with those indices, a filter with that mask.
+namespace {
+
+enum class JoinKind { Inner, LeftOuter, LeftSemi, LeftAnti };
+
+// the AND of the validity bitmaps of `cols` over the batch's rows: *bits == nullptr when no column has nulls; one column with nulls
+// lends its own buffer (and bit offset); more are ANDed into a bitmap of the call's
+Status JoinRowValidity(Session* s, const Datum& batch, const std::vector<int>& cols, BufferPtr* owner, const uint8_t** bits, int64_t* off) {
+  *bits = nullptr;
+  *off = 0;
+  std::vector<const ArrayData*> with_nulls;
+  for (int ci : cols) {
+    const ArrayData& a = *batch.chunks[ci];
+    if (a.null_count != 0 && a.buffers[0]) with_nulls.push_back(&a);
+  }
+  if (with_nulls.empty() || batch.num_rows == 0) return Status::OK();
+  auto vbits = [](const ArrayData* a) { return (const uint8_t*)a->buffers[0]->dptr; };
+  if (with_nulls.size() == 1) {
+    *owner = with_nulls[0]->buffers[0];
+    *bits = vbits(with_nulls[0]);
+    *off = with_nulls[0]->offset;
+    return Status::OK();
+  }
+  AHC_RETURN_NOT_OK(s->AllocateBitmap(batch.num_rows, owner));
+  uint8_t* ob = (uint8_t*)(*owner)->dptr;
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_bitmap_op(s->ctx(), AH_BIT_AND, vbits(with_nulls[0]), with_nulls[0]->offset, vbits(with_nulls[1]), with_nulls[1]->offset,
+                                              ob, 0, batch.num_rows)));
+  for (size_t i = 2; i < with_nulls.size(); i++)
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_bitmap_op(s->ctx(), AH_BIT_AND, ob, 0, vbits(with_nulls[i]), with_nulls[i]->offset, ob, 0, batch.num_rows)));
+  *bits = ob;
+  return Status::OK();
+}
+
+Status HashJoinImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Datum>& args, Datum* out) {
+  const HashJoinOptions* opts = dynamic_cast<const HashJoinOptions*>(o);
+  if (args[0].kind != DatumKind::Record || args[1].kind != DatumKind::Record)
+    return Status::Make(StatusCode::Invalid, "hash_join: both arguments must be record batches");
+  if (!opts || opts->LeftKeys.empty()) return Status::Make(StatusCode::Invalid, "hash_join: no keys (left_keys=<column>,...)");
+  const std::vector<std::string>& lnames = opts->LeftKeys;
+  const std::vector<std::string>& rnames = opts->RightKeys.empty() ? opts->LeftKeys : opts->RightKeys;
+  if (lnames.size() > 8) return Status::Make(StatusCode::Invalid, "hash_join: more than 8 keys (" + std::to_string(lnames.size()) + ")");
+  if (rnames.size() != lnames.size())
+    return Status::Make(StatusCode::Invalid, "hash_join: " + std::to_string(lnames.size()) + " left keys but " + std::to_string(rnames.size()) + " right keys");
+  JoinKind kind;
+  const std::string& jt = opts->JoinType;
+  if (jt.empty() || jt == "inner") kind = JoinKind::Inner;
+  else if (jt == "left_outer") kind = JoinKind::LeftOuter;
+  else if (jt == "left_semi") kind = JoinKind::LeftSemi;
+  else if (jt == "left_anti") kind = JoinKind::LeftAnti;
+  else return Status::Make(StatusCode::Invalid, "hash_join: unknown type '" + jt + "' (inner, left_outer, left_semi, left_anti)");
+  const bool pairs = kind == JoinKind::Inner || kind == JoinKind::LeftOuter;
+  Session* s = ctx->session;
+  const Datum &left = args[0], &right = args[1];
+  const int64_t n_left = left.num_rows, n_right = right.num_rows, n_all = n_left + n_right;
+  auto column = [](const Datum& batch, const std::string& name) -> int {
+    for (size_t i = 0; i < batch.names.size(); i++) if (batch.names[i] == name) return (int)i;
+    return -1;
+  };
+  auto type_name = [](const ArrayData& a) { return a.logical.empty() ? std::string(a.type->name) + " [" + a.type->format + "]" : a.logical; };
+  for (const Datum* b : {&left, &right})
+    for (auto& c : b->chunks)
+      if (c->on_host) return Status::Make(StatusCode::NotImplemented, "hash_join: host-resident columns are not taken; upload the batch first");
+  // the keys, position by position: names, then types — no promotion, the bytes of both sides must mean the same
+  std::vector<int> lcols, rcols;
+  for (size_t k = 0; k < lnames.size(); k++) {
+    const int li = column(left, lnames[k]), ri = column(right, rnames[k]);
+    if (li < 0) return Status::Make(StatusCode::Invalid, "hash_join: unknown key column '" + lnames[k] + "' of the left batch");
+    if (ri < 0) return Status::Make(StatusCode::Invalid, "hash_join: unknown key column '" + rnames[k] + "' of the right batch");
+    lcols.push_back(li);
+    rcols.push_back(ri);
+  }
+  for (size_t k = 0; k < lcols.size(); k++) {
+    const ArrayData &l = *left.chunks[lcols[k]], &r = *right.chunks[rcols[k]];
+    // a dictionary's indices are not its values: two indices may name equal values
+    for (const ArrayData* a : {&l, &r})
+      if (a->type->id == Type::DICTIONARY)
+        return Status::Make(StatusCode::NotImplemented, "hash_join: dictionary-typed key column '" + (a == &l ? lnames[k] : rnames[k]) + "'; decode it first");
+    const Type id = l.type->id;
+    if (!(id == Type::BOOL || IsBaseBinary(id) || IsNumeric(id) || IsFixedWidthBinary(id)))
+      return Status::Make(StatusCode::NotImplemented, "function 'hash_join' has no kernel matching input types (key: " + type_name(l) + ")");
+    if (id != r.type->id || std::string(l.type->format) != r.type->format || l.logical != r.logical)
+      return Status::Make(StatusCode::NotImplemented, "function 'hash_join' has no kernel matching input types (key '" + lnames[k] + "': " + type_name(l) +
+                                                          ", key '" + rnames[k] + "': " + type_name(r) + "; cast one side first)");
+  }
+  // the result's columns: every left column, then the right columns that are not keys
+  std::vector<int> rpayload;
+  if (pairs) {
+    for (size_t i = 0; i < right.names.size(); i++) {
+      if (std::find(rcols.begin(), rcols.end(), (int)i) != rcols.end()) continue;
+      if (column(left, right.names[i]) >= 0)
+        return Status::Make(StatusCode::Invalid, "hash_join: column '" + right.names[i] + "' is on both sides and is not a key; rename one");
+      rpayload.push_back((int)i);
+    }
+  }
+  if (n_all > ((int64_t)1 << 30))
+    return Status::Make(StatusCode::Invalid, "hash_join: " + std::to_string(n_all) + " rows on both sides together, more than 2^30");
+  // one id space for both sides: rows [0, n_left) of the concatenated keys are the left side's
+  BufferPtr ids, first_rows;
+  AHC_RETURN_NOT_OK(s->Allocate((n_all > 0 ? n_all : 1) * 4, &ids, /*zero_all=*/false));
+  int64_t ng = 0;
+  if (n_all > 0) {
+    AHC_RETURN_NOT_OK(s->Allocate((n_all + 1) * 8, &first_rows, /*zero_all=*/false));
+    std::vector<ArrayDataPtr> both(lcols.size());
+    std::vector<ah_group_key> gkeys;
+    for (size_t k = 0; k < lcols.size(); k++) {
+      AHC_RETURN_NOT_OK(Concatenate(s, {left.chunks[lcols[k]], right.chunks[rcols[k]]}, left.chunks[lcols[k]]->type, &both[k]));
+      const ArrayData& a = *both[k];
+      const Type id = a.type->id;
+      ah_group_key g{};
+      auto dptr = [&](int i) -> const uint8_t* { return a.buffers[i] ? (const uint8_t*)a.buffers[i]->dptr : nullptr; };
+      if (id == Type::BOOL) { g.bits = 1; g.data = dptr(1); }
+      else if (IsBaseBinary(id)) { g.offset_width = a.type->bit_width / 8; g.offsets = dptr(1); g.data = dptr(2); }
+      else { g.byte_width = a.type->bit_width / 8; g.data = dptr(1); }
+      g.valid = a.null_count != 0 ? dptr(0) : nullptr;
+      g.off = a.offset;
+      gkeys.push_back(g);
+    }
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_group_ids(s->ctx(), (int)gkeys.size(), gkeys.data(), n_all, (int32_t*)ids->dptr, (int64_t*)first_rows->dptr, &ng)));
+  }
+  const int32_t *lids = (const int32_t*)ids->dptr, *rids = lids + n_left;
+  BufferPtr lvalid_owner, rvalid_owner;
+  const uint8_t *lvalid, *rvalid;
+  int64_t loff, roff;
+  AHC_RETURN_NOT_OK(JoinRowValidity(s, left, lcols, &lvalid_owner, &lvalid, &loff));
+  AHC_RETURN_NOT_OK(JoinRowValidity(s, right, rcols, &rvalid_owner, &rvalid, &roff));
+  // the right side by id
+  BufferPtr starts, rows;
+  AHC_RETURN_NOT_OK(s->Allocate((ng + 1) * 8, &starts, /*zero_all=*/false));
+  AHC_RETURN_NOT_OK(s->Allocate((n_right > 0 ? n_right : 1) * 8, &rows, /*zero_all=*/false));
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_join_build(s->ctx(), rids, rvalid, roff, n_right, ng, (int64_t*)starts->dptr, (int64_t*)rows->dptr)));
+  if (!pairs) {   // semi / anti: the left rows with / without a match, through the filter path
+    BufferPtr bits;
+    AHC_RETURN_NOT_OK(s->AllocateBitmap(n_left, &bits));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_join_match_bits(s->ctx(), lids, lvalid, loff, n_left, (const int64_t*)starts->dptr, (uint8_t*)bits->dptr)));
+    if (kind == JoinKind::LeftAnti && n_left > 0) {
+      BufferPtr inverted;
+      AHC_RETURN_NOT_OK(s->AllocateBitmap(n_left, &inverted));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_copy_bitmap(s->ctx(), (const uint8_t*)bits->dptr, 0, n_left, (uint8_t*)inverted->dptr, 0, 1)));
+      bits = inverted;
+    }
+    auto mask = std::make_shared<ArrayData>();
+    mask->type = GetDataType(Type::BOOL);
+    mask->length = n_left;
+    mask->null_count = 0;
+    mask->buffers[1] = bits;
+    static const FilterOptions kDropNulls;
+    return CallFunction(ctx, "filter", &kDropNulls, {left, Datum::Of(mask)}, out);
+  }
+  // inner / left outer: count, size the result, expand
+  const int emit = kind == JoinKind::LeftOuter ? 1 : 0;
+  BufferPtr offsets, lrows, rrows, rrows_valid;
+  int64_t total = 0, unmatched = 0;
+  AHC_RETURN_NOT_OK(s->Allocate((n_left + 1) * 8, &offsets, /*zero_all=*/false));
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_join_count(s->ctx(), lids, lvalid, loff, n_left, (const int64_t*)starts->dptr, emit, (int64_t*)offsets->dptr, &total)));
+  if (total >= ((int64_t)1 << 31))
+    return Status::Make(StatusCode::Invalid, "hash_join: the result has " + std::to_string(total) + " rows, more than 2^31 - 1");
+  AHC_RETURN_NOT_OK(s->Allocate((total > 0 ? total : 1) * 8, &lrows, /*zero_all=*/false));
+  AHC_RETURN_NOT_OK(s->Allocate((total > 0 ? total : 1) * 8, &rrows, /*zero_all=*/false));
+  if (emit) AHC_RETURN_NOT_OK(s->AllocateBitmap(total, &rrows_valid));
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_join_expand(s->ctx(), lids, lvalid, loff, n_left, (const int64_t*)starts->dptr, (const int64_t*)rows->dptr,
+                                                 (const int64_t*)offsets->dptr, total, emit, (int64_t*)lrows->dptr, (int64_t*)rrows->dptr,
+                                                 emit ? (uint8_t*)rrows_valid->dptr : nullptr, emit ? &unmatched : nullptr)));
+  auto index = [&](const BufferPtr& data) {
+    auto idx = std::make_shared<ArrayData>();
+    idx->type = GetDataType(Type::INT64);
+    idx->length = total;
+    idx->null_count = 0;
+    idx->buffers[1] = data;
+    return idx;
+  };
+  ArrayDataPtr lidx = index(lrows), ridx = index(rrows);
+  if (unmatched) {   // an unmatched left row takes the right columns through Take's null-index path
+    ridx->null_count = unmatched;
+    ridx->buffers[0] = rrows_valid;
+  }
+  static const TakeOptions kNoBoundsCheck = [] { TakeOptions t; t.BoundsCheck = false; return t; }();
+  std::vector<std::string> names;
+  std::vector<ArrayDataPtr> cols;
+  for (size_t i = 0; i < left.chunks.size(); i++) {
+    Datum col;
+    AHC_RETURN_NOT_OK(CallFunction(ctx, "array_take", &kNoBoundsCheck, {Datum::Of(left.chunks[i]), Datum::Of(lidx)}, &col));
+    names.push_back(left.names[i]);
+    cols.push_back(col.array);
+  }
+  for (int ci : rpayload) {
+    Datum col;
+    AHC_RETURN_NOT_OK(CallFunction(ctx, "array_take", &kNoBoundsCheck, {Datum::Of(right.chunks[ci]), Datum::Of(ridx)}, &col));
+    names.push_back(right.names[ci]);
+    cols.push_back(col.array);
+  }
+  *out = Datum::OfRecord(std::move(names), std::move(cols), total);
+  return Status::OK();
+}
+
+}  // namespace
+
+void RegisterHashJoin(FunctionRegistry* reg) {
+  reg->AddFunction(std::make_shared<MetaFunction>("hash_join", Arity{2, false}, nullptr, HashJoinImpl), false);
 }
 
 // ---- fused extension (no reference analogue) --------------------------------

@@ -285,6 +285,39 @@ func (x *Context) GroupMean(sumType arrow.Type, sums, counts unsafe.Pointer, ngr
 	return x.err(C.ah_group_mean(x.c, C.int(sumType), sums, (*C.int64_t)(counts), C.int64_t(ngroups), (*C.double)(outMeans)))
 }
 
+// JoinBuild: the build side of a hash join over caller-supplied dense group ids as a CSR (ah_join_build): outStarts[g] .. outStarts[g+1]
+// (ngroups + 1 int64) delimit, in outRows (nBuild int64 of room), the valid build rows of group g in ascending row order.
+func (x *Context) JoinBuild(buildIDs, buildValid unsafe.Pointer, voff, nBuild, ngroups int64, outStarts, outRows unsafe.Pointer) error {
+	return x.err(C.ah_join_build(x.c, (*C.int32_t)(buildIDs), (*C.uint8_t)(buildValid), C.int64_t(voff), C.int64_t(nBuild), C.int64_t(ngroups),
+		(*C.int64_t)(outStarts), (*C.int64_t)(outRows)))
+}
+
+// JoinCount: outOffsets (nProbe + 1 int64) = the exclusive scan of every probe row's match count, at least 1 with emitUnmatched
+// (ah_join_count); total is the number of rows of the join's result.
+func (x *Context) JoinCount(probeIDs, probeValid unsafe.Pointer, poff, nProbe int64, starts unsafe.Pointer, emitUnmatched bool, outOffsets unsafe.Pointer) (total int64, err error) {
+	var t C.int64_t
+	err = x.err(C.ah_join_count(x.c, (*C.int32_t)(probeIDs), (*C.uint8_t)(probeValid), C.int64_t(poff), C.int64_t(nProbe), (*C.int64_t)(starts),
+		boolInt(emitUnmatched), (*C.int64_t)(outOffsets), &t))
+	return int64(t), err
+}
+
+// JoinExpand: the probe row and the build row of every output slot, total int64 each (ah_join_expand); with emitUnmatched also the
+// validity bitmap of the build rows (outBuildValid), whose clear bits are counted in nulls.
+func (x *Context) JoinExpand(probeIDs, probeValid unsafe.Pointer, poff, nProbe int64, starts, rows, offsets unsafe.Pointer, total int64, emitUnmatched bool,
+	outProbeRows, outBuildRows, outBuildValid unsafe.Pointer) (nulls int64, err error) {
+	var nc C.int64_t
+	err = x.err(C.ah_join_expand(x.c, (*C.int32_t)(probeIDs), (*C.uint8_t)(probeValid), C.int64_t(poff), C.int64_t(nProbe), (*C.int64_t)(starts),
+		(*C.int64_t)(rows), (*C.int64_t)(offsets), C.int64_t(total), boolInt(emitUnmatched), (*C.int64_t)(outProbeRows), (*C.int64_t)(outBuildRows),
+		(*C.uint8_t)(outBuildValid), &nc))
+	return int64(nc), err
+}
+
+// JoinMatchBits: bit i of outBits = probe row i is valid and its group holds a build row (ah_join_match_bits): the mask of a semi join.
+func (x *Context) JoinMatchBits(probeIDs, probeValid unsafe.Pointer, poff, nProbe int64, starts, outBits unsafe.Pointer) error {
+	return x.err(C.ah_join_match_bits(x.c, (*C.int32_t)(probeIDs), (*C.uint8_t)(probeValid), C.int64_t(poff), C.int64_t(nProbe), (*C.int64_t)(starts),
+		(*C.uint8_t)(outBits)))
+}
+
 // Lz4DecompressBlocks: independent LZ4 blocks of the device bytes src inflated into the device bytes dst (ah_lz4_decompress_blocks).
 // blocks holds 4 values per block {srcOff, srcLen (bit 62: stored), dstOff, dstLen ≤ 65536}, dstOff ascending; status receives one
 // byte per block (0 ok, 1 corrupt, 2 produced != dstLen) and nbad is the number of blocks with a status — those leave unspecified

@@ -561,6 +561,41 @@ int ah_group_min_max_typed(ah_ctx* ctx, int type, const int32_t* ids, int64_t ng
                            int64_t voff, int64_t n, void* out_mins, void* out_maxs, int64_t* out_counts);
 int ah_group_mean(ah_ctx* ctx, int sum_type, const void* sums, const int64_t* counts, int64_t ngroups, double* out_means);
 
+/* ---- hash join over CALLER-SUPPLIED dense group ids (NEW — no reference analogue: arrow-go has no join; definition in DESIGN.md
+ * §3.2a) -------------------------------------------------------------------------------------------------------------------
+ * Both sides carry ids from ONE id space (one ah_group_ids call over the left rows followed by the right rows), so equal keys are
+ * equal ids.  PRECONDITION, as for the ah_group_* aggregates: 0 <= id < ngroups for every row; the ids are not checked.  Each side
+ * has an optional row-validity bitmap (row i = bit off + i); a cleared bit means "a key column is null here": the row matches nothing.
+ * Row numbers, starts and offsets are int64.  <= 2^30 rows per side and call.
+ *
+ * ah_join_build   the build side as a CSR.  out_starts (ngroups + 1 entries): out_starts[g] .. out_starts[g + 1] delimit, in
+ *                 out_rows (n_build entries of room), the VALID build rows of group g in ASCENDING row order; out_starts[0] = 0 and
+ *                 out_starts[ngroups] = the number of valid rows.  The entries of out_rows behind that are unspecified.  n_build == 0:
+ *                 ngroups + 1 zeros, out_rows untouched.  ngroups < 2^31 - 1.  Synchronises (the sort's read-backs).
+ * ah_join_count   m[i] = out_starts[id + 1] - out_starts[id] of probe row i, 0 under a cleared validity bit; with emit_unmatched
+ *                 (left outer join) max(m[i], 1).  out_offsets (n_probe + 1 entries) = the exclusive scan of m;
+ *                 *out_total_host = out_offsets[n_probe], the rows of the result.  Synchronises once.
+ * ah_join_expand  the two index vectors of the result, `total` entries each.  Output slot j belongs to the probe row i with
+ *                 offsets[i] <= j < offsets[i + 1]: out_probe_rows[j] = i, out_build_rows[j] = rows[starts[id_i] + (j - offsets[i])].
+ *                 emit_unmatched: the one slot of a probe row without a match gets build row 0 and a CLEAR bit j in out_build_valid
+ *                 (ceil(total / 8) bytes, bit 0 = slot 0; every other slot's bit is set, the bits at and above `total` in the last
+ *                 byte are 0) and *out_null_count_host (nullable) = the clear bits below `total`, which takes a synchronisation.
+ *                 Without emit_unmatched out_build_valid and out_null_count_host are not touched (the count is set to 0).  starts /
+ *                 rows: ah_join_build's; offsets / total: ah_join_count's for the same probe arguments and the same emit_unmatched.
+ *                 Nothing behind `total` entries of either vector is written; total == 0 touches nothing.  Work is split by OUTPUT
+ *                 SLOT, 2048 per workgroup: a probe row with a million matches costs what a million rows with one match cost.
+ * ah_join_match_bits  bit i of out_bits (ceil(n_probe / 8) bytes, written whole, tail bits 0) = probe row i is valid and its
+ *                 group holds a valid build row: the mask of a semi join; inverted, of an anti join.  No host synchronisation. */
+int ah_join_build(ah_ctx* ctx, const int32_t* build_ids, const uint8_t* build_valid, int64_t voff, int64_t n_build, int64_t ngroups,
+                  int64_t* out_starts, int64_t* out_rows);
+int ah_join_count(ah_ctx* ctx, const int32_t* probe_ids, const uint8_t* probe_valid, int64_t poff, int64_t n_probe, const int64_t* starts,
+                  int emit_unmatched, int64_t* out_offsets, int64_t* out_total_host);
+int ah_join_expand(ah_ctx* ctx, const int32_t* probe_ids, const uint8_t* probe_valid, int64_t poff, int64_t n_probe, const int64_t* starts,
+                   const int64_t* rows, const int64_t* offsets, int64_t total, int emit_unmatched, int64_t* out_probe_rows,
+                   int64_t* out_build_rows, uint8_t* out_build_valid, int64_t* out_null_count_host);
+int ah_join_match_bits(ah_ctx* ctx, const int32_t* probe_ids, const uint8_t* probe_valid, int64_t poff, int64_t n_probe,
+                       const int64_t* starts, uint8_t* out_bits);
+
 /* ---- LZ4 blocks inflated in HBM (NEW — no reference analogue: the reference inflates IPC bodies on the host, arrow/ipc/
  * compression.go:25-72; definition in DESIGN.md §3.8) ----------------------------------------------------------------
  * src / dst: device memory.  blocks_host: 4 int64 per block {src_off, src_len, dst_off, dst_len}; src_len bit 62 set = stored block
