@@ -185,6 +185,8 @@ _SIGS = {
     "ah_group_sum_typed": [_vp, _int, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp],
     "ah_group_min_max_typed": [_vp, _int, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "ah_group_mean": [_vp, _int, _vp, _vp, _i64, _vp],
+    "ah_group_m2": [_vp, _int, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "ah_group_variance": [_vp, _vp, _vp, _i64, _int, _int, _vp],
     "ah_join_build": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
     "ah_join_count": [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp, _pi64],
     "ah_join_expand": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _pi64],

@@ -772,6 +772,16 @@ class Context:
         """out_means[g] = float64(sums[g]) / float64(counts[g]), 0.0 where the count is 0; sum_type: AH_INT64, AH_UINT64 or AH_FLOAT64"""
         check(self.handle, lib.ah_group_mean(self.handle, sum_type, _ptr(sums), _ptr(counts), ngroups, _ptr(out_means)))
 
+    def group_m2(self, type_id: int, ids, ngroups: int, vals, vvalid, voff: int, n: int, out_means, out_m2, out_counts) -> None:
+        """means, sums of squared deviations from the mean and valid counts (ngroups float64 / float64 / int64) of a value column of any
+        numeric type id, read at its own width and taken as cast to float64; the bytes are the same on every run and launch geometry"""
+        check(self.handle, lib.ah_group_m2(self.handle, type_id, _ptr(ids), ngroups, _ptr(vals), _ptr(vvalid), voff, n, _ptr(out_means),
+                                           _ptr(out_m2), _ptr(out_counts)))
+
+    def group_variance(self, m2, counts, ngroups: int, ddof: int, take_sqrt: bool, out) -> None:
+        """out[g] = m2[g] / float64(counts[g] - ddof), its square root with take_sqrt; 0.0 where counts[g] <= ddof"""
+        check(self.handle, lib.ah_group_variance(self.handle, _ptr(m2), _ptr(counts), ngroups, ddof, 1 if take_sqrt else 0, _ptr(out)))
+
     # ---- hash join over dense group ids (ah_join.hip): ids int32, row numbers / starts / offsets int64, validity = bit off + row -----------
     def join_build(self, build_ids, build_valid, voff: int, n_build: int, ngroups: int, out_starts, out_rows) -> None:
         """out_starts[g] .. out_starts[g + 1] (ngroups + 1 entries) delimit, in out_rows (n_build entries of room), the valid build rows

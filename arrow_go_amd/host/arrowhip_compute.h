@@ -318,8 +318,10 @@ struct RoundOptions : FunctionOptions { int64_t NDigits = 0; RoundMode Mode = Ro
 struct RoundToMultipleOptions : FunctionOptions { ScalarPtr Multiple; RoundMode Mode = RoundHalfToEven; const char* TypeName() const override { return "RoundToMultipleOptions"; } };
 // group_by (no reference analogue — arrow-go has no hash aggregate): the key columns and the aggregates by column NAME,
 // as pyarrow's Table.group_by(keys).aggregate([(column, function), …]) writes them.  Function: sum, mean, min, max, count, count_all
-// (count_all has no column).
-struct GroupByAggregate { std::string Function, Column; };
+// (count_all has no column), variance, stddev, count_distinct.  Ddof (delta degrees of freedom, pyarrow's VarianceOptions.ddof) belongs
+// to variance and stddev alone: the option string's third field, "variance:v:1".  DdofGiven: the field was written; a field that is
+// not a non-negative integer arrives as Ddof = −1, and group_by answers it with Invalid.
+struct GroupByAggregate { std::string Function, Column; int Ddof = 0; bool DdofGiven = false; };
 struct GroupByOptions : FunctionOptions {
   std::vector<std::string> Keys;
   std::vector<GroupByAggregate> Aggregates;

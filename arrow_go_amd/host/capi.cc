@@ -328,7 +328,7 @@ AHC_EXPORT int ahc_datum_info(ahc_datum* d, int* kind, int* type_id, int64_t* le
 //   sort_keys=<col>:<asc|desc>:<at_end|at_start>,…                                                (SortOptions, several keys)
 //   ndigits=<n>   round_mode=down|up|towards_zero|towards_infinity|half_down|half_up|half_towards_zero|half_towards_infinity|
 //   half_to_even|half_to_odd   multiple=<type>:<value>                                            (RoundOptions / RoundToMultipleOptions)
-//   keys=<name>,…   aggregates=<sum|mean|min|max|count>:<name>,…,count_all                          (GroupByOptions)
+//   keys=<name>,…   aggregates=<sum|mean|min|max|count|count_distinct>:<name>,…,<variance|stddev>:<name>[:<ddof>],…,count_all   (GroupByOptions)
 //   left_keys=<name>,…   right_keys=<name>,…   type=inner|left_outer|left_semi|left_anti            (HashJoinOptions)
 //   skip_nulls=0|1   start=<type>:<value>|null:<type>   (e.g. start=int64:10, start=double:1.5, start=null:int32)
 struct ParsedOptions {
@@ -434,7 +434,7 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
         }
         p->pick = &p->sort;
       }
-      if (k == "keys" || k == "aggregates") {   // group_by: names split at ',', an aggregate at its first ':' ("sum:v"; "count_all" has no column)
+      if (k == "keys" || k == "aggregates") {   // group_by: names split at ',', an aggregate at its ':' ("sum:v", "variance:v:1"; "count_all" has no column)
         size_t q = 0;
         while (q <= v.size()) {
           size_t e = v.find(',', q);
@@ -442,8 +442,16 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
           std::string item = v.substr(q, e - q);
           if (k == "keys") { if (!item.empty() || e < v.size()) p->group_by.Keys.push_back(item); }
           else if (!item.empty()) {
-            size_t c = item.find(':');
-            p->group_by.Aggregates.push_back({item.substr(0, c), c == std::string::npos ? std::string() : item.substr(c + 1)});
+            size_t c = item.find(':'), c2 = c == std::string::npos ? c : item.find(':', c + 1);
+            compute::GroupByAggregate ag;
+            ag.Function = item.substr(0, c);
+            if (c != std::string::npos) ag.Column = item.substr(c + 1, c2 == std::string::npos ? c2 : c2 - c - 1);
+            if (c2 != std::string::npos) {   // the third field: ddof, decimal digits only; anything else is −1, which group_by refuses
+              const std::string d = item.substr(c2 + 1);
+              ag.DdofGiven = true;
+              ag.Ddof = !d.empty() && d.size() <= 9 && d.find_first_not_of("0123456789") == std::string::npos ? atoi(d.c_str()) : -1;
+            }
+            p->group_by.Aggregates.push_back(ag);
           }
           q = e + 1;
         }

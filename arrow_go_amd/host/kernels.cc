@@ -1905,14 +1905,34 @@ void RegisterVectorCumulative(FunctionRegistry* reg) {
 // ---- group_by (no reference analogue: arrow-go has no hash aggregate) --------------------------------------------
 // One RecordDatum in, one out: the key columns gathered at every group's first row, then one column per aggregate, rows = groups in
 // first-seen order.  ah_group_ids runs once per call; per value column the typed aggregates of ah_group_agg.hip run once each and
-// are shared by the aggregates that name the column (sum + mean + count: one ah_group_sum_typed, one ah_group_mean).
+// are shared by the aggregates that name the column (sum + mean + count: one ah_group_sum_typed, one ah_group_mean; variance + stddev
+// at any ddof + mean + count: one ah_group_m2, then one ah_group_variance per output column).  count_distinct is a composition: a
+// second ah_group_ids over the pair (group id, value), the group id and the value's validity bit gathered at every pair's first row,
+// and ah_group_count over those.
 namespace {
 
 struct GroupByColumnWork {   // what the aggregates naming one value column need, and what has been computed for it
-  bool sum = false, min_max = false, count = false;
-  BufferPtr sums, mins, maxs, means, counts, validity;
+  bool sum = false, mean = false, min_max = false, count = false, m2 = false, distinct = false;
+  bool means_done = false;   // ah_group_m2 has left the means
+  BufferPtr sums, mins, maxs, means, m2s, counts, distinct_counts, validity;
   int64_t nulls = 0;   // groups without a valid value
+  std::map<int, std::pair<BufferPtr, int64_t>> ddof_validity;   // ddof > 0 → bits of counts > ddof (null: all set), groups with counts ≤ ddof
 };
+
+// a column as ah_group_ids takes it; false: not a type it takes
+bool GroupKeyOf(const ArrayData& a, ah_group_key* out) {
+  const Type id = a.type->id;
+  ah_group_key k{};
+  auto dptr = [&](int i) -> const uint8_t* { return a.buffers[i] ? (const uint8_t*)a.buffers[i]->dptr : nullptr; };
+  if (id == Type::BOOL) { k.bits = 1; k.data = dptr(1); }
+  else if (IsBaseBinary(id)) { k.offset_width = a.type->bit_width / 8; k.offsets = dptr(1); k.data = dptr(2); }
+  else if (IsNumeric(id) || IsFixedWidthBinary(id)) { k.byte_width = a.type->bit_width / 8; k.data = dptr(1); }
+  else return false;
+  k.valid = a.null_count != 0 ? dptr(0) : nullptr;
+  k.off = a.offset;
+  *out = k;
+  return true;
+}
 
 Status GroupByImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Datum>& args, Datum* out) {
   const GroupByOptions* opts = dynamic_cast<const GroupByOptions*>(o);
@@ -1943,13 +1963,7 @@ Status GroupByImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Dat
     // a dictionary's indices are not its values: two indices may name equal values
     if (id == Type::DICTIONARY) return Status::Make(StatusCode::NotImplemented, "group_by: dictionary-typed key column '" + name + "'; decode it first");
     ah_group_key k{};
-    auto dptr = [&](int i) -> const uint8_t* { return a.buffers[i] ? (const uint8_t*)a.buffers[i]->dptr : nullptr; };
-    if (id == Type::BOOL) { k.bits = 1; k.data = dptr(1); }
-    else if (IsBaseBinary(id)) { k.offset_width = a.type->bit_width / 8; k.offsets = dptr(1); k.data = dptr(2); }
-    else if (IsNumeric(id) || IsFixedWidthBinary(id)) { k.byte_width = a.type->bit_width / 8; k.data = dptr(1); }
-    else return no_kernel("key", a);
-    k.valid = a.null_count != 0 ? dptr(0) : nullptr;
-    k.off = a.offset;
+    if (!GroupKeyOf(a, &k)) return no_kernel("key", a);
     key_cols.push_back(ci);
     gkeys.push_back(k);
   }
@@ -1963,15 +1977,28 @@ Status GroupByImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Dat
       count_all = true;
       continue;
     }
-    if (f != "sum" && f != "mean" && f != "min" && f != "max" && f != "count")
+    const bool moment = f == "variance" || f == "stddev";
+    if (f != "sum" && f != "mean" && f != "min" && f != "max" && f != "count" && f != "count_distinct" && !moment)
       return Status::Make(StatusCode::Invalid, "group_by: unknown aggregate '" + f + "'");
+    if (ag.DdofGiven && !moment)
+      return Status::Make(StatusCode::Invalid, "group_by: ddof is an option of variance and stddev, not of '" + f + "' ('" + f + ":" + ag.Column + ":<ddof>')");
+    if (ag.Ddof < 0)
+      return Status::Make(StatusCode::Invalid, "group_by: the ddof of '" + f + ":" + ag.Column + "' must be an integer >= 0");
     const int ci = column(ag.Column);
     if (ci < 0) return Status::Make(StatusCode::Invalid, "group_by: unknown column '" + ag.Column + "' of aggregate '" + f + "'");
     const ArrayData& a = *batch.chunks[ci];
     GroupByColumnWork& w = work[ci];
     if (f == "count") { w.count = true; continue; }
-    if (!IsNumeric(a.type->id) || ((f == "sum" || f == "mean") && !a.logical.empty())) return no_kernel(f, a);
-    if (f == "sum" || f == "mean") w.sum = true; else w.min_max = true;
+    if (f == "count_distinct") {
+      if (a.type->id == Type::DICTIONARY)
+        return Status::Make(StatusCode::NotImplemented, "group_by: count_distinct of the dictionary-typed column '" + ag.Column + "'; decode it first");
+      ah_group_key k{};
+      if (!GroupKeyOf(a, &k)) return no_kernel(f, a);
+      w.distinct = true;
+      continue;
+    }
+    if (!IsNumeric(a.type->id) || ((f == "sum" || f == "mean" || moment) && !a.logical.empty())) return no_kernel(f, a);
+    if (f == "sum") w.sum = true; else if (f == "mean") w.mean = true; else if (moment) w.m2 = true; else w.min_max = true;
   }
   // ids and first rows, once
   BufferPtr ids, first_rows;
@@ -2001,12 +2028,62 @@ Status GroupByImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Dat
     const ArrayData& a = *batch.chunks[kv.first];
     GroupByColumnWork& w = kv.second;
     const uint8_t* vvalid = a.buffers[0] && a.null_count != 0 ? (const uint8_t*)a.buffers[0]->dptr : nullptr;
-    const int width = w.sum || w.min_max ? a.type->bit_width / 8 : 0;
+    // the mean is ah_group_m2's where that runs anyway — but an 8-byte integer's stays the wrapping sum's quotient, as without a variance
+    const bool m2_mean = w.m2 && !(IsInteger(a.type->id) && a.type->bit_width == 64);
+    const bool need_sum = w.sum || (w.mean && !m2_mean);
+    const bool reads = need_sum || w.min_max || w.m2;
+    const int width = reads ? a.type->bit_width / 8 : 0;
     const uint8_t* vals = width && a.buffers[1] ? (const uint8_t*)a.buffers[1]->dptr + a.offset * width : nullptr;
     AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.counts, /*zero_all=*/false));
-    if (w.sum) {
-      AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.sums, /*zero_all=*/false));
+    if (w.m2) {
       AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.means, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.m2s, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_group_m2(s->ctx(), (int)a.type->id, idp, ng, vals, vvalid, a.offset, n, (double*)w.means->dptr, (double*)w.m2s->dptr,
+                                                  (int64_t*)w.counts->dptr)));
+      w.means_done = m2_mean;
+    }
+    if (w.distinct && ng > 0) {
+      ah_group_key pair[2] = {};
+      pair[0].byte_width = 4;
+      pair[0].data = (const uint8_t*)idp;
+      GroupKeyOf(a, &pair[1]);
+      BufferPtr pair_ids, pair_rows;
+      AHC_RETURN_NOT_OK(s->Allocate(n * 4, &pair_ids, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->Allocate((n + 1) * 8, &pair_rows, /*zero_all=*/false));
+      int64_t npairs = 0;
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_group_ids(s->ctx(), 2, pair, n, (int32_t*)pair_ids->dptr, (int64_t*)pair_rows->dptr, &npairs)));
+      auto rows = std::make_shared<ArrayData>();
+      rows->type = GetDataType(Type::INT64);
+      rows->length = npairs;
+      rows->null_count = 0;
+      rows->buffers[1] = pair_rows;
+      static const TakeOptions kNoBoundsCheck = [] { TakeOptions t; t.BoundsCheck = false; return t; }();
+      auto all_ids = std::make_shared<ArrayData>();
+      all_ids->type = GetDataType(Type::INT32);
+      all_ids->length = n;
+      all_ids->null_count = 0;
+      all_ids->buffers[1] = ids;
+      Datum gids, vbits;
+      AHC_RETURN_NOT_OK(CallFunction(ctx, "array_take", &kNoBoundsCheck, {Datum::Of(all_ids), Datum::Of(rows)}, &gids));
+      if (vvalid) {   // the value's validity bits, gathered as the values of a Boolean column that lies where the bitmap lies
+        auto valid_bits = std::make_shared<ArrayData>();
+        valid_bits->type = GetDataType(Type::BOOL);
+        valid_bits->length = n;
+        valid_bits->offset = a.offset;
+        valid_bits->null_count = 0;
+        valid_bits->buffers[1] = a.buffers[0];
+        AHC_RETURN_NOT_OK(CallFunction(ctx, "array_take", &kNoBoundsCheck, {Datum::Of(valid_bits), Datum::Of(rows)}, &vbits));
+      }
+      if (gids.array->offset != 0) return Status::Make(StatusCode::Invalid, "group_by: the gather returned a sliced array");
+      AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.distinct_counts, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_group_count(s->ctx(), (const int32_t*)gids.array->buffers[1]->dptr, ng,
+                                                     vvalid ? (const uint8_t*)vbits.array->buffers[1]->dptr : nullptr, vvalid ? vbits.array->offset : 0, npairs,
+                                                     (int64_t*)w.distinct_counts->dptr)));
+    }
+    if (w.distinct && ng == 0) AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.distinct_counts, /*zero_all=*/false));
+    if (need_sum) {
+      AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.sums, /*zero_all=*/false));
+      if (!w.means) AHC_RETURN_NOT_OK(s->Allocate(room * 8, &w.means, /*zero_all=*/false));
       AHC_RETURN_NOT_OK(s->FromStatus(ah_group_sum_typed(s->ctx(), (int)a.type->id, idp, ng, vals, vvalid, a.offset, n, w.sums->dptr, (int64_t*)w.counts->dptr)));
     }
     if (w.min_max) {
@@ -2015,31 +2092,42 @@ Status GroupByImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Dat
       AHC_RETURN_NOT_OK(s->FromStatus(ah_group_min_max_typed(s->ctx(), (int)a.type->id, idp, ng, vals, vvalid, a.offset, n, w.mins->dptr, w.maxs->dptr,
                                                              (int64_t*)w.counts->dptr)));
     }
-    if (!w.sum && !w.min_max)
+    if (!need_sum && !w.min_max && !w.m2 && w.count)
       AHC_RETURN_NOT_OK(s->FromStatus(ah_group_count(s->ctx(), idp, ng, vvalid, a.offset, n, (int64_t*)w.counts->dptr)));
     // a group holds at least one row, so only a column with nulls can leave a group without a valid value: validity = counts != 0
-    if (vvalid && ng > 0 && (w.sum || w.min_max)) {
+    // (variance and stddev at ddof > 0: validity = counts > ddof, whether the column has nulls or not)
+    auto count_validity = [&](const char* cmp, int64_t bound, BufferPtr* validity, int64_t* nulls) -> Status {
       auto counts = std::make_shared<ArrayData>();
       counts->type = GetDataType(Type::INT64);
       counts->length = ng;
       counts->null_count = 0;
       counts->buffers[1] = w.counts;
-      auto zero = std::make_shared<Scalar>();
-      zero->type = counts->type;
-      zero->valid = true;
+      auto than = std::make_shared<Scalar>();
+      than->type = counts->type;
+      than->valid = true;
+      memcpy(than->value, &bound, 8);
       Datum bits;
-      AHC_RETURN_NOT_OK(CallFunction(ctx, "not_equal", nullptr, {Datum::Of(counts), Datum::Of(zero)}, &bits));
+      AHC_RETURN_NOT_OK(CallFunction(ctx, cmp, nullptr, {Datum::Of(counts), Datum::Of(than)}, &bits));
       ArraySpan span;
       span.type = GetDataType(Type::BOOL);
       span.len = ng;
       span.offset = bits.array->offset;
       span.buffers[0].WrapBuffer(bits.array->buffers[1]);
-      AHC_RETURN_NOT_OK(span.UpdateNullCount(s, &w.nulls));
-      if (w.nulls) {
+      AHC_RETURN_NOT_OK(span.UpdateNullCount(s, nulls));
+      if (*nulls) {
         if (bits.array->offset != 0) return Status::Make(StatusCode::Invalid, "group_by: the comparison returned a sliced bitmap");
-        w.validity = bits.array->buffers[1];
+        *validity = bits.array->buffers[1];
       }
-    }
+      return Status::OK();
+    };
+    if (vvalid && ng > 0 && (need_sum || w.min_max || w.m2)) AHC_RETURN_NOT_OK(count_validity("not_equal", 0, &w.validity, &w.nulls));
+    if (w.m2 && ng > 0)
+      for (auto& ag : opts->Aggregates)
+        if ((ag.Function == "variance" || ag.Function == "stddev") && column(ag.Column) == kv.first && ag.Ddof > 0 && !w.ddof_validity.count(ag.Ddof)) {
+          auto& v = w.ddof_validity[ag.Ddof];
+          v.second = 0;
+          AHC_RETURN_NOT_OK(count_validity("greater", ag.Ddof, &v.first, &v.second));
+        }
   }
   BufferPtr all_counts;
   if (count_all) {
@@ -2064,12 +2152,27 @@ Status GroupByImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Dat
     if (f == "count") {
       col->type = GetDataType(Type::INT64);
       col->buffers[1] = w.counts;
+    } else if (f == "count_distinct") {
+      col->type = GetDataType(Type::INT64);
+      col->buffers[1] = w.distinct_counts;
+    } else if (f == "variance" || f == "stddev") {
+      BufferPtr vals;
+      AHC_RETURN_NOT_OK(s->Allocate(room * 8, &vals, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_group_variance(s->ctx(), (const double*)w.m2s->dptr, (const int64_t*)w.counts->dptr, ng, ag.Ddof, f == "stddev",
+                                                        (double*)vals->dptr)));
+      col->type = GetDataType(Type::FLOAT64);
+      col->buffers[1] = vals;
+      if (ag.Ddof > 0 && ng > 0) { col->buffers[0] = w.ddof_validity[ag.Ddof].first; col->null_count = w.ddof_validity[ag.Ddof].second; }
+      else { col->buffers[0] = w.validity; col->null_count = w.nulls; }
     } else {
       col->null_count = w.nulls;
       col->buffers[0] = w.validity;
       if (f == "sum") {
         col->type = GetDataType(IsFloating(a.type->id) ? Type::FLOAT64 : IsSignedInteger(a.type->id) ? Type::INT64 : Type::UINT64);
         col->buffers[1] = w.sums;
+      } else if (f == "mean" && w.means_done) {
+        col->type = GetDataType(Type::FLOAT64);
+        col->buffers[1] = w.means;
       } else if (f == "mean") {
         const int sum_type = IsFloating(a.type->id) ? AH_FLOAT64 : IsSignedInteger(a.type->id) ? AH_INT64 : AH_UINT64;
         AHC_RETURN_NOT_OK(s->FromStatus(ah_group_mean(s->ctx(), sum_type, w.sums->dptr, (const int64_t*)w.counts->dptr, ng, (double*)w.means->dptr)));

@@ -285,6 +285,24 @@ func (x *Context) GroupMean(sumType arrow.Type, sums, counts unsafe.Pointer, ngr
 	return x.err(C.ah_group_mean(x.c, C.int(sumType), sums, (*C.int64_t)(counts), C.int64_t(ngroups), (*C.double)(outMeans)))
 }
 
+// GroupM2: the means, the sums of squared deviations from the mean and the valid counts of every group (ah_group_m2) for a value
+// column of any numeric type id, read at its own width and taken as cast to Float64.  outMeans / outM2 hold ngroups float64,
+// outCounts ngroups int64; the bytes are the same on every run.
+func (x *Context) GroupM2(typeID arrow.Type, ids unsafe.Pointer, ngroups int64, vals, vvalid unsafe.Pointer, voff, n int64, outMeans, outM2, outCounts unsafe.Pointer) error {
+	return x.err(C.ah_group_m2(x.c, C.int(typeID), (*C.int32_t)(ids), C.int64_t(ngroups), vals, (*C.uint8_t)(vvalid), C.int64_t(voff), C.int64_t(n),
+		(*C.double)(outMeans), (*C.double)(outM2), (*C.int64_t)(outCounts)))
+}
+
+// GroupVariance: out[g] = m2[g] / float64(counts[g] - ddof), its square root with takeSqrt, 0 where counts[g] <= ddof
+// (ah_group_variance).
+func (x *Context) GroupVariance(m2, counts unsafe.Pointer, ngroups int64, ddof int, takeSqrt bool, out unsafe.Pointer) error {
+	s := 0
+	if takeSqrt {
+		s = 1
+	}
+	return x.err(C.ah_group_variance(x.c, (*C.double)(m2), (*C.int64_t)(counts), C.int64_t(ngroups), C.int(ddof), C.int(s), (*C.double)(out)))
+}
+
 // JoinBuild: the build side of a hash join over caller-supplied dense group ids as a CSR (ah_join_build): outStarts[g] .. outStarts[g+1]
 // (ngroups + 1 int64) delimit, in outRows (nBuild int64 of room), the valid build rows of group g in ascending row order.
 func (x *Context) JoinBuild(buildIDs, buildValid unsafe.Pointer, voff, nBuild, ngroups int64, outStarts, outRows unsafe.Pointer) error {
