@@ -319,6 +319,22 @@ def num_functions() -> int:
     return int(lib.ahc_num_functions())
 
 
+def select_k_options(k, sort_keys=None, order: str = "ascending", null_placement: str = "at_end") -> str:
+    """The options string of select_k: "k=<k>" beside "sort_keys=<column>:<asc|desc>:<at_end|at_start>,…" (a record batch: most
+    significant key first) or "order=…;null_placement=…" (one array).  Only what cannot be written into the string is refused
+    here (k must be an integer >= 0); the keys are the library's to judge, as for sort_indices."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise ValueError(f"select_k: k must be an integer >= 0, not {k!r}")
+    if sort_keys is None:
+        return f"k={k};order={order};null_placement={null_placement}"
+    items = []
+    for key in sort_keys:
+        key = (key,) if isinstance(key, int) else tuple(key)
+        col, ordr, npl = key[0], key[1] if len(key) > 1 else "asc", key[2] if len(key) > 2 else "at_end"
+        items.append(f"{int(col)}:{ {'ascending': 'asc', 'descending': 'desc'}.get(ordr, ordr)}:{npl}")
+    return "k=%d;sort_keys=%s" % (k, ",".join(items))
+
+
 class Session:
     """A device session: ah_ctx + ExecCtx with its own child registry."""
 
@@ -452,7 +468,8 @@ class Session:
     def set_option(self, name: str, value: int) -> None:
         """ExecCtx fields of this session: 'chunk_bytes' (ExecCtx.ChunkSize's role for host-resident arguments), 'host_threshold_bytes';
         for the read_ipc calls that follow: 'ipc_device_lz4' (1: LZ4_FRAME bodies of independent blocks are inflated in HBM, 0: on the
-        host like every other compressed body), 'ipc_device_lz4_min_bytes' (smaller compressed bodies stay on the host)."""
+        host like every other compressed body), 'ipc_device_lz4_min_bytes' (smaller compressed bodies stay on the host);
+        'select_k_route' (0: select_k chooses its route, 1: the radix route, 2: the sort with its final widening cut at k)."""
         self._check(lib.ahc_session_set_option(self.h, name.encode(), int(value)))
 
     def import_host(self, arr) -> "DeviceArray":
@@ -624,6 +641,14 @@ class Session:
             if any(ch in name for ch in ",:;="):
                 raise ValueError(f"group_by: column name {name!r} cannot be written into an options string")
         return self.call_function("group_by", [batch], "keys=%s;aggregates=%s" % (",".join(keys), ",".join(items)), keep_on_device=keep_on_device)
+
+    def select_k(self, values, k, sort_keys=None, order: str = "ascending", null_placement: str = "at_end", keep_on_device: bool = False):
+        """call_function("select_k", [values], "k=…;…"): the first min(k, rows) entries of sort_indices with the same keys — uint64
+        row numbers, stable, NaNs next to the nulls — without sorting the column when the first key is an integer or float column
+        (ORDER BY … LIMIT k).  values: an array, a chunked array or a record batch; sort_keys (a record batch): [(column index,
+        'asc' | 'desc', 'at_end' | 'at_start'), …], most significant first; one array: order and null_placement.  The session
+        option 'select_k_route' (0 auto, 1 radix, 2 sort) forces a route; the result does not depend on it."""
+        return self.call_function("select_k", [values], select_k_options(k, sort_keys, order, null_placement), keep_on_device=keep_on_device)
 
     def hash_join(self, left, right, keys, right_keys=None, join_type: str = "inner", keep_on_device: bool = False):
         """call_function("hash_join", [left, right], "left_keys=…;right_keys=…;type=…"): the two record batches joined on their key

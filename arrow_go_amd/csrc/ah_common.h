@@ -184,11 +184,15 @@ int ah_partition_by_group(ah_ctx* ctx, const int32_t* ids, const unsigned long l
 // applicable or a bucket came out too large — the pairs are clobbered and the caller regenerates them for the LSD passes
 int ah_sort_rest_msd(ah_ctx* ctx, unsigned long long* keys, unsigned* rows, unsigned long long* alt_keys, unsigned* alt_rows, int64_t n,
                      unsigned long long varying, unsigned long long kmin, unsigned long long kmax, int float_bytes, int descending, void* tmp,
-                     unsigned long long* out64, int* used);
+                     unsigned long long* out64, int64_t out64_n, int* used);
 size_t ah_sort_msd_temp_bytes(int64_t n);   // size of `tmp`; 0: the path does not apply to n pairs
 // internal (ah_sort.hip): (key, row) pairs sorted by the full 64-bit key with the stable LSD passes; *sorted_keys = where the keys ended up
 int ah_sort_pairs_lsd(ah_ctx* ctx, unsigned long long* keys, unsigned* rows, unsigned long long* alt_keys, unsigned* alt_rows, int64_t n,
                       unsigned* hist, unsigned* offs, unsigned long long** sorted_keys);
+// internal (ah_sort.hip): the m rows `rows` (row numbers of the keys' columns, not in the temp arena; NULL: rows 0 … m − 1)
+// ordered by the keys as ah_sort_indices_keys orders all rows, the first min(head, m) entries of the order written; rows that
+// tie on every key keep their order in `rows`.  Takes the temp arena.  The keys are checked as ah_sort_indices_keys checks them.
+int ah_sort_rows_keys(ah_ctx* ctx, int nkeys, const ah_sort_key* keys, const unsigned* rows, int64_t m, int64_t head, uint64_t* out_indices);
 // internal (ah_take_binned.hip): Take for random indices into a column the caches cannot hold; *used says whether it ran
 int ah_take_binned_try(ah_ctx* ctx, int byte_width, const void* values, const uint8_t* vvalid, int64_t voff, int64_t nvalues, int iw,
                        int is_signed, const void* idx, const uint8_t* ivalid, int64_t ioff, int64_t nidx, void* out_values,

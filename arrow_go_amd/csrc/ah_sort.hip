@@ -27,28 +27,6 @@
 
 namespace {
 
-enum { kCatRest = 0, kCatNaN = 1, kCatNull = 2 };
-
-// order-preserving unsigned key, zero-extended to 64 bits
-template <typename T>
-__device__ __forceinline__ unsigned long long make_key(T v, bool descending) {
-  using U = typename std::make_unsigned<typename std::conditional<std::is_floating_point<T>::value,
-                                                                    typename std::conditional<sizeof(T) == 4, int, long long>::type, T>::type>::type;
-  constexpr U sign = (U)1 << (sizeof(T) * 8 - 1);
-  U k;
-  if constexpr (std::is_floating_point<T>::value) {
-    if (v == (T)0) v = (T)0;  // −0.0 → +0.0: they tie (cmp.Compare)
-    U b = __builtin_bit_cast(U, v);
-    k = (b & sign) ? (U)~b : (U)(b | sign);
-  } else if constexpr (std::is_signed<T>::value) {
-    k = (U)v ^ sign;
-  } else {
-    k = (U)v;
-  }
-  if (descending) k = (U)~k;
-  return (unsigned long long)k;
-}
-
 // ---- the element source of a pass -------------------------------------------------------------
 // Column<T>: pass (1) — reads the column, digit = category, emits (key, row).
 // Pairs:     an LSD pass — reads (key, row) pairs, digit = a key byte.
@@ -202,7 +180,7 @@ int sort_by_column(ah_ctx* c, SortBuffers& b, const void* values, const uint8_t*
     if (rows_in == nullptr && nvar >= 4 && c->opt_sort_msd) {
       int used = -1;
       if ((rc = ah_sort_rest_msd(c, kcur, rcur, kalt, ralt, rest_n, varying, kmin, kmax, std::is_floating_point<T>::value ? (int)sizeof(T) : 0, descending, b.msd_tmp,
-                                 (unsigned long long*)(rest_n == n ? b.final_out : nullptr), &used)) != AH_OK) return rc;
+                                 (unsigned long long*)(rest_n == n ? b.final_out : nullptr), b.final_n, &used)) != AH_OK) return rc;
       if (used > 0) {
         done = true;   // sorted rows are in rcur (each bucket is rewritten in place) — or already widened in the output
         b.emitted = rest_n == n && b.final_out != nullptr;
@@ -237,7 +215,9 @@ int sort_dispatch(ah_ctx* c, SortBuffers& b, const SortCol& k, int64_t n, const 
   return ah_fail(c, AH_ENOTIMPL, "sorting not supported for type %d", k.type);  // vector_sort.go:266-268
 }
 
-int sort_keys(ah_ctx* c, int nkeys, const SortCol* keys, int64_t n, uint64_t* out) {
+// rows0: the rows to order, n of them (NULL: rows 0 … n − 1).  Rows that tie on every key keep the order they have in rows0.
+// head ≥ 0: only the first `head` (≤ n) entries of the order are written to `out`.
+int sort_keys(ah_ctx* c, int nkeys, const SortCol* keys, int64_t n, uint64_t* out, const unsigned* rows0 = nullptr, int64_t head = -1) {
   SortBuffers b;
   const int64_t ntiles = ah_ceil_div(n, kTile);
   int rc;
@@ -263,8 +243,8 @@ int sort_keys(ah_ctx* c, int nkeys, const SortCol* keys, int64_t n, uint64_t* ou
   if (any_binary)
     for (int i = 0; i < kBinArrays; i++) tmp.take((size_t)n * 4, &b.bin[i]);
   // lexicographic order by keys 0..k−1 = stable sorts by key k−1, …, key 0 in turn (every pass is stable)
-  const unsigned* rows_in = nullptr;
-  if (nkeys == 1) b.final_out = out;
+  const unsigned* rows_in = rows0;
+  if (nkeys == 1) { b.final_out = out; b.final_n = head < 0 ? n : head; }
   for (int k = nkeys - 1; k >= 0; k--) {
     if ((rc = sort_dispatch(c, b, keys[k], n, rows_in)) != AH_OK) return rc;
     if (k > 0) {
@@ -273,7 +253,8 @@ int sort_keys(ah_ctx* c, int nkeys, const SortCol* keys, int64_t n, uint64_t* ou
     }
   }
   if (!b.emitted) {
-    emit_kernel<<<ah_stream_grid(c, ah_ceil_div(n, kBlock), 8), kBlock, 0, c->stream>>>(b.ra, n, out);
+    const int64_t written = head < 0 ? n : head;
+    emit_kernel<<<ah_stream_grid(c, ah_ceil_div(written, kBlock), 8), kBlock, 0, c->stream>>>(b.ra, written, out);
     AH_LAUNCH_CHECK(c);
   }
   return AH_OK;
@@ -338,6 +319,15 @@ static int check_key(ah_ctx* c, const ah_sort_key& k, SortCol* col) {
   if (rc != AH_OK) return rc;
   col->values = (const uint8_t*)k.values + k.off * ah_type_width(k.type);
   return AH_OK;
+}
+
+int ah_sort_rows_keys(ah_ctx* c, int nkeys, const ah_sort_key* keys, const unsigned* rows, int64_t m, int64_t head, uint64_t* out_indices) {
+  std::vector<SortCol> cols((size_t)nkeys);
+  for (int k = 0; k < nkeys; k++) {
+    const int rc = check_key(c, keys[k], &cols[k]);
+    if (rc != AH_OK) return rc;
+  }
+  return m > 0 && head > 0 ? sort_keys(c, nkeys, cols.data(), m, out_indices, rows, head < m ? head : m) : AH_OK;
 }
 
 AH_EXPORT int ah_sort_indices(ah_ctx* c, int type, const void* values, const uint8_t* valid, int64_t off, int64_t n, int descending,

@@ -299,7 +299,7 @@ struct C64 {
 constexpr int kMsRowBits = 27;   // the MSD path takes ≤ 2^27 rows (ah_sort_msd_temp_bytes)
 template <int SLOTS>
 __device__ __forceinline__ void ms_sort_bucket(const unsigned long long* __restrict__ keys, const unsigned* rows, unsigned s, int m,
-                                               int lane, unsigned* out_rows, unsigned long long* __restrict__ out64) {
+                                               int lane, unsigned* out_rows, unsigned long long* __restrict__ out64, unsigned out_n) {
   KR x[SLOTS];
 #pragma unroll
   for (int sl = 0; sl < SLOTS; sl++) {   // slots past the bucket hold the largest pair
@@ -307,7 +307,7 @@ __device__ __forceinline__ void ms_sort_bucket(const unsigned long long* __restr
     x[sl].k = i < m ? keys[s + i] : ~0ull;
     x[sl].r = i < m ? rows[s + i] : ~0u;
   }
-  auto emit = [&](int i, unsigned row) { if (i < m) { if (out64) out64[s + i] = row; else out_rows[s + i] = row; } };
+  auto emit = [&](int i, unsigned row) { if (i < m) { if (out64) { if (s + i < out_n) out64[s + i] = row; } else out_rows[s + i] = row; } };
   if (SLOTS <= 2) {
     const unsigned long long k0 = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(x[0].k >> 32)) << 32) |
                                   __builtin_amdgcn_readfirstlane((unsigned)x[0].k);   // lane 0 of slot 0 is inside the bucket (m ≥ 1)
@@ -366,7 +366,7 @@ __device__ __forceinline__ void ms_sort_bucket(const unsigned long long* __restr
 
 __global__ __launch_bounds__(256) void ms_local_kernel(const unsigned long long* __restrict__ keys, const unsigned* rows,
                                                         const unsigned* __restrict__ bstart, int64_t nbuckets, unsigned* out_rows,
-                                                        unsigned long long* __restrict__ out64, unsigned* __restrict__ oversize,
+                                                        unsigned long long* __restrict__ out64, unsigned out_n, unsigned* __restrict__ oversize,
                                                         unsigned* __restrict__ big_list) {
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -381,11 +381,11 @@ __global__ __launch_bounds__(256) void ms_local_kernel(const unsigned long long*
     }
     return;
   }
-  if (m == 1) { if (lane == 0) { if (out64) out64[s] = rows[s]; else out_rows[s] = rows[s]; } return; }
-  if (m <= 64) ms_sort_bucket<1>(keys, rows, s, m, lane, out_rows, out64);
-  else if (m <= 128) ms_sort_bucket<2>(keys, rows, s, m, lane, out_rows, out64);
-  else if (m <= 256) ms_sort_bucket<4>(keys, rows, s, m, lane, out_rows, out64);   // the tail of the size distribution: a few buckets in a million
-  else ms_sort_bucket<8>(keys, rows, s, m, lane, out_rows, out64);
+  if (m == 1) { if (lane == 0) { if (out64) { if (s < out_n) out64[s] = rows[s]; } else out_rows[s] = rows[s]; } return; }
+  if (m <= 64) ms_sort_bucket<1>(keys, rows, s, m, lane, out_rows, out64, out_n);
+  else if (m <= 128) ms_sort_bucket<2>(keys, rows, s, m, lane, out_rows, out64, out_n);
+  else if (m <= 256) ms_sort_bucket<4>(keys, rows, s, m, lane, out_rows, out64, out_n);   // the tail of the size distribution: a few buckets in a million
+  else ms_sort_bucket<8>(keys, rows, s, m, lane, out_rows, out64, out_n);
 }
 
 // A bucket of 513 … 8192 rows (the rows beyond the sample's extremes, a run of equal keys): one workgroup, bitonic network in LDS.
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(256) void ms_local_kernel(const unsigned long long*
 __global__ __launch_bounds__(kThreads) void ms_big_kernel(const unsigned long long* __restrict__ keys, const unsigned* rows,
                                                            const unsigned* __restrict__ bstart, const unsigned* __restrict__ oversize,
                                                            const unsigned* __restrict__ big_list, unsigned* out_rows,
-                                                           unsigned long long* __restrict__ out64) {
+                                                           unsigned long long* __restrict__ out64, unsigned out_n) {
   __shared__ unsigned long long s_k[kBigMax];
   __shared__ unsigned s_r[kBigMax];
   if (blockIdx.x >= oversize[1] || blockIdx.x >= (unsigned)kBigList) return;
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(kThreads) void ms_big_kernel(const unsigned long lo
       __syncthreads();
     }
   }
-  for (int i = threadIdx.x; i < m; i += kThreads) { if (out64) out64[s + i] = s_r[i]; else out_rows[s + i] = s_r[i]; }
+  for (int i = threadIdx.x; i < m; i += kThreads) { if (out64) { if (s + i < out_n) out64[s + i] = s_r[i]; } else out_rows[s + i] = s_r[i]; }
 }
 
 }  // namespace
@@ -443,11 +443,11 @@ size_t ah_sort_msd_temp_bytes(int64_t n) {
 }
 
 // keys / rows: the `rest` range (n pairs, row order).  alt_keys / alt_rows: same-sized scratch.  tmp: ah_sort_msd_temp_bytes(n) bytes.
-// *used = 1: the rows are in sorted order in `rows` — or, if out64 is given, widened in out64[0 .. n) and NOT in `rows`.
+// *used = 1: the rows are in sorted order in `rows` — or, if out64 is given, widened in out64[0 .. out64_n) (out64_n ≤ n: the head of the order) and NOT in `rows`.
 // *used = 0: gave up half-way, keys / rows / alt_* are clobbered.  *used = −1: not attempted, nothing touched.
 int ah_sort_rest_msd(ah_ctx* c, unsigned long long* keys, unsigned* rows, unsigned long long* alt_keys, unsigned* alt_rows, int64_t n,
                      unsigned long long varying, unsigned long long kmin, unsigned long long kmax, int float_bytes, int descending, void* tmp,
-                     unsigned long long* out64, int* used) {
+                     unsigned long long* out64, int64_t out64_n, int* used) {
   *used = -1;
   if (!tmp || varying == 0 || ah_sort_msd_temp_bytes(n) == 0) return AH_OK;
   unsigned* out_rows = rows;   // the last step rewrites every bucket in place
@@ -526,9 +526,9 @@ int ah_sort_rest_msd(ah_ctx* c, unsigned long long* keys, unsigned* rows, unsign
                                                                       rows, nullptr);
   AH_LAUNCH_CHECK(c);
   // 4: buckets
-  ms_local_kernel<<<(unsigned)ah_ceil_div((int64_t)nbuckets, 4), 256, 0, c->stream>>>(keys, rows, bstart, (int64_t)nbuckets, out_rows, out64, oversize, big_list);
+  ms_local_kernel<<<(unsigned)ah_ceil_div((int64_t)nbuckets, 4), 256, 0, c->stream>>>(keys, rows, bstart, (int64_t)nbuckets, out_rows, out64, (unsigned)out64_n, oversize, big_list);
   AH_LAUNCH_CHECK(c);
-  ms_big_kernel<<<kBigList, kThreads, 0, c->stream>>>(keys, rows, bstart, oversize, big_list, out_rows, out64);
+  ms_big_kernel<<<kBigList, kThreads, 0, c->stream>>>(keys, rows, bstart, oversize, big_list, out_rows, out64, (unsigned)out64_n);
   AH_LAUNCH_CHECK(c);
   AH_HIP(c, hipMemcpyAsync(&c->pinned[12], oversize, 8, hipMemcpyDeviceToHost, c->stream));
   AH_HIP(c, hipStreamSynchronize(c->stream));

@@ -1,8 +1,10 @@
 // ah_sort_radix.h — the stable 8-bit LSD radix pass shared by the sorts (ah_sort.hip: numeric keys and the group-by
-// partition; ah_sort_binary.hip: binary, fixed-size binary and decimal keys) and the temporaries of one sort_indices call.
+// partition; ah_sort_binary.hip: binary, fixed-size binary and decimal keys; ah_select.hip: the survivors of select_k), the
+// order-preserving key and the row categories of a numeric sort key, and the temporaries of one sort_indices call.
 // Everything here lives in an anonymous namespace: every translation unit that includes it gets its own instances.
 #pragma once
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 #include "ah_common.h"
 #include "ah_reduce.h"
@@ -19,6 +21,29 @@ constexpr int kMaxTilesPerBlock = 8;             // tiles one workgroup handles 
 
 // small inputs keep one tile per workgroup (parallelism), large ones eight (fewer histogram rows)
 static inline int tiles_per_block(int64_t n) { return n >= ((int64_t)1 << 24) ? kMaxTilesPerBlock : 1; }
+
+// the three categories of a sort key's rows and the key transform: shared by the sort (ah_sort.hip) and select_k (ah_select.hip)
+enum { kCatRest = 0, kCatNaN = 1, kCatNull = 2 };
+
+// order-preserving unsigned key, zero-extended to 64 bits
+template <typename T>
+__device__ __forceinline__ unsigned long long make_key(T v, bool descending) {
+  using U = typename std::make_unsigned<typename std::conditional<std::is_floating_point<T>::value,
+                                                                    typename std::conditional<sizeof(T) == 4, int, long long>::type, T>::type>::type;
+  constexpr U sign = (U)1 << (sizeof(T) * 8 - 1);
+  U k;
+  if constexpr (std::is_floating_point<T>::value) {
+    if (v == (T)0) v = (T)0;  // −0.0 → +0.0: they tie (cmp.Compare)
+    U b = __builtin_bit_cast(U, v);
+    k = (b & sign) ? (U)~b : (U)(b | sign);
+  } else if constexpr (std::is_signed<T>::value) {
+    k = (U)v ^ sign;
+  } else {
+    k = (U)v;
+  }
+  if (descending) k = (U)~k;
+  return (unsigned long long)k;
+}
 
 struct Pairs {
   const unsigned long long* keys;
@@ -239,6 +264,7 @@ constexpr int kBinArrays = 8;
 struct SortBuffers {  // temporaries shared by all keys of one call
   void* msd_tmp = nullptr;  // ah_sort_msd.hip's tables (nullptr: that path is off for this call)
   uint64_t* final_out = nullptr;  // single-key call: where the widened result goes; the MSD path writes it directly when every row is `rest`
+  int64_t final_n = 0;            // … and how many entries of the order go there (n, or the head select_k asks for)
   bool emitted = false;
   unsigned long long *ka, *kb, *andor;
   unsigned *ra, *rb, *rc;  // ra / rb: ping-pong of a key's passes; rc: the previous key's result

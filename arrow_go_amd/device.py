@@ -659,6 +659,15 @@ class Context:
             s.descending, s.nulls_at_start = int(d), int(nf)
         check(self.handle, lib.ah_sort_indices_keys(self.handle, len(keys), arr, n, _ptr(out_indices)))
 
+    def select_k(self, keys, n: int, k: int, out_indices, route: int = 0) -> None:
+        """the first min(k, n) entries sort_indices_keys gives for the same keys, into out_indices (ah_select_k); route: 0 auto,
+        1 the radix route (a numeric first key), 2 the sort with its final widening cut at k entries"""
+        arr = (SortKey * len(keys))()
+        for s, (t, v, o, w, m, off, d, nf) in zip(arr, keys):
+            s.type, s.values, s.offsets, s.byte_width, s.valid, s.off = t, _ptr(v), _ptr(o), w, _ptr(m), off
+            s.descending, s.nulls_at_start = int(d), int(nf)
+        check(self.handle, lib.ah_select_k(self.handle, len(keys), arr, n, k, route, _ptr(out_indices)))
+
     def take_boolean(self, data, vvalid, voff: int, nvalues: int, idx_byte_width: int, idx_signed: bool, idx, ivalid, ioff: int, nidx: int,
                      out_data, out_valid) -> int:
         r, bad = C.c_int64(), C.c_int64()

@@ -309,6 +309,13 @@ struct SortOptions : FunctionOptions {
   std::vector<SortKey> Keys;
   const char* TypeName() const override { return "SortKeys"; }
 };
+// select_k: the first K entries of sort_indices(Keys) — Arrow C++'s SelectKOptions (the reference has no select_k; the keys are
+// compute.SortOptions' keys and order as sort_indices orders)
+struct SelectKOptions : FunctionOptions {
+  int64_t K = -1;   // −1: not given
+  std::vector<SortKey> Keys;
+  const char* TypeName() const override { return "SelectKOptions"; }
+};
 // kernels.CumulativeOptions (vector_cumulative.go:30-39): nil Start = zero of the input type
 struct CumulativeOptions : FunctionOptions { ScalarPtr Start; bool SkipNulls = false; const char* TypeName() const override { return "CumulativeOptions"; } };
 // kernels.RoundMode / RoundOptions / RoundToMultipleOptions (rounding.go:37-66, 93-104; defaults arithmetic.go:78-80)
@@ -387,6 +394,8 @@ struct ExecCtx {
   int64_t ChunkBytes = 0;
   // ahc_import_host keeps an array on the host from this many value bytes on; smaller ones are uploaded at import
   int64_t HostThresholdBytes = (int64_t)64 << 20;
+  // select_k: the route handed to ah_select_k (AH_SELECT_AUTO 0, AH_SELECT_RADIX 1, AH_SELECT_SORT 2)
+  int SelectKRoute = 0;
 };
 
 // ---- host-resident arguments (hoststream.cc) --------------------------------------------------------------------------------

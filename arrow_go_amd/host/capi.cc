@@ -253,6 +253,10 @@ AHC_EXPORT int ahc_session_set_option(ahc_session* s, const char* name, int64_t 
   if (value < 0) return Fail(s, Status::Make(StatusCode::Invalid, "option '" + n + "': negative value"));
   if (n == "chunk_bytes") s->ectx.ChunkBytes = value;
   else if (n == "host_threshold_bytes") s->ectx.HostThresholdBytes = value;
+  else if (n == "select_k_route") {
+    if (value > 2) return Fail(s, Status::Make(StatusCode::Invalid, "option 'select_k_route': 0 (auto), 1 (radix) or 2 (sort)"));
+    s->ectx.SelectKRoute = (int)value;
+  }
   else if (n == "ipc_device_lz4") s->ipc_device_lz4 = value != 0;
   else if (n == "ipc_device_lz4_min_bytes") s->ipc_device_lz4_min_bytes = value;
   else return Fail(s, Status::Make(StatusCode::KeyError, "unknown session option '" + n + "'"));
@@ -339,6 +343,7 @@ struct ParsedOptions {
   compute::CastOptions cast;
   compute::SetOptions set;
   compute::SortOptions sort;
+  compute::SelectKOptions select_k;
   compute::RoundOptions round;
   compute::RoundToMultipleOptions round_multiple;
   compute::GroupByOptions group_by;
@@ -476,6 +481,12 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
         else p->sort.Keys[0].Placement = v == "at_start" ? compute::SortNullsAtStart : compute::SortNullsAtEnd;
         p->pick = &p->sort;
       }
+      if (k == "k") {   // select_k: digits with an optional sign; anything else is −1, which select_k refuses
+        const size_t d0 = !v.empty() && (v[0] == '-' || v[0] == '+') ? 1 : 0;
+        const bool digits = v.size() > d0 && v.size() <= 18 && v.find_first_not_of("0123456789", d0) == std::string::npos;
+        p->select_k.K = digits ? strtoll(v.c_str(), nullptr, 10) : -1;
+        if (p->select_k.K < 0) p->select_k.K = -1;
+      }
       if (k == "ndigits") { p->round.NDigits = strtoll(v.c_str(), nullptr, 10); p->pick = &p->round; }
       if (k == "multiple") { p->round_multiple.Multiple = ParseScalarText(v); p->pick = &p->round_multiple; }
       if (k == "round_mode") {
@@ -499,6 +510,12 @@ AHC_EXPORT int ahc_call(ahc_session* s, const char* name, const char* options, i
   for (int i = 0; i < nargs; i++) a.push_back(args[i]->d);
   ParsedOptions po;
   ParseOptions(options, &po);
+  const std::string fname = name ? name : "";
+  if (fname == "select_k" || fname == "select_k_unstable") {   // k beside either spelling of the sort keys; a missing k stays −1
+    po.select_k.Keys = po.sort.Keys;
+    if (po.select_k.Keys.empty()) po.select_k.Keys.push_back(compute::SortKey());
+    po.pick = &po.select_k;
+  }
   Datum res;
   // (host-resident arguments are compute::CallFunction's business: streamed span by span where the function allows it, uploaded
   // whole — once, ArrayData::device_twin — where it does not)

@@ -1705,40 +1705,42 @@ void RegisterScalarSetLookup(FunctionRegistry* reg) {
 // ---- sort_indices / sort ------------------------------------------------------------------------------
 // sortIndicesMetaFunc → sortIndicesImpl (compute/vector_sort.go:42-52, 117-190) → kernels.SortIndices
 // (kernels/vector_sort.go:388-481), array input: one key, ColumnIndex ignored; uint64 indices, no nulls
-static Status SortIndicesImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Datum>& args_in, Datum* out) {
-  const SortOptions* opts = dynamic_cast<const SortOptions*>(o);
-  if (!opts || opts->Keys.empty()) return Status::Make(StatusCode::Invalid, "must provide at least one sort key");  // :119-121
-  Session* s = ctx->session;
+// What sort_indices and select_k share: the arguments as equal-length arrays (a record batch → its columns, a chunked column →
+// its concatenation) and the options' keys as ah_sort_keys over them.  `fn` names the caller in the messages.
+static Status PrepareSortKeys(Session* s, const char* fn, const std::vector<SortKey>& keys_in, const std::vector<Datum>& args_in,
+                              std::vector<Datum>* args_out, std::vector<ah_sort_key>* skeys, int64_t* length_out) {
+  const std::string name = fn;
+  if (keys_in.empty()) return Status::Make(StatusCode::Invalid, "must provide at least one sort key");  // :119-121
   // a chunked column is sorted as its logical concatenation: the indices address the whole column
   // (compute/vector_sort.go:144-148, SortIndicesChunked :226)
-  std::vector<Datum> args = args_in;
+  std::vector<Datum>& args = *args_out;
+  args = args_in;
   if (args.size() == 1 && args[0].kind == DatumKind::Record) {  // KindRecord (:150-166): the keys name columns of the batch
     std::vector<Datum> cols;
     for (auto& c : args_in[0].chunks) cols.push_back(Datum::Of(c));
-    if (cols.empty()) return Status::Make(StatusCode::Invalid, "sort_indices: record batch without columns");
+    if (cols.empty()) return Status::Make(StatusCode::Invalid, name + ": record batch without columns");
     args = cols;
   }
   for (auto& a : args) {
     if (a.kind != DatumKind::Chunked) continue;
-    if (a.chunks.empty()) return Status::Make(StatusCode::NotImplemented, "sort_indices of a chunked array without chunks");
+    if (a.chunks.empty()) return Status::Make(StatusCode::NotImplemented, name + " of a chunked array without chunks");
     ArrayDataPtr whole;
     AHC_RETURN_NOT_OK(Concatenate(s, a.chunks, a.chunked_type, &whole));
     a = Datum::Of(whole);
   }
   // one array: the first key, ColumnIndex ignored (:130-141); several arrays = the columns of a record batch,
   // every key names its column (:153-166)
-  std::vector<SortKey> keys = opts->Keys;
+  std::vector<SortKey> keys = keys_in;
   if (args.size() == 1) { keys.resize(1); keys[0].ColumnIndex = 0; }
   if (keys.size() > 8)  // maxRadixSortKeys (kernels/vector_sort.go:60): beyond it the reference switches comparator
-    return Status::Make(StatusCode::NotImplemented, "sort_indices: more than 8 sort keys");
+    return Status::Make(StatusCode::NotImplemented, name + ": more than 8 sort keys");
   int64_t length = -1;
   for (auto& a : args) {
     if (a.kind != DatumKind::Array)
-      return Status::Make(StatusCode::NotImplemented, "unsupported type for sort_indices operation: the accelerated path sorts arrays");
+      return Status::Make(StatusCode::NotImplemented, "unsupported type for " + name + " operation: the accelerated path sorts arrays");
     if (length < 0) length = a.array->length;
     else if (length != a.array->length) return Status::Make(StatusCode::Invalid, "all columns must have the same length");  // kernels :403-407
   }
-  std::vector<ah_sort_key> skeys;
   for (size_t i = 0; i < keys.size(); i++) {
     const SortKey& key = keys[i];
     if (key.ColumnIndex < 0 || key.ColumnIndex >= (int)args.size())
@@ -1762,15 +1764,54 @@ static Status SortIndicesImpl(ExecCtx* ctx, const FunctionOptions* o, const std:
     k.off = a.offset;
     k.descending = key.Order == SortOrderDescending;
     k.nulls_at_start = key.Placement == SortNullsAtStart;
-    skeys.push_back(k);
+    skeys->push_back(k);
   }
+  *length_out = length;
+  return Status::OK();
+}
+
+// `length` uint64 row numbers without nulls, not yet written
+static Status AllocateIndices(Session* s, int64_t length, std::shared_ptr<ArrayData>* out) {
   auto res = std::make_shared<ArrayData>();
   res->type = GetDataType(Type::UINT64);
   res->length = length;
   res->null_count = 0;
   AHC_RETURN_NOT_OK(s->Allocate(length * 8, &res->buffers[1], /*zero_all=*/false));
+  *out = res;
+  return Status::OK();
+}
+
+static Status SortIndicesImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Datum>& args_in, Datum* out) {
+  const SortOptions* opts = dynamic_cast<const SortOptions*>(o);
+  if (!opts || opts->Keys.empty()) return Status::Make(StatusCode::Invalid, "must provide at least one sort key");  // :119-121
+  Session* s = ctx->session;
+  std::vector<Datum> args;
+  std::vector<ah_sort_key> skeys;
+  int64_t length = 0;
+  AHC_RETURN_NOT_OK(PrepareSortKeys(s, "sort_indices", opts->Keys, args_in, &args, &skeys, &length));
+  std::shared_ptr<ArrayData> res;
+  AHC_RETURN_NOT_OK(AllocateIndices(s, length, &res));
   if (length > 0)
     AHC_RETURN_NOT_OK(s->FromStatus(ah_sort_indices_keys(s->ctx(), (int)skeys.size(), skeys.data(), length, (uint64_t*)res->buffers[1]->dptr)));
+  *out = Datum::Of(res);
+  return Status::OK();
+}
+
+// select_k / select_k_unstable: the first min(K, length) entries of sort_indices with the same keys, without the sort where the
+// first key is numeric (ah_select_k, csrc/ah_select.hip); takes what sort_indices takes
+static Status SelectKImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Datum>& args_in, Datum* out) {
+  const SelectKOptions* opts = dynamic_cast<const SelectKOptions*>(o);
+  if (!opts || opts->K < 0) return Status::Make(StatusCode::Invalid, "select_k: a non-negative k must be given");
+  Session* s = ctx->session;
+  std::vector<Datum> args;
+  std::vector<ah_sort_key> skeys;
+  int64_t length = 0;
+  AHC_RETURN_NOT_OK(PrepareSortKeys(s, "select_k", opts->Keys, args_in, &args, &skeys, &length));
+  const int64_t k = std::min(opts->K, length);
+  std::shared_ptr<ArrayData> res;
+  AHC_RETURN_NOT_OK(AllocateIndices(s, k, &res));
+  if (k > 0)
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_select_k(s->ctx(), (int)skeys.size(), skeys.data(), length, k, ctx->SelectKRoute, (uint64_t*)res->buffers[1]->dptr)));
   *out = Datum::Of(res);
   return Status::OK();
 }
@@ -1785,6 +1826,9 @@ void RegisterVectorSort(FunctionRegistry* reg) {
         AHC_RETURN_NOT_OK(CallFunction(ctx, "sort_indices", o, args, &indices));
         return CallFunction(ctx, "take", nullptr, {args[0], indices}, out);
       }), false);
+  // one implementation under two names, like sub / subtract: Arrow C++ calls it select_k_unstable, and a stable answer is a valid one
+  for (const char* name : {"select_k", "select_k_unstable"})
+    reg->AddFunction(std::make_shared<MetaFunction>(name, Arity{1, true}, nullptr, SelectKImpl), false);
 }
 
 // ---- cumulative_sum / cumulative_sum_checked ---------------------------------------------------

@@ -467,13 +467,19 @@ type SortColumn struct {
 // SortIndicesKeys mirrors sort_indices over keys of every sortable kind (kernels/vector_sort.go:195-245): stable, lexicographic
 // by key 0, 1, …; binary values bytewise, decimals by value.  The key table is built in C memory, as in SortIndicesMulti.
 func (x *Context) SortIndicesKeys(keys []SortColumn, n int64, outIndices unsafe.Pointer) error {
-	k := len(keys)
-	if k == 0 {
+	if len(keys) == 0 {
 		return fmt.Errorf("%w: arrowhip: SortIndicesKeys wants at least one key", arrow.ErrInvalid)
 	}
+	tbl := sortKeyTable(keys)
+	defer C.free(tbl)
+	return x.err(C.ah_sort_indices_keys(x.c, C.int(len(keys)), (*C.ah_sort_key)(tbl), C.int64_t(n), (*C.uint64_t)(outIndices)))
+}
+
+// sortKeyTable is the ah_sort_key table of the keys, in C memory: the caller frees it.
+func sortKeyTable(keys []SortColumn) unsafe.Pointer {
+	k := len(keys)
 	var one C.ah_sort_key
 	tbl := C.malloc(C.size_t(k) * C.size_t(unsafe.Sizeof(one)))
-	defer C.free(tbl)
 	ks := unsafe.Slice((*C.ah_sort_key)(tbl), k)
 	for i, key := range keys {
 		typ := C.int(key.Type)
@@ -487,7 +493,27 @@ func (x *Context) SortIndicesKeys(keys []SortColumn, n int64, outIndices unsafe.
 		ks[i].valid, ks[i].off = (*C.uint8_t)(key.Valid), C.int64_t(key.Off)
 		ks[i].descending, ks[i].nulls_at_start = boolInt(key.Descending), boolInt(key.NullsAtStart)
 	}
-	return x.err(C.ah_sort_indices_keys(x.c, C.int(k), (*C.ah_sort_key)(tbl), C.int64_t(n), (*C.uint64_t)(outIndices)))
+	return tbl
+}
+
+// SelectKRoute is the route of SelectK: the library's choice, the radix route (a numeric first key), or the sort and its head.
+type SelectKRoute int
+
+const (
+	SelectKAuto  SelectKRoute = C.AH_SELECT_AUTO
+	SelectKRadix SelectKRoute = C.AH_SELECT_RADIX
+	SelectKSort  SelectKRoute = C.AH_SELECT_SORT
+)
+
+// SelectK writes the first min(k, n) entries SortIndicesKeys would write for the same keys (ORDER BY … LIMIT k), without sorting
+// the column where the first key is numeric.  outIndices holds min(k, n) uint64 row numbers.
+func (x *Context) SelectK(keys []SortColumn, n, k int64, route SelectKRoute, outIndices unsafe.Pointer) error {
+	if len(keys) == 0 {
+		return fmt.Errorf("%w: arrowhip: SelectK wants at least one key", arrow.ErrInvalid)
+	}
+	tbl := sortKeyTable(keys)
+	defer C.free(tbl)
+	return x.err(C.ah_select_k(x.c, C.int(len(keys)), (*C.ah_sort_key)(tbl), C.int64_t(n), C.int64_t(k), C.int(route), (*C.uint64_t)(outIndices)))
 }
 
 // ---- ingest slots: the building blocks of Ingest for callers that run their own kernels on the chunks ------------------------

@@ -935,6 +935,18 @@ typedef struct ah_sort_key {
  * Binary keys are sorted in rounds of 7 bytes: a round re-sorts only the rows still tied.  Data buffers of
  * the 64-bit-offset types may exceed 4 GiB.  Synchronises. */
 int ah_sort_indices_keys(ah_ctx* ctx, int nkeys, const ah_sort_key* keys, int64_t n, uint64_t* out_indices);
+/* select_k: exactly the first min(k, n) entries ah_sort_indices_keys returns for the same keys (kernels.SortIndices,
+ * kernels/vector_sort.go:388-481, cut at k: ORDER BY … LIMIT k) without sorting the column — stable, ties in input order,
+ * −0.0 ties +0.0, NaNs next to the nulls.  AH_SELECT_RADIX: a first key of an integer or float type; the threshold key by MSD
+ * histogram levels over key 0, one collecting pass, a sort of the k survivors; AH_ENOTIMPL for any other
+ * first key.  AH_SELECT_SORT: the sort with its final widening cut at k entries, for every key the sort takes.
+ * AH_SELECT_AUTO chooses on the host from n, k and the key types.  The result does not depend on the route.  k < 0:
+ * AH_EINVALID; k = 0 or n = 0 write nothing. */
+#define AH_SELECT_AUTO 0
+#define AH_SELECT_RADIX 1
+#define AH_SELECT_SORT 2
+int ah_select_k(ah_ctx* ctx, int nkeys, const ah_sort_key* keys, int64_t n, int64_t k, int route, uint64_t* out_indices);
+/* route: AH_SELECT_AUTO 0 | AH_SELECT_RADIX 1 | AH_SELECT_SORT 2.  out_indices holds min(k, n) entries.  Synchronises. */
 
 /* Boolean VALUES (booleanTakeImpl, kernels/vector_selection.go:990-1074): data and validity are bitmaps
  * indexed at voff + idx; a null output keeps data bit 0.  Output bitmaps start at bit 0.  Filter of a

@@ -139,7 +139,8 @@ int ahc_export(ahc_session* s, ahc_datum* d, struct ArrowArray* arr, struct Arro
  * first time it meets it; the copy stays with the datum, which counts as device-resident from then on (ahc_datum_on_host → 0,
  * ahc_datum_buffers → the device pointers, later calls use the copy instead of streaming).  A column larger than the free HBM can be
  * added, compared, filtered, cast and summed this way: only three spans of it are on the device at any time.
- * ahc_session_set_option: "chunk_bytes" (bytes of the widest column per span: ExecCtx.ChunkSize's role; 0 = 32 MiB),
+ * ahc_session_set_option: "select_k_route" (select_k: 0 the library chooses, 1 the radix route, 2 the sort cut at k entries),
+ * "chunk_bytes" (bytes of the widest column per span: ExecCtx.ChunkSize's role; 0 = 32 MiB),
  * "host_threshold_bytes". */
 int ahc_import_host(ahc_session* s, struct ArrowArray* arr, struct ArrowSchema* schema, ahc_datum** out);
 int ahc_datum_on_host(ahc_datum* d);
