@@ -28,6 +28,10 @@
  *     compute/exec.go:165) but serves one call at a time.
  *   - buffers must not alias unless stated; sizes are in ELEMENTS unless named
  *     nbytes / nbits.
+ *   - a call writes nothing outside the bytes its declaration gives an output — for a
+ *     bitmap, nothing outside the bits the declaration gives — whether it succeeds or
+ *     returns an error; data pointers need the alignment of their element type and no
+ *     more (an output may be an interior slice of a larger buffer).
  */
 #ifndef ARROWHIP_H
 #define ARROWHIP_H
