@@ -165,6 +165,9 @@ _SIGS = {
     "ah_sort_indices_multi": [_vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
     "ah_sort_indices_keys": [_vp, _int, _vp, _i64, _vp],
     "ah_select_k": [_vp, _int, _vp, _i64, _i64, _int, _vp],
+    "ah_window_flags": [_vp, _vp, _int, _vp, _vp, _i64, _vp],
+    "ah_window_rank": [_vp, _int, _vp, _vp, _i64, _vp],
+    "ah_window_scan": [_vp, _int, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
     "ah_take_binary_offsets": [_vp, _int, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _i64, _i64, _int, _vp, _vp, _pi64, _pi64, _pi64],
     "ah_take_binary_data": [_vp, _int, _vp, _vp, _i64, _int, _vp, _i64, _vp, _vp],
     "ah_take_boolean": [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _i64, _i64, _int, _vp, _vp, _pi64, _pi64],

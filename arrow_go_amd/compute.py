@@ -335,6 +335,72 @@ def select_k_options(k, sort_keys=None, order: str = "ascending", null_placement
     return "k=%d;sort_keys=%s" % (k, ",".join(items))
 
 
+_ORDER_WORDS = {"asc": "asc", "ascending": "asc", "desc": "desc", "descending": "desc"}
+_WINDOW_RANKS = ("row_number", "rank", "dense_rank")
+_WINDOW_SCANS = ("cumulative_sum", "cumulative_min", "cumulative_max", "cumulative_count")
+
+
+def _option_name(fn: str, name) -> str:
+    """a column name that can stand in an options string"""
+    if not isinstance(name, str) or not name:
+        raise ValueError(f"{fn}: a column name must be a non-empty string, not {name!r}")
+    if any(ch in name for ch in ",:;="):
+        raise ValueError(f"{fn}: column name {name!r} cannot be written into an options string")
+    return name
+
+
+def window_options(partition_by=(), order_by=(), functions=()) -> str:
+    """The options string of window: "partition_by=a,b;order_by=c:asc:at_end,d:desc:at_start;functions=row_number,cumulative_sum:v".
+    partition_by: column names (or one name); order_by: names or (name, 'asc' | 'desc'[, 'at_end' | 'at_start']) tuples, most
+    significant first; functions: 'row_number' | 'rank' | 'dense_rank' and (column, 'cumulative_sum' | 'cumulative_min' |
+    'cumulative_max' | 'cumulative_count') pairs, as group_by takes its aggregates.  Refused here: what cannot be written into
+    the string (names with ',', ':', ';' or '='), an unknown function, order or placement word, and an empty function list;
+    what depends on the batch (unknown columns, types, duplicate output names, more than 7 order keys) is the library's to judge."""
+    parts = [partition_by] if isinstance(partition_by, str) else list(partition_by or ())
+    orders = [order_by] if isinstance(order_by, str) else list(order_by or ())
+    funcs = [functions] if isinstance(functions, str) else list(functions or ())
+    if not funcs:
+        raise ValueError("window: no functions")
+    okeys = []
+    for key in orders:
+        key = (key,) if isinstance(key, str) else tuple(key)
+        if not 1 <= len(key) <= 3:
+            raise ValueError(f"window: an order key is a name or (name, order[, null placement]), not {key!r}")
+        ordr, npl = key[1] if len(key) > 1 else "asc", key[2] if len(key) > 2 else "at_end"
+        if ordr not in _ORDER_WORDS:
+            raise ValueError(f"window: order {ordr!r} of key {key[0]!r} is not asc or desc")
+        if npl not in ("at_end", "at_start"):
+            raise ValueError(f"window: null placement {npl!r} of key {key[0]!r} is not at_end or at_start")
+        okeys.append("%s:%s:%s" % (_option_name("window", key[0]), _ORDER_WORDS[ordr], npl))
+    items = []
+    for f in funcs:
+        if isinstance(f, str):
+            if f not in _WINDOW_RANKS:
+                raise ValueError(f"window: {f!r} is not a ranking function ({', '.join(_WINDOW_RANKS)}); a running aggregate is (column, function)")
+            items.append(f)
+            continue
+        if len(f) != 2 or f[1] not in _WINDOW_SCANS:
+            raise ValueError(f"window: a running aggregate is (column, function), function one of {', '.join(_WINDOW_SCANS)}, not {f!r}")
+        items.append("%s:%s" % (f[1], _option_name("window", f[0])))
+    return "partition_by=%s;order_by=%s;functions=%s" % (",".join(_option_name("window", p) for p in parts), ",".join(okeys), ",".join(items))
+
+
+def rank_options(sort_keys=None, order: str = "ascending", null_placement: str = "at_end", tiebreaker: str = "min") -> str:
+    """The options string of rank: "sort_keys=…" (a record batch: (column index, 'asc' | 'desc', 'at_end' | 'at_start'), most
+    significant first, as select_k_options writes them) or "order=…;null_placement=…" (one array), then "tiebreaker=min|first|dense".
+    tiebreaker 'max' is Arrow C++'s fourth choice and is not implemented: the library answers it with ErrNotImplemented."""
+    if tiebreaker not in ("min", "first", "dense", "max"):
+        raise ValueError(f"rank: tiebreaker {tiebreaker!r} is not min, first, dense or max")
+    if sort_keys is None:
+        return f"order={order};null_placement={null_placement};tiebreaker={tiebreaker}"
+    items = []
+    for key in sort_keys:
+        key = (key,) if isinstance(key, int) else tuple(key)
+        col, ordr, npl = key[0], key[1] if len(key) > 1 else "asc", key[2] if len(key) > 2 else "at_end"
+        items.append(f"{int(col)}:{_ORDER_WORDS.get(ordr, ordr)}:{npl}")
+    return "sort_keys=%s;tiebreaker=%s" % (",".join(items), tiebreaker)
+
+
 class Session:
     """A device session: ah_ctx + ExecCtx with its own child registry."""
 
@@ -649,6 +715,33 @@ class Session:
         'asc' | 'desc', 'at_end' | 'at_start'), …], most significant first; one array: order and null_placement.  The session
         option 'select_k_route' (0 auto, 1 radix, 2 sort) forces a route; the result does not depend on it."""
         return self.call_function("select_k", [values], select_k_options(k, sort_keys, order, null_placement), keep_on_device=keep_on_device)
+
+    def window(self, batch, partition_by=(), order_by=(), functions=(), keep_on_device: bool = False):
+        """call_function("window", [batch], window_options(...)): one value per INPUT row — the output has the batch's rows in the
+        batch's order and one column per function: row_number, rank, dense_rank (UInt64, 1-based, never null) and
+        "<column>_cumulative_sum" / "_min" / "_max" / "_count", the running aggregate over ROWS BETWEEN UNBOUNDED PRECEDING AND
+        CURRENT ROW of the row's partition.  Partitions: rows equal on every partition_by column as group_by's keys are equal
+        (bytes; a null is a value); no partition_by: one partition.  Order inside a partition: the stable sort order of order_by
+        (as sort_indices orders; none: the input order).  Rows that tie on every order key are peers: they share a rank; with no
+        order_by every row is its own peer group.  A running aggregate is null exactly where its input value is null and otherwise
+        covers the valid values up to and including the row; cumulative_count is never null.  Sums: Int64 / UInt64 (wrapping) /
+        Float64; min / max: the input type, NaNs ignored unless all values so far are NaN.  A pyarrow Table is taken when every
+        column has one chunk.  Column names must not contain ',', ':', ';' or '='."""
+        import pyarrow as pa
+        if isinstance(batch, pa.Table):
+            for name, col in zip(batch.schema.names, batch.columns):
+                if col.num_chunks > 1:
+                    raise ErrInvalid(f"window: column {name!r} is chunked ({col.num_chunks} chunks); combine_chunks() first")
+            batch = pa.RecordBatch.from_arrays([c.chunk(0) if c.num_chunks else pa.array([], c.type) for c in batch.columns], names=batch.schema.names)
+        return self.call_function("window", [batch], window_options(partition_by, order_by, functions), keep_on_device=keep_on_device)
+
+    def rank(self, values, sort_keys=None, order: str = "ascending", null_placement: str = "at_end", tiebreaker: str = "min",
+             keep_on_device: bool = False):
+        """call_function("rank", [values], rank_options(...)): the 1-based UInt64 rank of every row in the sort order of
+        sort_indices with the same keys — Arrow C++'s rank.  tiebreaker: 'min' rows that tie share the smallest of their positions
+        (RANK()), 'first' ties numbered in input order (ROW_NUMBER()), 'dense' ranks without gaps (DENSE_RANK()).  Nulls tie with
+        nulls, NaNs with NaNs, -0.0 with +0.0.  values: an array, a chunked array or a record batch with sort_keys."""
+        return self.call_function("rank", [values], rank_options(sort_keys, order, null_placement, tiebreaker), keep_on_device=keep_on_device)
 
     def hash_join(self, left, right, keys, right_keys=None, join_type: str = "inner", keep_on_device: bool = False):
         """call_function("hash_join", [left, right], "left_keys=…;right_keys=…;type=…"): the two record batches joined on their key

@@ -668,6 +668,26 @@ class Context:
             s.descending, s.nulls_at_start = int(d), int(nf)
         check(self.handle, lib.ah_select_k(self.handle, len(keys), arr, n, k, route, _ptr(out_indices)))
 
+    # ---- window functions (ah_window.hip): enqueued on the compute stream, no synchronisation ------------
+    def window_flags(self, part_ids, keys, order, n: int, out_flags) -> None:
+        """out_flags[p] for every sorted position p (row order[p]; order None: the identity): bit 0 a partition starts (part_ids:
+        int32 by row, or None = one partition), bit 1 a peer group starts (the rows do not tie on the keys, laid out as for
+        sort_indices_keys; descending / nulls_at_start are not looked at) (ah_window_flags)"""
+        arr = (SortKey * max(len(keys), 1))()
+        for s, (t, v, o, w, m, off, d, nf) in zip(arr, keys):
+            s.type, s.values, s.offsets, s.byte_width, s.valid, s.off = t, _ptr(v), _ptr(o), w, _ptr(m), off
+            s.descending, s.nulls_at_start = int(d), int(nf)
+        check(self.handle, lib.ah_window_flags(self.handle, _ptr(part_ids), len(keys), arr, _ptr(order), n, _ptr(out_flags)))
+
+    def window_rank(self, kind: int, flags, order, n: int, out) -> None:
+        """out[order[p]] (uint64) = kind 0 row_number, 1 rank, 2 dense_rank at sorted position p (ah_window_rank)"""
+        check(self.handle, lib.ah_window_rank(self.handle, kind, _ptr(flags), _ptr(order), n, _ptr(out)))
+
+    def window_scan(self, op: int, type_id: int, values, valid, off: int, flags, order, n: int, out_values) -> None:
+        """out_values[order[p]] = the running op (0 sum, 1 min, 2 max, 3 count) of the column over its partition up to sorted
+        position p; a null row gets payload 0 and the caller copies the validity (ah_window_scan)"""
+        check(self.handle, lib.ah_window_scan(self.handle, op, type_id, _ptr(values), _ptr(valid), off, _ptr(flags), _ptr(order), n, _ptr(out_values)))
+
     def take_boolean(self, data, vvalid, voff: int, nvalues: int, idx_byte_width: int, idx_signed: bool, idx, ivalid, ioff: int, nidx: int,
                      out_data, out_valid) -> int:
         r, bad = C.c_int64(), C.c_int64()

@@ -341,6 +341,22 @@ struct HashJoinOptions : FunctionOptions {
   std::string JoinType;
   const char* TypeName() const override { return "HashJoinOptions"; }
 };
+// window (no reference analogue — arrow-go has no window operator): partition and order columns of the record batch by
+// NAME; Functions: row_number, rank, dense_rank (no column) and cumulative_sum / _min / _max / _count of a numeric column
+struct WindowOrderKey { std::string Column; SortOrder Order = SortOrderAscending; NullPlacement Placement = SortNullsAtEnd; };
+struct WindowFunction { std::string Function, Column; };
+struct WindowOptions : FunctionOptions {
+  std::vector<std::string> PartitionBy;
+  std::vector<WindowOrderKey> OrderBy;
+  std::vector<WindowFunction> Functions;
+  const char* TypeName() const override { return "WindowOptions"; }
+};
+// rank: Arrow C++'s RankOptions over compute.SortOptions' keys; Tiebreaker: min (also ""), first, dense — max is not implemented
+struct RankOptions : FunctionOptions {
+  std::vector<SortKey> Keys;
+  std::string Tiebreaker;
+  const char* TypeName() const override { return "RankOptions"; }
+};
 struct CompareFilterSumOptions : FunctionOptions { int cmpop = AH_CMP_GT; const char* TypeName() const override { return "CompareFilterSumOptions"; } };
 
 // compute.Datum (datum.go:35-40): array or scalar
@@ -537,6 +553,7 @@ void RegisterVectorHash(FunctionRegistry* reg);
 void RegisterFusedExtensions(FunctionRegistry* reg);
 void RegisterGroupBy(FunctionRegistry* reg);
 void RegisterHashJoin(FunctionRegistry* reg);
+void RegisterWindow(FunctionRegistry* reg);
 
 // ---- compute.Expression (arrow/compute/expression.go:59-78,596-620) and its executor
 // (arrow/compute/exprs/exec.go:440-700 ExecuteScalarExpression / executeScalarBatch) --------

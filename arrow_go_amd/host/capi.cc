@@ -334,6 +334,8 @@ AHC_EXPORT int ahc_datum_info(ahc_datum* d, int* kind, int* type_id, int64_t* le
 //   half_to_even|half_to_odd   multiple=<type>:<value>                                            (RoundOptions / RoundToMultipleOptions)
 //   keys=<name>,…   aggregates=<sum|mean|min|max|count|count_distinct>:<name>,…,<variance|stddev>:<name>[:<ddof>],…,count_all   (GroupByOptions)
 //   left_keys=<name>,…   right_keys=<name>,…   type=inner|left_outer|left_semi|left_anti            (HashJoinOptions)
+//   partition_by=<name>,…   order_by=<name>[:asc|desc[:at_end|at_start]],…   functions=row_number|rank|dense_rank|cumulative_<sum|min|max|count>:<name>,…   (WindowOptions)
+//   tiebreaker=min|first|dense   beside sort_keys=… or order=…;null_placement=…                     (RankOptions)
 //   skip_nulls=0|1   start=<type>:<value>|null:<type>   (e.g. start=int64:10, start=double:1.5, start=null:int32)
 struct ParsedOptions {
   compute::FilterOptions filter;
@@ -348,6 +350,8 @@ struct ParsedOptions {
   compute::RoundToMultipleOptions round_multiple;
   compute::GroupByOptions group_by;
   compute::HashJoinOptions hash_join;
+  compute::WindowOptions window;
+  compute::RankOptions rank;
   const compute::FunctionOptions* pick = nullptr;
 };
 static const struct { const char* name; Type id; } kTypeNames[] = {
@@ -475,6 +479,36 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
         p->pick = &p->hash_join;
       }
       if (k == "type") { p->hash_join.JoinType = v; p->pick = &p->hash_join; }
+      if (k == "partition_by" || k == "order_by" || k == "functions") {   // window: items split at ',', their fields at ':'
+        size_t q = 0;
+        while (q <= v.size()) {
+          size_t e = v.find(',', q);
+          if (e == std::string::npos) e = v.size();
+          const std::string item = v.substr(q, e - q);
+          const size_t c1 = item.find(':'), c2 = c1 == std::string::npos ? c1 : item.find(':', c1 + 1);
+          const std::string f0 = item.substr(0, c1);
+          const std::string f1 = c1 == std::string::npos ? "" : item.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+          const std::string f2 = c2 == std::string::npos ? "" : item.substr(c2 + 1);
+          if (!item.empty() || e < v.size()) {   // (an empty value lists nothing; an empty item between commas is a name the batch does not have)
+            if (k == "partition_by") p->window.PartitionBy.push_back(item);
+            else if (k == "order_by") {
+              compute::WindowOrderKey key;
+              key.Column = f0;
+              key.Order = f1 == "desc" || f1 == "descending" ? compute::SortOrderDescending : compute::SortOrderAscending;
+              key.Placement = f2 == "at_start" ? compute::SortNullsAtStart : compute::SortNullsAtEnd;
+              p->window.OrderBy.push_back(key);
+            } else {
+              compute::WindowFunction fn;
+              fn.Function = f0;
+              fn.Column = c1 == std::string::npos ? "" : item.substr(c1 + 1);
+              p->window.Functions.push_back(fn);
+            }
+          }
+          q = e + 1;
+        }
+        p->pick = &p->window;
+      }
+      if (k == "tiebreaker") p->rank.Tiebreaker = v;
       if (k == "order" || k == "null_placement") {
         if (p->sort.Keys.empty()) p->sort.Keys.push_back(compute::SortKey());
         if (k == "order") p->sort.Keys[0].Order = v == "descending" ? compute::SortOrderDescending : compute::SortOrderAscending;
@@ -515,6 +549,12 @@ AHC_EXPORT int ahc_call(ahc_session* s, const char* name, const char* options, i
     po.select_k.Keys = po.sort.Keys;
     if (po.select_k.Keys.empty()) po.select_k.Keys.push_back(compute::SortKey());
     po.pick = &po.select_k;
+  }
+  if (fname == "window") po.pick = &po.window;   // also without options: the refusal is window's
+  if (fname == "rank") {   // tiebreaker beside either spelling of the sort keys
+    po.rank.Keys = po.sort.Keys;
+    if (po.rank.Keys.empty()) po.rank.Keys.push_back(compute::SortKey());
+    po.pick = &po.rank;
   }
   Datum res;
   // (host-resident arguments are compute::CallFunction's business: streamed span by span where the function allows it, uploaded

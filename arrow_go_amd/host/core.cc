@@ -781,6 +781,7 @@ FunctionRegistry* GetFunctionRegistry() {
     RegisterFusedExtensions(r);
     RegisterGroupBy(r);
     RegisterHashJoin(r);
+    RegisterWindow(r);
     return r;
   }();
   return reg;
@@ -1264,7 +1265,7 @@ const std::map<std::string, TemporalRule>& TemporalRules() {
       {"array_filter", TemporalRule::Preserve}, {"unique", TemporalRule::Preserve}, {"sort", TemporalRule::Preserve},
       {"dictionary_encode", TemporalRule::Preserve},
       {"is_null", TemporalRule::Plain}, {"is_not_null", TemporalRule::Plain}, {"sort_indices", TemporalRule::Plain},
-      {"select_k", TemporalRule::Plain}, {"select_k_unstable", TemporalRule::Plain},
+      {"select_k", TemporalRule::Plain}, {"select_k_unstable", TemporalRule::Plain}, {"rank", TemporalRule::Plain},
       {"equal", TemporalRule::Same}, {"not_equal", TemporalRule::Same}, {"greater", TemporalRule::Same}, {"greater_equal", TemporalRule::Same},
       {"less", TemporalRule::Same}, {"less_equal", TemporalRule::Same}, {"is_in", TemporalRule::Same},
       {"add", TemporalRule::Add}, {"add_unchecked", TemporalRule::Add},

@@ -2485,5 +2485,235 @@ void RegisterFusedExtensions(FunctionRegistry* reg) {
   }
 }
 
+// ---- window / rank (no reference analogue: arrow-go has no window operator) ---------------------------------------
+// window: one RecordDatum in, one out with the SAME rows in the same order and one column per function.  Five steps: dense partition
+// ids (ah_group_ids), the stable order of (partition id, order keys) (ah_sort_indices_keys; skipped when there is neither), the
+// partition / peer flags of that order (ah_window_flags), one ah_window_rank / ah_window_scan per function, and for the running
+// aggregates the input column's validity copied (ah_copy_bitmap): an output row is null exactly where the input value is.
+// rank: the same without partitions over one array or one record batch's sort keys.
+namespace {
+
+constexpr int64_t kWindowMaxRows = (int64_t)1 << 30;
+
+// the order of `keys` (column indices into `cols`, the partition ids in front when given) and its flags
+Status WindowOrderAndFlags(Session* s, const char* fn, const std::vector<Datum>& cols, const std::vector<SortKey>& keys_in, const BufferPtr& ids,
+                           int64_t n, BufferPtr* order_buf, BufferPtr* flags_buf) {
+  std::vector<Datum> args = cols;
+  std::vector<SortKey> keys;
+  if (ids) {
+    auto col = std::make_shared<ArrayData>();
+    col->type = GetDataType(Type::INT32);
+    col->length = n;
+    col->null_count = 0;
+    col->buffers[1] = ids;
+    SortKey k;
+    k.ColumnIndex = (int)args.size();
+    args.push_back(Datum::Of(col));
+    keys.push_back(k);
+  }
+  keys.insert(keys.end(), keys_in.begin(), keys_in.end());
+  std::vector<ah_sort_key> skeys;
+  const uint64_t* order = nullptr;
+  if (!keys.empty()) {
+    std::vector<Datum> flat;
+    int64_t length = 0;
+    AHC_RETURN_NOT_OK(PrepareSortKeys(s, fn, keys, args, &flat, &skeys, &length));
+    AHC_RETURN_NOT_OK(s->Allocate(n * 8, order_buf, /*zero_all=*/false));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_sort_indices_keys(s->ctx(), (int)skeys.size(), skeys.data(), n, (uint64_t*)(*order_buf)->dptr)));
+    order = (const uint64_t*)(*order_buf)->dptr;
+  }
+  const size_t first = ids ? 1 : 0;   // the flags compare the order keys; the partition id has its own bit
+  AHC_RETURN_NOT_OK(s->Allocate(n, flags_buf, /*zero_all=*/false));
+  return s->FromStatus(ah_window_flags(s->ctx(), ids ? (const int32_t*)ids->dptr : nullptr, (int)(skeys.size() - first), skeys.data() + first, order, n,
+                                       (uint8_t*)(*flags_buf)->dptr));
+}
+
+Status WindowImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Datum>& args, Datum* out) {
+  const WindowOptions* opts = dynamic_cast<const WindowOptions*>(o);
+  if (args[0].kind != DatumKind::Record) return Status::Make(StatusCode::Invalid, "window: the argument must be a record batch");
+  if (!opts || opts->Functions.empty())
+    return Status::Make(StatusCode::Invalid, "window: no functions (functions=row_number,rank,dense_rank,cumulative_sum:<column>,...)");
+  if (opts->PartitionBy.size() > 8)
+    return Status::Make(StatusCode::Invalid, "window: more than 8 partition columns (" + std::to_string(opts->PartitionBy.size()) + ")");
+  if (opts->OrderBy.size() > 7)   // the partition id is the sort's first key, and the sort takes 8
+    return Status::Make(StatusCode::Invalid, "window: more than 7 order keys (" + std::to_string(opts->OrderBy.size()) + ")");
+  Session* s = ctx->session;
+  const Datum& batch = args[0];
+  const int64_t n = batch.num_rows;
+  if (n > kWindowMaxRows) return Status::Make(StatusCode::Invalid, "window: " + std::to_string(n) + " rows, more than 2^30");
+  auto column = [&](const std::string& name) -> int {
+    for (size_t i = 0; i < batch.names.size(); i++) if (batch.names[i] == name) return (int)i;
+    return -1;
+  };
+  auto no_kernel = [](const std::string& what, const ArrayData& a) {
+    return Status::Make(StatusCode::NotImplemented, "function 'window' has no kernel matching input types (" + what + ": " +
+                                                        (a.logical.empty() ? std::string(a.type->name) : a.logical) + ")");
+  };
+  for (auto& c : batch.chunks)
+    if (c->on_host) return Status::Make(StatusCode::NotImplemented, "window: host-resident columns are not taken; upload the batch first");
+  // everything named is checked before anything runs
+  std::vector<ah_group_key> pkeys;
+  for (auto& name : opts->PartitionBy) {
+    const int ci = column(name);
+    if (ci < 0) return Status::Make(StatusCode::KeyError, "window: unknown partition column '" + name + "'");
+    const ArrayData& a = *batch.chunks[ci];
+    if (a.type->id == Type::DICTIONARY)
+      return Status::Make(StatusCode::NotImplemented, "window: dictionary-typed partition column '" + name + "'; decode it first");
+    ah_group_key k{};
+    if (!GroupKeyOf(a, &k)) return no_kernel("partition column '" + name + "'", a);
+    pkeys.push_back(k);
+  }
+  std::vector<SortKey> okeys;
+  for (auto& key : opts->OrderBy) {
+    const int ci = column(key.Column);
+    if (ci < 0) return Status::Make(StatusCode::KeyError, "window: unknown order column '" + key.Column + "'");
+    SortKey k;
+    k.ColumnIndex = ci;
+    k.Order = key.Order;
+    k.Placement = key.Placement;
+    okeys.push_back(k);
+  }
+  struct Plan { int kind; int column; std::string name; };   // kind: 0 … 2 ah_window_rank's, 10 + ah_window_scan's op
+  std::vector<Plan> plan;
+  for (auto& f : opts->Functions) {
+    Plan p{-1, -1, ""};
+    if (f.Function == "row_number") p.kind = AH_WINDOW_ROW_NUMBER;
+    else if (f.Function == "rank") p.kind = AH_WINDOW_RANK;
+    else if (f.Function == "dense_rank") p.kind = AH_WINDOW_DENSE_RANK;
+    else if (f.Function == "cumulative_sum") p.kind = 10 + AH_WINDOW_SUM;
+    else if (f.Function == "cumulative_min") p.kind = 10 + AH_WINDOW_MIN;
+    else if (f.Function == "cumulative_max") p.kind = 10 + AH_WINDOW_MAX;
+    else if (f.Function == "cumulative_count") p.kind = 10 + AH_WINDOW_COUNT;
+    else return Status::Make(StatusCode::Invalid, "window: unknown function '" + f.Function + "'");
+    if (p.kind < 10) {
+      if (!f.Column.empty()) return Status::Make(StatusCode::Invalid, "window: " + f.Function + " takes no column, got '" + f.Column + "'");
+      p.name = f.Function;
+    } else {
+      if (f.Column.empty()) return Status::Make(StatusCode::Invalid, "window: " + f.Function + " needs a column ('" + f.Function + ":<column>')");
+      p.column = column(f.Column);
+      if (p.column < 0) return Status::Make(StatusCode::KeyError, "window: unknown column '" + f.Column + "' of function '" + f.Function + "'");
+      const ArrayData& a = *batch.chunks[p.column];
+      if (!IsNumeric(a.type->id) || (p.kind == 10 + AH_WINDOW_SUM && !a.logical.empty())) return no_kernel(f.Function + " of column '" + f.Column + "'", a);
+      p.name = f.Column + "_" + f.Function;
+    }
+    for (auto& q : plan)
+      if (q.name == p.name) return Status::Make(StatusCode::Invalid, "window: two output columns named '" + p.name + "'");
+    plan.push_back(p);
+  }
+  // 1. partition ids   2. the order   3. the flags
+  BufferPtr ids, first_rows, order_buf, flags_buf;
+  if (n > 0) {
+    if (!pkeys.empty()) {
+      int64_t ng = 0;
+      AHC_RETURN_NOT_OK(s->Allocate(n * 4, &ids, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->Allocate((n + 1) * 8, &first_rows, /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_group_ids(s->ctx(), (int)pkeys.size(), pkeys.data(), n, (int32_t*)ids->dptr, (int64_t*)first_rows->dptr, &ng)));
+      first_rows.reset();
+    }
+    std::vector<Datum> cols;
+    for (auto& c : batch.chunks) cols.push_back(Datum::Of(c));
+    AHC_RETURN_NOT_OK(WindowOrderAndFlags(s, "window", cols, okeys, ids, n, &order_buf, &flags_buf));
+  } else {   // nothing runs, but a key the sort would refuse is refused all the same
+    for (auto& k : okeys) {
+      const ArrayData& a = *batch.chunks[k.ColumnIndex];
+      const Type id = a.type->id;
+      if (!(IsInteger(id) || IsFloating(id) || IsBaseBinary(id) || IsFixedWidthBinary(id)))
+        return Status::Make(StatusCode::NotImplemented, std::string("sorting not supported for type ") + a.type->name);
+    }
+  }
+  const uint8_t* flags = flags_buf ? (const uint8_t*)flags_buf->dptr : nullptr;
+  const uint64_t* order = order_buf ? (const uint64_t*)order_buf->dptr : nullptr;
+  // 4. one call per function   5. the validity of the running aggregates
+  const int64_t room = n > 0 ? n : 1;
+  std::vector<std::string> names;
+  std::vector<ArrayDataPtr> cols_out;
+  for (auto& p : plan) {
+    auto col = std::make_shared<ArrayData>();
+    col->length = n;
+    col->null_count = 0;
+    if (p.kind < 10) {
+      col->type = GetDataType(Type::UINT64);
+      AHC_RETURN_NOT_OK(s->Allocate(room * 8, &col->buffers[1], /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_window_rank(s->ctx(), p.kind, flags, order, n, (uint64_t*)col->buffers[1]->dptr)));
+    } else {
+      const int op = p.kind - 10;
+      const ArrayData& a = *batch.chunks[p.column];
+      const Type id = a.type->id;
+      const int width = a.type->bit_width / 8;
+      const uint8_t* vvalid = a.buffers[0] && a.null_count != 0 ? (const uint8_t*)a.buffers[0]->dptr : nullptr;
+      const uint8_t* vals = a.buffers[1] ? (const uint8_t*)a.buffers[1]->dptr + a.offset * width : nullptr;
+      int out_width = width;
+      if (op == AH_WINDOW_SUM) {
+        col->type = GetDataType(IsFloating(id) ? Type::FLOAT64 : IsSignedInteger(id) ? Type::INT64 : Type::UINT64);
+        out_width = 8;
+      } else if (op == AH_WINDOW_COUNT) {
+        col->type = GetDataType(Type::INT64);
+        out_width = 8;
+      } else {
+        col->type = a.type;
+        col->logical = a.logical;
+      }
+      AHC_RETURN_NOT_OK(s->Allocate(room * out_width, &col->buffers[1], /*zero_all=*/false));
+      AHC_RETURN_NOT_OK(s->FromStatus(ah_window_scan(s->ctx(), op, (int)id, vals, vvalid, a.offset, flags, order, n, col->buffers[1]->dptr)));
+      if (vvalid && op != AH_WINDOW_COUNT && n > 0) {
+        AHC_RETURN_NOT_OK(s->Allocate((n + 7) / 8, &col->buffers[0], /*zero_all=*/false));
+        AHC_RETURN_NOT_OK(s->FromStatus(ah_copy_bitmap(s->ctx(), vvalid, a.offset, n, (uint8_t*)col->buffers[0]->dptr, 0, 0)));
+        col->null_count = a.null_count;
+        if (col->null_count < 0) {
+          ArraySpan span;
+          span.type = GetDataType(Type::BOOL);
+          span.len = n;
+          span.offset = 0;
+          span.buffers[0].WrapBuffer(col->buffers[0]);
+          AHC_RETURN_NOT_OK(span.UpdateNullCount(s, &col->null_count));
+        }
+      }
+    }
+    names.push_back(p.name);
+    cols_out.push_back(col);
+  }
+  *out = Datum::OfRecord(std::move(names), std::move(cols_out), n);
+  return Status::OK();
+}
+
+Status RankImpl(ExecCtx* ctx, const FunctionOptions* o, const std::vector<Datum>& args_in, Datum* out) {
+  const RankOptions* opts = dynamic_cast<const RankOptions*>(o);
+  if (!opts || opts->Keys.empty()) return Status::Make(StatusCode::Invalid, "rank: must provide at least one sort key");
+  const std::string& tb = opts->Tiebreaker;
+  int kind;
+  if (tb.empty() || tb == "min") kind = AH_WINDOW_RANK;
+  else if (tb == "first") kind = AH_WINDOW_ROW_NUMBER;
+  else if (tb == "dense") kind = AH_WINDOW_DENSE_RANK;
+  else if (tb == "max") return Status::Make(StatusCode::NotImplemented, "rank: tiebreaker=max is not implemented (min, first or dense)");
+  else return Status::Make(StatusCode::Invalid, "rank: unknown tiebreaker '" + tb + "' (min, first or dense)");
+  Session* s = ctx->session;
+  // the arguments as the sort flattens them, so that a chunked column is concatenated once
+  std::vector<Datum> flat;
+  std::vector<ah_sort_key> checked;
+  int64_t n = 0;
+  AHC_RETURN_NOT_OK(PrepareSortKeys(s, "rank", opts->Keys, args_in, &flat, &checked, &n));
+  if (n > kWindowMaxRows) return Status::Make(StatusCode::Invalid, "rank: " + std::to_string(n) + " rows, more than 2^30");
+  std::vector<SortKey> keys = opts->Keys;
+  if (flat.size() == 1) { keys.resize(1); keys[0].ColumnIndex = 0; }
+  std::shared_ptr<ArrayData> res;
+  AHC_RETURN_NOT_OK(AllocateIndices(s, n, &res));
+  if (n > 0) {
+    BufferPtr order_buf, flags_buf;
+    AHC_RETURN_NOT_OK(WindowOrderAndFlags(s, "rank", flat, keys, nullptr, n, &order_buf, &flags_buf));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_window_rank(s->ctx(), kind, (const uint8_t*)flags_buf->dptr, (const uint64_t*)order_buf->dptr, n,
+                                                   (uint64_t*)res->buffers[1]->dptr)));
+  }
+  *out = Datum::Of(res);
+  return Status::OK();
+}
+
+}  // namespace
+
+void RegisterWindow(FunctionRegistry* reg) {
+  reg->AddFunction(std::make_shared<MetaFunction>("window", Arity{1, false}, nullptr, WindowImpl), false);
+  // Arity: one array, or the columns of a record batch as separate arguments, as sort_indices
+  reg->AddFunction(std::make_shared<MetaFunction>("rank", Arity{1, true}, nullptr, RankImpl), false);
+}
+
 }  // namespace compute
 }  // namespace arrowhip

@@ -516,6 +516,53 @@ func (x *Context) SelectK(keys []SortColumn, n, k int64, route SelectKRoute, out
 	return x.err(C.ah_select_k(x.c, C.int(len(keys)), (*C.ah_sort_key)(tbl), C.int64_t(n), C.int64_t(k), C.int(route), (*C.uint64_t)(outIndices)))
 }
 
+// ---- window functions: ranks and running aggregates over the partitions of a sort order ---------------------------------------
+// The caller brings dense partition ids (GroupIds) and the order SortIndicesKeys wrote for (partition id, order keys); the three
+// calls are enqueued on the compute stream and do not synchronise.  order nil: the identity.
+
+// WindowRankKind selects what WindowRank writes.
+type WindowRankKind int
+
+const (
+	WindowRowNumber WindowRankKind = C.AH_WINDOW_ROW_NUMBER
+	WindowRank      WindowRankKind = C.AH_WINDOW_RANK
+	WindowDenseRank WindowRankKind = C.AH_WINDOW_DENSE_RANK
+)
+
+// WindowScanOp selects the running aggregate of WindowScan.
+type WindowScanOp int
+
+const (
+	WindowSum   WindowScanOp = C.AH_WINDOW_SUM
+	WindowMin   WindowScanOp = C.AH_WINDOW_MIN
+	WindowMax   WindowScanOp = C.AH_WINDOW_MAX
+	WindowCount WindowScanOp = C.AH_WINDOW_COUNT
+)
+
+// WindowFlags writes one byte per sorted position p (row order[p]): bit 0 a partition starts there (partIds: int32 by row, nil =
+// one partition), bit 1 a peer group starts there (the rows at p-1 and p do not tie on every key).  No keys: every row is its own
+// peer group.
+func (x *Context) WindowFlags(partIds unsafe.Pointer, keys []SortColumn, order unsafe.Pointer, n int64, outFlags unsafe.Pointer) error {
+	var tbl unsafe.Pointer
+	if len(keys) > 0 {
+		tbl = sortKeyTable(keys)
+		defer C.free(tbl)
+	}
+	return x.err(C.ah_window_flags(x.c, (*C.int32_t)(partIds), C.int(len(keys)), (*C.ah_sort_key)(tbl), (*C.uint64_t)(order), C.int64_t(n), (*C.uint8_t)(outFlags)))
+}
+
+// WindowRank writes out[order[p]] (uint64, 1-based) = the row number, rank or dense rank at sorted position p.
+func (x *Context) WindowRank(kind WindowRankKind, flags, order unsafe.Pointer, n int64, out unsafe.Pointer) error {
+	return x.err(C.ah_window_rank(x.c, C.int(kind), (*C.uint8_t)(flags), (*C.uint64_t)(order), C.int64_t(n), (*C.uint64_t)(out)))
+}
+
+// WindowScan writes outValues[order[p]] = the running aggregate of the column over the row's partition up to sorted position p.
+// Sums are 8 bytes per row (Int64, Uint64 or Float64), minima and maxima have the input type, counts are Int64.  A null row gets
+// payload 0; the output's validity is the input's, which the caller copies (CopyBitmap).
+func (x *Context) WindowScan(op WindowScanOp, typeID arrow.Type, values, valid unsafe.Pointer, off int64, flags, order unsafe.Pointer, n int64, outValues unsafe.Pointer) error {
+	return x.err(C.ah_window_scan(x.c, C.int(op), C.int(typeID), values, (*C.uint8_t)(valid), C.int64_t(off), (*C.uint8_t)(flags), (*C.uint64_t)(order), C.int64_t(n), outValues))
+}
+
 // ---- ingest slots: the building blocks of Ingest for callers that run their own kernels on the chunks ------------------------
 
 func (i *Ingest) Depth() int      { return int(C.ah_ingest_depth(i.g)) }

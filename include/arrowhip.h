@@ -952,6 +952,51 @@ int ah_sort_indices_keys(ah_ctx* ctx, int nkeys, const ah_sort_key* keys, int64_
 int ah_select_k(ah_ctx* ctx, int nkeys, const ah_sort_key* keys, int64_t n, int64_t k, int route, uint64_t* out_indices);
 /* route: AH_SELECT_AUTO 0 | AH_SELECT_RADIX 1 | AH_SELECT_SORT 2.  out_indices holds min(k, n) entries.  Synchronises. */
 
+/* ---- window functions: ranks and running aggregates over the partitions of a sort order (NEW — no reference analogue: arrow-go
+ * has no window operator; definition in DESIGN.md §3.7.3) ---------------------------------------------------------------------
+ * The caller brings dense partition ids (ah_group_ids) and `order`, the n uint64 row numbers ah_sort_indices_keys wrote for the
+ * keys (partition id ascending, then the ORDER BY keys): sorted position p holds row order[p].  order == NULL is the identity
+ * (position p holds row p).  PRECONDITION: `order` is a permutation of [0, n); an entry outside [0, n) is never used as an
+ * address (its position reads and writes nothing), any other violation gives unspecified values inside the outputs.  n <= 2^30
+ * (AH_EINVALID above).  n == 0: nothing touched.  All three calls are enqueued on the compute stream and do not synchronise;
+ * temporaries: O(n / 2048) words of the scratch arena.
+ *
+ * ah_window_flags: out_flags[p] (n bytes, one per SORTED position): bit 0 = a partition starts at p, bit 1 = a peer group starts
+ * at p; position 0 starts both, and a partition start is a peer start.  p > 0 compares row order[p - 1] with row order[p]:
+ * bit 0 iff part_ids differs (part_ids: n int32 indexed by ROW, or NULL = one partition); bit 1 iff bit 0, or the rows do not
+ * tie on some key.  Rows tie on a key as the comparator of ah_sort_indices_keys ties them: both null; both NaN (any payload);
+ * equal values with -0.0 = +0.0; binary and fixed-size binary values of equal length and equal bytes; decimals of equal value
+ * (= equal bytes).  order_keys: 0 <= nkeys <= 8 entries of host memory laid out as for ah_sort_indices_keys (row i = element
+ * off + i of every buffer); descending and nulls_at_start are not looked at.  nkeys == 0: every row is its own peer group. */
+int ah_window_flags(ah_ctx* ctx, const int32_t* part_ids, int nkeys, const ah_sort_key* order_keys, const uint64_t* order, int64_t n,
+                    uint8_t* out_flags);
+/* ah_window_rank: out[order[p]] (n uint64, 1-based, every row written once) = AH_WINDOW_ROW_NUMBER: p - s + 1, s the last
+ * partition start at or before p; AH_WINDOW_RANK: g - s + 1, g the last peer-group start at or before p (the row number of the
+ * first row of p's peer group); AH_WINDOW_DENSE_RANK: the number of peer-group starts in [s, p].  `flags`: what ah_window_flags
+ * wrote for the same order. */
+#define AH_WINDOW_ROW_NUMBER 0
+#define AH_WINDOW_RANK 1
+#define AH_WINDOW_DENSE_RANK 2
+int ah_window_rank(ah_ctx* ctx, int kind, const uint8_t* flags, const uint64_t* order, int64_t n, uint64_t* out);
+/* ah_window_scan: the running aggregate of a value column over ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW of the row's
+ * partition in the given order — a segmented inclusive scan over the sorted positions restarting where bit 0 of `flags` is set,
+ * the column gathered through `order` and the result scattered back: out_values[order[p]], one store per row, EVERY row written.
+ * `values` points at row 0 of the call (element-aligned), `valid` (nullable) is read at bit off + row; `type`: any of the ten
+ * numeric ids.  A row whose value is null gets payload 0 and does not contribute; the output's validity is the input's, which
+ * the caller copies (ah_copy_bitmap): no validity bit is written here.
+ *   AH_WINDOW_SUM    out: 8 bytes per row — wrapping Int64 (signed types), wrapping UInt64 (unsigned types), Float64 (floats, added
+ *                    in double in a tree that depends on n and the flags only: the same bytes on every run; no float atomics).
+ *   AH_WINDOW_MIN / AH_WINDOW_MAX   out: the input type.  The rules of ah_group_min_max_typed on the prefix: NaNs are ignored
+ *                    unless every valid value so far is a NaN, then the canonical quiet NaN; -0 < +0.
+ *   AH_WINDOW_COUNT  out: int64, the valid values so far (valid == NULL: the row number); never null; `type` and `values` are
+ *                    not looked at. */
+#define AH_WINDOW_SUM 0
+#define AH_WINDOW_MIN 1
+#define AH_WINDOW_MAX 2
+#define AH_WINDOW_COUNT 3
+int ah_window_scan(ah_ctx* ctx, int op, int type, const void* values, const uint8_t* valid, int64_t off, const uint8_t* flags,
+                   const uint64_t* order, int64_t n, void* out_values);
+
 /* Boolean VALUES (booleanTakeImpl, kernels/vector_selection.go:990-1074): data and validity are bitmaps
  * indexed at voff + idx; a null output keeps data bit 0.  Output bitmaps start at bit 0.  Filter of a
  * boolean column = ah_filter_to_indices + this (the reference's own boolFilterWriter never advances its
