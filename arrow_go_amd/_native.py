@@ -168,6 +168,12 @@ _SIGS = {
     "ah_window_flags": [_vp, _vp, _int, _vp, _vp, _i64, _vp],
     "ah_window_rank": [_vp, _int, _vp, _vp, _i64, _vp],
     "ah_window_scan": [_vp, _int, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
+    "ah_if_else": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "ah_if_else_boolean": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "ah_if_else_binary_offsets": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp, _pi64],
+    "ah_if_else_binary_data": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp],
+    "ah_fill_null_indices": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _pi64],
+    "ah_fill_null_directed": [_vp, _int, _vp, _vp, _i64, _i64, _int, _vp, _vp, _pi64],
     "ah_take_binary_offsets": [_vp, _int, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _i64, _i64, _int, _vp, _vp, _pi64, _pi64, _pi64],
     "ah_take_binary_data": [_vp, _int, _vp, _vp, _i64, _int, _vp, _i64, _vp, _vp],
     "ah_take_boolean": [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _i64, _i64, _int, _vp, _vp, _pi64, _pi64],

@@ -743,6 +743,39 @@ class Session:
         nulls, NaNs with NaNs, -0.0 with +0.0.  values: an array, a chunked array or a record batch with sort_keys."""
         return self.call_function("rank", [values], rank_options(sort_keys, order, null_placement, tiebreaker), keep_on_device=keep_on_device)
 
+    # -- conditionals (Arrow C++'s semantics; every argument a pyarrow Array, ChunkedArray, Scalar or DeviceArray)
+    def if_else(self, cond, left, right, keep_on_device: bool = False):
+        """call_function("if_else", [cond, left, right]): row i is null where cond[i] is null, otherwise left[i] (cond true) or
+        right[i] with that side's validity.  cond is Boolean; left and right have one type — numeric sides of different types are
+        promoted by the rule `add` uses, every other pairing must match exactly.  Any argument may be a scalar; a scalar cond is
+        decided on the host: one side is returned (a scalar side broadcast), an all-null column for a null cond.  Fixed-width sides:
+        one streaming pass without a host synchronisation.  Under a null slot the payload is zero bytes, a null Boolean's data bit
+        is 0, a null string has length 0."""
+        return self.call_function("if_else", [cond, left, right], keep_on_device=keep_on_device)
+
+    def coalesce(self, *values, keep_on_device: bool = False):
+        """call_function("coalesce", values): per row the first valid value among the arguments, null if there is none.  One value
+        type (numeric arguments are promoted as for if_else).  A right fold of if_else whose condition is the left argument's
+        validity bitmap: k arguments cost k - 1 passes over the column, an argument without nulls ends the fold and is returned
+        as it is."""
+        return self.call_function("coalesce", list(values), keep_on_device=keep_on_device)
+
+    def fill_null(self, values, fill_value, keep_on_device: bool = False):
+        """call_function("fill_null", [values, fill_value]) = coalesce(values, fill_value): the nulls of `values` replaced by
+        fill_value (a scalar or an array of the same length)."""
+        return self.call_function("fill_null", [values, fill_value], keep_on_device=keep_on_device)
+
+    def fill_null_forward(self, values, keep_on_device: bool = False):
+        """call_function("fill_null_forward", [values]): a null row takes the nearest valid row before it and stays null when there
+        is none (leading nulls).  Over a chunked array the carry crosses the chunk borders; the result is chunked like the input.
+        A column without nulls is returned as it is.  At most 2^32 - 1 rows."""
+        return self.call_function("fill_null_forward", [values], keep_on_device=keep_on_device)
+
+    def fill_null_backward(self, values, keep_on_device: bool = False):
+        """call_function("fill_null_backward", [values]): a null row takes the nearest valid row after it and stays null when there
+        is none (trailing nulls); otherwise as fill_null_forward."""
+        return self.call_function("fill_null_backward", [values], keep_on_device=keep_on_device)
+
     def hash_join(self, left, right, keys, right_keys=None, join_type: str = "inner", keep_on_device: bool = False):
         """call_function("hash_join", [left, right], "left_keys=…;right_keys=…;type=…"): the two record batches joined on their key
         columns (right_keys None: the same names as `keys`).  join_type: inner, left_outer, left_semi or left_anti.  Rows: the left rows

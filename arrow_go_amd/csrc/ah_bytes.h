@@ -134,6 +134,33 @@ __device__ __forceinline__ void wave_compare(unsigned long long need, const uint
   }
 }
 
+// The row copy of the var-length outputs (the Take of ah_varlen.hip, the if_else of ah_conditional.hip): a wave owns 64 output rows,
+// each lane brings its row's source, destination and length (len ≤ 0: nothing to copy).  The rows that have bytes are compacted
+// into `s_rows` (the wave's own 64 entries of LDS) in row order; four 16-lane groups then copy four rows at a time, 4 (unaligned)
+// bytes per lane.  Called with all 64 lanes active; s_rows may be reused as soon as it returns.
+struct CopyRow { const uint8_t* src; uint8_t* dst; long long len; };
+struct __attribute__((packed)) U32u { unsigned v; };  // 4 bytes at any address (gfx950 global memory runs in unaligned-access mode)
+__device__ __forceinline__ void wave_copy_rows(CopyRow* s_rows, const uint8_t* src, uint8_t* dst, long long len) {
+  const int lane = ah_lane();
+  const int group = lane >> 4, sub = lane & 15;
+  const unsigned long long todo = __ballot(len > 0);
+  const int count = __popcll(todo);
+  if (len > 0) s_rows[__popcll(todo & (lane == 0 ? 0ull : (~0ull >> (64 - lane))))] = CopyRow{src, dst, len};
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // LDS ops of a wave are in order; keep the compiler from reordering
+  __builtin_amdgcn_wave_barrier();
+  for (int k = group; k < count; k += 4) {
+    volatile const CopyRow* rp = &s_rows[k];  // written by other lanes of this wave
+    CopyRow r;
+    r.src = rp->src; r.dst = rp->dst; r.len = rp->len;
+    long long b = (long long)sub * 4;
+    for (; b + 4 <= r.len; b += 64) ((U32u*)(r.dst + b))->v = ((const U32u*)(r.src + b))->v;
+    const long long tail = r.len & ~3ll;  // the last len mod 4 bytes
+    if (sub < (int)(r.len - tail)) r.dst[tail + sub] = r.src[tail + sub];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the next chunk overwrites s_rows
+  __builtin_amdgcn_wave_barrier();
+}
+
 // The offsets buffer of a var-length output from the inclusive scan of its rows' lengths (the Take of ah_varlen.hip, the formatted
 // casts of ah_cast_string.hip): out_offsets[0] = 0, out_offsets[i + 1] = incl[i]; int32 offsets: flag an overflow
 template <typename OffT, int BLOCK>

@@ -45,16 +45,12 @@ __global__ __launch_bounds__(kBlock) void lens_kernel(const OffT* __restrict__ o
   });
 }
 
-struct __attribute__((packed)) U32u { unsigned v; };  // 4 bytes at any address (gfx950 global memory runs in unaligned-access mode)
-
 template <typename OffT, typename IdxT>
 __global__ __launch_bounds__(kBlock) void copy_kernel(const OffT* __restrict__ offsets, const uint8_t* __restrict__ data, int64_t voff,
                                                        const IdxT* __restrict__ idx, int64_t n, const OffT* __restrict__ out_offsets,
                                                        uint8_t* __restrict__ out_data) {
-  struct Row { long long src, dst, len; };
-  __shared__ Row s_rows[kBlock / 64][64];
+  __shared__ CopyRow s_rows[kBlock / 64][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int group = lane >> 4, sub = lane & 15;  // four 16-lane groups copy four rows at a time, 4 bytes per lane
   const int64_t nchunks = (n + 63) >> 6;
   const int64_t wave_stride = (int64_t)gridDim.x * (kBlock / 64);
   for (int64_t c = (int64_t)blockIdx.x * (kBlock / 64) + wave; c < nchunks; c += wave_stride) {
@@ -65,25 +61,7 @@ __global__ __launch_bounds__(kBlock) void copy_kernel(const OffT* __restrict__ o
       len = (long long)out_offsets[i + 1] - dst;
       if (len > 0) src = (long long)offsets[voff + (int64_t)idx[i]];  // len > 0 ⇒ a valid, in-bounds slot (IdxT is unsigned)
     }
-    // rows that have bytes, compacted into LDS in row order
-    const unsigned long long todo = __ballot(len > 0);
-    const int count = __popcll(todo);
-    if (len > 0) s_rows[wave][__popcll(todo & (lane == 0 ? 0ull : (~0ull >> (64 - lane))))] = Row{src, dst, len};
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // LDS ops of a wave are in order; keep the compiler from reordering
-    __builtin_amdgcn_wave_barrier();
-    for (int k = group; k < count; k += 4) {
-      volatile const Row* rp = &s_rows[wave][k];  // written by other lanes of this wave
-      Row r;
-      r.src = rp->src; r.dst = rp->dst; r.len = rp->len;
-      const uint8_t* sp = data + r.src;
-      uint8_t* dp = out_data + r.dst;
-      long long b = (long long)sub * 4;
-      for (; b + 4 <= r.len; b += 64) ((U32u*)(dp + b))->v = ((const U32u*)(sp + b))->v;
-      const long long tail = r.len & ~3ll;  // the last len mod 4 bytes
-      if (sub < (int)(r.len - tail)) dp[tail + sub] = sp[tail + sub];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the next chunk overwrites s_rows
-    __builtin_amdgcn_wave_barrier();
+    wave_copy_rows(s_rows[wave], data + src, out_data + dst, len);   // (ah_bytes.h)
   }
 }
 

@@ -259,6 +259,16 @@ class _CmpOperand(C.Structure):  # ah_cmp_operand (arrowhip.h)
                 ("broadcast", C.c_int)]
 
 
+class _CondSide(C.Structure):  # ah_cond_side (arrowhip.h)
+    _fields_ = [("offset_width", C.c_int), ("byte_width", C.c_int), ("offsets", C.c_void_p), ("data", C.c_void_p), ("valid", C.c_void_p),
+                ("off", C.c_int64), ("broadcast", C.c_int)]
+
+
+def _cond_side(side) -> _CondSide:
+    ow, bw, offsets, data, valid, off, broadcast = side
+    return _CondSide(ow, bw, _ptr(offsets), _ptr(data), _ptr(valid), off, int(broadcast))
+
+
 class Context:
     """ah_ctx: one GPU, a compute stream and a copy stream."""
 
@@ -687,6 +697,55 @@ class Context:
         """out_values[order[p]] = the running op (0 sum, 1 min, 2 max, 3 count) of the column over its partition up to sorted
         position p; a null row gets payload 0 and the caller copies the validity (ah_window_scan)"""
         check(self.handle, lib.ah_window_scan(self.handle, op, type_id, _ptr(values), _ptr(valid), off, _ptr(flags), _ptr(order), n, _ptr(out_values)))
+
+    # ---- conditionals (ah_conditional.hip).  A side: (offset_width, byte_width, offsets, data, valid, off, broadcast) — offset_width 0
+    # for fixed slots of byte_width bytes and for Boolean sides (data a bitmap), 4 / 8 for var-length sides; broadcast 1: a scalar as a
+    # one-row device column, every row reads element off.  cond_data / cond_valid: bitmaps read at bit cond_off + row.
+    def if_else(self, cond_data, cond_valid, cond_off: int, left, right, n: int, out_values, out_valid) -> None:
+        """fixed-width sides: row i = left[i] where cond[i] else right[i], null where cond[i] or the chosen side is (payload 0);
+        no synchronisation (ah_if_else)"""
+        lo, ro = _cond_side(left), _cond_side(right)
+        check(self.handle, lib.ah_if_else(self.handle, _ptr(cond_data), _ptr(cond_valid), cond_off, C.byref(lo), C.byref(ro), n, _ptr(out_values),
+                                          _ptr(out_valid)))
+
+    def if_else_boolean(self, cond_data, cond_valid, cond_off: int, left, right, n: int, out_data, out_valid) -> None:
+        """Boolean sides: data and validity bitmaps from bit 0 (ah_if_else_boolean)"""
+        lo, ro = _cond_side(left), _cond_side(right)
+        check(self.handle, lib.ah_if_else_boolean(self.handle, _ptr(cond_data), _ptr(cond_valid), cond_off, C.byref(lo), C.byref(ro), n,
+                                                  _ptr(out_data), _ptr(out_valid)))
+
+    def if_else_binary_offsets(self, cond_data, cond_valid, cond_off: int, left, right, n: int, out_offset_width: int, out_offsets,
+                               out_valid) -> int:
+        """var-length sides, first call: out_offsets[0 … n] and the validity → the number of data bytes (ah_if_else_binary_offsets)"""
+        lo, ro = _cond_side(left), _cond_side(right)
+        total = C.c_int64()
+        check(self.handle, lib.ah_if_else_binary_offsets(self.handle, _ptr(cond_data), _ptr(cond_valid), cond_off, C.byref(lo), C.byref(ro), n,
+                                                         out_offset_width, _ptr(out_offsets), _ptr(out_valid), C.byref(total)))
+        return total.value
+
+    def if_else_binary_data(self, cond_data, cond_valid, cond_off: int, left, right, n: int, out_offset_width: int, out_offsets,
+                            out_data) -> None:
+        """var-length sides, second call: the bytes (ah_if_else_binary_data)"""
+        lo, ro = _cond_side(left), _cond_side(right)
+        check(self.handle, lib.ah_if_else_binary_data(self.handle, _ptr(cond_data), _ptr(cond_valid), cond_off, C.byref(lo), C.byref(ro), n,
+                                                      out_offset_width, _ptr(out_offsets), _ptr(out_data)))
+
+    def fill_null_indices(self, valid, off: int, n: int, direction: int, out_idx, out_idx_valid, want_null_count: bool = True):
+        """out_idx[i] (uint32) = the nearest valid row at or before (direction 0) / at or after (1) row i, out_idx_valid its bit: what
+        the Take family reads as (idx, ivalid).  → the null count, or None without the synchronisation (ah_fill_null_indices)"""
+        nulls = C.c_int64()
+        check(self.handle, lib.ah_fill_null_indices(self.handle, _ptr(valid), off, n, direction, _ptr(out_idx), _ptr(out_idx_valid),
+                                                    C.byref(nulls) if want_null_count else None))
+        return nulls.value if want_null_count else None
+
+    def fill_null_directed(self, byte_width: int, values, valid, off: int, n: int, direction: int, out_values, out_valid,
+                           want_null_count: bool = True):
+        """the same walk with the gather fused in, for values of 1 / 2 / 4 / 8 / 16 / 32 bytes: out_values[i] = values[off + source]
+        (ah_fill_null_directed)"""
+        nulls = C.c_int64()
+        check(self.handle, lib.ah_fill_null_directed(self.handle, byte_width, _ptr(values), _ptr(valid), off, n, direction, _ptr(out_values),
+                                                     _ptr(out_valid), C.byref(nulls) if want_null_count else None))
+        return nulls.value if want_null_count else None
 
     def take_boolean(self, data, vvalid, voff: int, nvalues: int, idx_byte_width: int, idx_signed: bool, idx, ivalid, ioff: int, nidx: int,
                      out_data, out_valid) -> int:

@@ -474,6 +474,9 @@ class ScalarFunction : public Function {  // functions.go:239-290
   // compareFunction.DispatchBest's other two steps (scalar_compare.go:37-63): castBinaryDecimalArgs(decPromoteAdd) when an
   // argument is a decimal (utils.go:261-326) and commonBinary (utils.go:401-436) when no numeric type is common
   bool promote_binary_decimal = false;
+  // the conditionals (if_else, coalesce, fill_null): when no kernel matches exactly, the arguments from this position on — the
+  // values, not the condition — are promoted to commonNumeric by the rule `add` uses; −1: no such step
+  int promote_from = -1;
   Status DispatchBest(std::vector<const DataType*>* types, const exec::ScalarKernel** out) const;
  private:
   std::vector<exec::ScalarKernel> kernels_;
@@ -554,6 +557,7 @@ void RegisterFusedExtensions(FunctionRegistry* reg);
 void RegisterGroupBy(FunctionRegistry* reg);
 void RegisterHashJoin(FunctionRegistry* reg);
 void RegisterWindow(FunctionRegistry* reg);
+void RegisterConditional(FunctionRegistry* reg);
 
 // ---- compute.Expression (arrow/compute/expression.go:59-78,596-620) and its executor
 // (arrow/compute/exprs/exec.go:440-700 ExecuteScalarExpression / executeScalarBatch) --------

@@ -313,9 +313,16 @@ std::vector<exec::ScalarKernel*> ScalarFunction::Kernels() {
   for (auto& k : kernels_) out.push_back(&k);
   return out;
 }
+// a signature of a varargs function: its last input type stands for every further argument (kernel.go:330-452, IsVarArgs)
+static bool MatchesVarArgs(const exec::KernelSignature& sig, const std::vector<const DataType*>& types) {
+  if (sig.in_types.empty() || types.size() < sig.in_types.size()) return false;
+  for (size_t i = 0; i < types.size(); i++)
+    if (!types[i] || types[i]->id != sig.in_types[std::min(i, sig.in_types.size() - 1)]) return false;
+  return true;
+}
 Status ScalarFunction::DispatchExact(const std::vector<const DataType*>& types, const exec::ScalarKernel** out) const {
   for (auto& k : kernels_)  // first matching signature wins (functions.go:209-213)
-    if (k.sig.MatchesInputs(types)) { *out = &k; return Status::OK(); }
+    if (arity_.IsVarArgs ? MatchesVarArgs(k.sig, types) : k.sig.MatchesInputs(types)) { *out = &k; return Status::OK(); }
   for (auto& k : parametric_kernels_)
     if (k.sig.MatchesInputs(types)) { *out = &k; return Status::OK(); }
   return Status::Make(StatusCode::NotImplemented, "function '" + name_ + "' has no kernel matching input types " + TypesToString(types));
@@ -588,6 +595,18 @@ Status ScalarFunction::DispatchBest(std::vector<const DataType*>* types, const e
     Status st2 = DispatchExact(promoted, out);
     if (st2.ok()) { *types = promoted; return st2; }
   }
+  if (!st.ok() && promote_from >= 0) {   // the conditionals: the value arguments go to their common numeric type, the condition stays
+    if ((int)types->size() > promote_from) {
+      const std::vector<const DataType*> values(types->begin() + promote_from, types->end());
+      if (const DataType* common = CommonNumeric(values)) {
+        std::vector<const DataType*> promoted(*types);
+        for (size_t i = (size_t)promote_from; i < promoted.size(); i++) promoted[i] = common;
+        Status st2 = DispatchExact(promoted, out);
+        if (st2.ok()) { *types = promoted; return st2; }
+      }
+    }
+    return st;
+  }
   if (st.ok() || !promote_numeric || types->size() != 2) return st;
   if (const DataType* common = CommonNumeric(*types)) {
     std::vector<const DataType*> promoted(types->size(), common);
@@ -782,6 +801,7 @@ FunctionRegistry* GetFunctionRegistry() {
     RegisterGroupBy(r);
     RegisterHashJoin(r);
     RegisterWindow(r);
+    RegisterConditional(r);
     return r;
   }();
   return reg;

@@ -2715,5 +2715,289 @@ void RegisterWindow(FunctionRegistry* reg) {
   reg->AddFunction(std::make_shared<MetaFunction>("rank", Arity{1, true}, nullptr, RankImpl), false);
 }
 
+// ---- conditionals: if_else, coalesce, fill_null, fill_null_forward, fill_null_backward -------------------------------
+// No reference analogue (arrow-go registers none of them); the semantics are Arrow C++'s.  if_else: row i is null where cond[i] is null,
+// otherwise left[i] or right[i] with that side's validity.  coalesce: the first valid value of the row.  The directed fills: a null
+// row takes the nearest valid row before / after it.  Any argument may be an array or a scalar; a scalar is a one-row device column
+// every row reads (ah_cond_side.broadcast).
+namespace {
+
+constexpr int kForward = 0, kBackward = 1;
+
+// the value types: every type the take of this layer accepts, dictionaries left out
+std::vector<Type> ConditionalValueTypes() {
+  std::vector<Type> t(std::begin(kNumericTypes), std::end(kNumericTypes));
+  t.push_back(Type::BOOL);
+  t.insert(t.end(), std::begin(kBinaryTypes), std::end(kBinaryTypes));
+  for (Type f : {Type::FIXED_SIZE_BINARY, Type::DECIMAL128, Type::DECIMAL256}) t.push_back(f);
+  return t;
+}
+
+// the bits a call reads its condition from
+struct CondBits {
+  const uint8_t* data = nullptr;
+  const uint8_t* valid = nullptr;
+  int64_t off = 0;
+};
+
+// one side as ah_if_else takes it, with the array that owns its buffers
+struct CondSide {
+  ah_cond_side s;
+  ArrayDataPtr keep;
+};
+Status SideOf(Session* s, const Datum& d, CondSide* out) {
+  const bool broadcast = d.kind == DatumKind::Scalar;
+  if (broadcast) AHC_RETURN_NOT_OK(ScalarToArray(s, *d.scalar, &out->keep));
+  else out->keep = d.array;
+  const ArrayData& a = *out->keep;
+  auto dptr = [&](int i) -> const void* { return a.buffers[i] ? a.buffers[i]->dptr : nullptr; };
+  out->s = ah_cond_side{};
+  if (IsBaseBinary(a.type->id)) {
+    out->s.offset_width = a.type->bit_width / 8;
+    out->s.offsets = dptr(1);
+    out->s.data = dptr(2);
+  } else {
+    out->s.byte_width = a.type->bit_width / 8;   // (Boolean: 0, the data is a bitmap)
+    out->s.data = dptr(1);
+  }
+  out->s.valid = a.null_count != 0 ? (const uint8_t*)dptr(0) : nullptr;
+  out->s.off = a.offset;
+  out->s.broadcast = broadcast ? 1 : 0;
+  return Status::OK();
+}
+
+// n rows chosen by the condition's bits from two sides of one type.  Fixed-width and Boolean sides: one launch, no synchronisation,
+// the null count left to whoever asks for it; var-length sides: the offsets call brings the byte count home.
+Status IfElseRows(Session* s, const CondBits& c, const Datum& left, const Datum& right, int64_t n, Datum* out) {
+  CondSide l, r;
+  AHC_RETURN_NOT_OK(SideOf(s, left, &l));
+  AHC_RETURN_NOT_OK(SideOf(s, right, &r));
+  const DataType* t = l.keep->type;
+  auto res = std::make_shared<ArrayData>();
+  res->type = t;
+  res->length = n;
+  res->logical = l.keep->logical;
+  const bool nulls = c.valid || l.s.valid || r.s.valid;
+  res->null_count = nulls ? kUnknownNullCount : 0;
+  if (nulls) AHC_RETURN_NOT_OK(s->AllocateBitmap(n, &res->buffers[0]));
+  uint8_t* ov = nulls ? (uint8_t*)res->buffers[0]->dptr : nullptr;
+  if (t->id == Type::BOOL) {
+    AHC_RETURN_NOT_OK(s->AllocateBitmap(n, &res->buffers[1]));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_if_else_boolean(s->ctx(), c.data, c.valid, c.off, &l.s, &r.s, n, (uint8_t*)res->buffers[1]->dptr, ov)));
+  } else if (IsBaseBinary(t->id)) {
+    const int ow = t->bit_width / 8;
+    int64_t total = 0;
+    AHC_RETURN_NOT_OK(s->Allocate((n + 1) * ow, &res->buffers[1]));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_if_else_binary_offsets(s->ctx(), c.data, c.valid, c.off, &l.s, &r.s, n, ow, res->buffers[1]->dptr, ov, &total)));
+    AHC_RETURN_NOT_OK(s->Allocate(total, &res->buffers[2], /*zero_all=*/false));
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_if_else_binary_data(s->ctx(), c.data, c.valid, c.off, &l.s, &r.s, n, ow, res->buffers[1]->dptr, (uint8_t*)res->buffers[2]->dptr)));
+  } else {
+    AHC_RETURN_NOT_OK(s->Allocate(n * (t->bit_width / 8), &res->buffers[1], /*zero_all=*/false));   // every slot is written
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_if_else(s->ctx(), c.data, c.valid, c.off, &l.s, &r.s, n, res->buffers[1]->dptr, ov)));
+  }
+  *out = Datum::Of(res);
+  return Status::OK();
+}
+
+// n null rows of a type: zero payload, zero lengths
+Status AllNullRows(Session* s, const DataType* t, const std::string& logical, int64_t n, Datum* out) {
+  auto res = std::make_shared<ArrayData>();
+  res->type = t;
+  res->length = n;
+  res->null_count = n;
+  res->logical = logical;
+  AHC_RETURN_NOT_OK(s->AllocateBitmap(n, &res->buffers[0]));
+  if (t->id == Type::BOOL) AHC_RETURN_NOT_OK(s->AllocateBitmap(n, &res->buffers[1]));
+  else if (IsBaseBinary(t->id)) {
+    AHC_RETURN_NOT_OK(s->Allocate((n + 1) * (t->bit_width / 8), &res->buffers[1]));
+    AHC_RETURN_NOT_OK(s->Allocate(0, &res->buffers[2]));
+  } else AHC_RETURN_NOT_OK(s->Allocate(n * (t->bit_width / 8), &res->buffers[1]));
+  *out = Datum::Of(res);
+  return Status::OK();
+}
+
+// a scalar as a column of n rows: if_else over a condition of n zero bits with the scalar on both sides
+Status BroadcastRows(Session* s, const Datum& scalar, int64_t n, Datum* out) {
+  BufferPtr zeros;
+  AHC_RETURN_NOT_OK(s->AllocateBitmap(n, &zeros));
+  CondBits c;
+  c.data = (const uint8_t*)zeros->dptr;
+  return IfElseRows(s, c, scalar, scalar, n, out);
+}
+
+std::string ValueTypeText(const DataType* t) { return IsFixedWidthBinary(t->id) ? std::string(t->name) + "[" + t->format + "]" : std::string(t->name); }
+
+// A scalar function of this family: dispatch as every scalar function (DispatchBest with promote_from: the VALUE arguments go to
+// their common numeric type by the rule `add` uses, every other pairing must match exactly), the implicit safe casts, and then the
+// family's own executor — the arguments arrive as arrays or scalars of one value type, chunked columns already concatenated
+// (ExecuteChunked) and re-chunked behind it.
+class ConditionalFunction : public ScalarFunction {
+ public:
+  using Impl = std::function<Status(Session*, const std::vector<Datum>&, int64_t, Datum*)>;   // (session, arguments, rows or −1: all scalars, result)
+  ConditionalFunction(std::string name, Arity arity, int first_value, Impl impl) : ScalarFunction(std::move(name), arity), impl_(std::move(impl)) {
+    promote_from = first_value;
+    for (Type t : ConditionalValueTypes()) {
+      exec::ScalarKernel k;
+      for (int i = 0; i < arity.NArgs; i++) k.sig.in_types.push_back(i < first_value ? Type::BOOL : t);
+      k.sig.out_is_first_input = false;
+      k.sig.out_type = t;
+      k.exec_fn = [](KernelCtx*, const ExecSpan&, ExecResult*) { return Status::Make(StatusCode::NotImplemented, "the conditionals run through their function's executor"); };
+      AddKernel(std::move(k));
+    }
+  }
+  Status Execute(ExecCtx* ctx, const FunctionOptions*, const std::vector<Datum>& args_in, Datum* out) override {
+    AHC_RETURN_NOT_OK(CheckArity(args_in.size()));
+    Session* s = ctx ? ctx->session : nullptr;
+    if (!s) return Status::Make(StatusCode::Invalid, "ExecCtx has no device session");
+    std::vector<Datum> args = args_in;
+    std::vector<const DataType*> types;
+    for (auto& a : args) {
+      if (a.kind != DatumKind::Array && a.kind != DatumKind::Scalar) return Status::Make(StatusCode::NotImplemented, "function '" + name_ + "' takes arrays, chunked arrays and scalars");
+      types.push_back(a.type());
+    }
+    const std::vector<const DataType*> given = types;
+    const exec::ScalarKernel* kernel = nullptr;
+    AHC_RETURN_NOT_OK(DispatchBest(&types, &kernel));
+    for (size_t i = 0; i < args.size(); i++) {   // the implicit casts are SAFE casts (execInternal, exec.go:105-114)
+      if (args[i].type()->id == types[i]->id) continue;
+      Datum casted;
+      AHC_RETURN_NOT_OK(CastDatum(ctx, args[i], CastOptions::Safe(types[i]), &casted));
+      args[i] = casted;
+    }
+    // parametric value types (decimal precision and scale, the width of a fixed-size binary) match exactly too
+    for (size_t i = (size_t)promote_from + 1; i < args.size(); i++)
+      if (args[i].type() != args[promote_from].type() && strcmp(args[i].type()->format, args[promote_from].type()->format) != 0) {
+        std::string text = "(";
+        for (size_t j = 0; j < given.size(); j++) text += std::string(j ? ", " : "") + ValueTypeText(given[j]);
+        return Status::Make(StatusCode::NotImplemented, "function '" + name_ + "' has no kernel matching input types " + text + ")");
+      }
+    int64_t n = -1;   // inferBatchLength (executor.go:352-390)
+    for (auto& a : args) {
+      if (a.kind != DatumKind::Array) continue;
+      if (n < 0) n = a.array->length;
+      else if (n != a.array->length) return Status::Make(StatusCode::Invalid, "array arguments must all be the same length");
+    }
+    return impl_(s, args, n, out);
+  }
+ private:
+  Impl impl_;
+};
+
+Status IfElseImpl(Session* s, const std::vector<Datum>& args, int64_t n, Datum* out) {
+  const Datum& cond = args[0];
+  if (cond.kind == DatumKind::Scalar) {   // decided here: one side is the result
+    const Datum& side = (cond.scalar->value[0] & 1) ? args[1] : args[2];
+    if (n < 0) {   // all scalars: a scalar
+      if (cond.scalar->valid) { *out = side; return Status::OK(); }
+      auto sc = std::make_shared<Scalar>(*args[1].scalar);
+      sc->valid = false;
+      memset(sc->value, 0, sizeof(sc->value));
+      sc->bytes.clear();
+      *out = Datum::Of(sc);
+      return Status::OK();
+    }
+    if (!cond.scalar->valid) {
+      const Datum& any = args[1].kind == DatumKind::Array ? args[1] : args[2];
+      return AllNullRows(s, args[1].type(), any.array->logical, n, out);
+    }
+    if (side.kind == DatumKind::Array) { *out = side; return Status::OK(); }
+    return BroadcastRows(s, side, n, out);
+  }
+  const ArrayData& c = *cond.array;
+  CondBits bits;
+  bits.data = c.buffers[1] ? (const uint8_t*)c.buffers[1]->dptr : nullptr;
+  bits.valid = c.buffers[0] && c.null_count != 0 ? (const uint8_t*)c.buffers[0]->dptr : nullptr;
+  bits.off = c.offset;
+  return IfElseRows(s, bits, args[1], args[2], n, out);
+}
+
+// coalesce(x1 … xk) = if_else(is_valid(x1), x1, coalesce(x2 … xk)): a right fold of if_else whose condition is the left argument's
+// validity bitmap at its offset.  A left argument without nulls is the result as it is, a null scalar leaves the rest.
+Status CoalesceImpl(Session* s, const std::vector<Datum>& args, int64_t n, Datum* out) {
+  Datum acc = args.back();
+  for (size_t i = args.size() - 1; i-- > 0;) {
+    const Datum& x = args[i];
+    if (x.kind == DatumKind::Scalar) {
+      if (x.scalar->valid) acc = x;
+      continue;
+    }
+    exec::ArraySpan span;
+    span.SetMembers(*x.array);
+    AHC_RETURN_NOT_OK(span.UpdateNullCount(s));
+    if (span.nulls == 0) { acc = x; continue; }
+    x.array->null_count = span.nulls;
+    CondBits bits;
+    bits.data = (const uint8_t*)x.array->buffers[0]->dptr;
+    bits.off = x.array->offset;
+    AHC_RETURN_NOT_OK(IfElseRows(s, bits, x, acc, n, &acc));
+  }
+  if (acc.kind == DatumKind::Scalar && n >= 0) return BroadcastRows(s, acc, n, out);
+  *out = acc;
+  return Status::OK();
+}
+
+// fill_null_forward / fill_null_backward: the fused entry for values of 1 / 2 / 4 / 8 / 16 / 32 bytes; Boolean, var-length and
+// other widths through ah_fill_null_indices and the Take of their layout.  A column without nulls is returned as it is.  A chunked
+// column arrives concatenated (ExecuteChunked), so the carry crosses the chunk borders, and leaves re-chunked like the input.
+Status ExecFillDirected(KernelCtx* k, const ExecSpan& b, ExecResult* out, int direction) {
+  Session* s = k->session;
+  ArraySpan in = b.values[0].array;
+  AHC_RETURN_NOT_OK(in.UpdateNullCount(s));
+  const int64_t n = in.len;
+  if (in.nulls == 0 || n == 0) {
+    *out = in;
+    out->nulls = 0;
+    return Status::OK();
+  }
+  const int w = in.type->bit_width / 8;
+  const bool fixed = in.type->id != Type::BOOL && !IsBaseBinary(in.type->id);
+  if (fixed) AHC_RETURN_NOT_OK(CheckSlotWidth(in));
+  const bool word_aligned = fixed && (((uintptr_t)in.buffers[1].buf) & (uintptr_t)((w < 8 ? w : 8) - 1)) == 0;
+  if (fixed && word_aligned && (w == 1 || w == 2 || w == 4 || w == 8 || w == 16 || w == 32)) {
+    BufferPtr vb, db;
+    AHC_RETURN_NOT_OK(k->AllocateBitmap(n, &vb));
+    AHC_RETURN_NOT_OK(k->Allocate(n * w, &db, /*zero_all=*/false));
+    int64_t nulls = 0;
+    AHC_RETURN_NOT_OK(s->FromStatus(ah_fill_null_directed(s->ctx(), w, in.buffers[1].buf, in.buffers[0].buf, in.offset, n, direction, db->dptr, (uint8_t*)vb->dptr, &nulls)));
+    out->len = n;
+    out->offset = 0;
+    out->buffers[0].WrapBuffer(vb);
+    out->buffers[1].WrapBuffer(db);
+    out->nulls = nulls;
+    return Status::OK();
+  }
+  IndexOperand ix;
+  ix.width = 4;
+  ix.len = n;
+  AHC_RETURN_NOT_OK(s->Allocate(n * 4, &ix.data_buf, /*zero_all=*/false));
+  AHC_RETURN_NOT_OK(s->AllocateBitmap(n, &ix.valid_buf));
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_fill_null_indices(s->ctx(), in.buffers[0].buf, in.offset, n, direction, (uint32_t*)ix.data_buf->dptr, (uint8_t*)ix.valid_buf->dptr, &ix.nulls)));
+  ix.data = ix.data_buf->dptr;
+  ix.valid = ix.nulls ? (const uint8_t*)ix.valid_buf->dptr : nullptr;
+  // the sources are valid rows: the output has a null exactly where an index slot is null
+  if (in.type->id == Type::BOOL) return TakeBooleanCommon(k, in, ix, ix.nulls != 0, out);
+  if (!fixed) return TakeBinaryCommon(k, in, ix, ix.nulls != 0, out);
+  return TakeFixedCommon(k, in, ix, ix.nulls != 0, /*bounds_check=*/0, out);
+}
+
+}  // namespace
+
+void RegisterConditional(FunctionRegistry* reg) {
+  reg->AddFunction(std::make_shared<ConditionalFunction>("if_else", Arity{3, false}, 1, IfElseImpl), false);
+  reg->AddFunction(std::make_shared<ConditionalFunction>("coalesce", Arity{1, true}, 0, CoalesceImpl), false);
+  reg->AddFunction(std::make_shared<ConditionalFunction>("fill_null", Arity{2, false}, 0, CoalesceImpl), false);
+  for (int direction : {kForward, kBackward}) {
+    auto fn = std::make_shared<VectorFunction>(direction == kForward ? "fill_null_forward" : "fill_null_backward", Arity{1, false});
+    for (Type t : ConditionalValueTypes()) {
+      exec::VectorKernel k;
+      k.sig.in_types = {t};
+      k.exec_fn = [direction](KernelCtx* c, const ExecSpan& b, ExecResult* o) { return ExecFillDirected(c, b, o, direction); };
+      k.can_execute_chunkwise = false;   // the carry crosses chunk borders
+      fn->AddKernel(std::move(k));
+    }
+    reg->AddFunction(fn, false);
+  }
+}
+
 }  // namespace compute
 }  // namespace arrowhip

@@ -563,6 +563,81 @@ func (x *Context) WindowScan(op WindowScanOp, typeID arrow.Type, values, valid u
 	return x.err(C.ah_window_scan(x.c, C.int(op), C.int(typeID), values, (*C.uint8_t)(valid), C.int64_t(off), (*C.uint8_t)(flags), (*C.uint64_t)(order), C.int64_t(n), outValues))
 }
 
+// ---- conditionals: if_else and the directed null fills (no reference analogue; Arrow C++'s semantics) ---------------------------
+
+// CondSide is one side of the IfElse calls (ah_cond_side).  Fixed width: OffsetWidth 0, Data the slots of ByteWidth bytes; Boolean
+// (IfElseBoolean): Data a bitmap; var-length: OffsetWidth 4 or 8, Offsets the offsets buffer, Data the value bytes.  Valid (nil: no
+// nulls) and, for Boolean sides, Data are read at bit Off + i; row i is element Off + i.  Broadcast: a scalar as a one-row device
+// column, every row reads element Off.
+type CondSide struct {
+	OffsetWidth, ByteWidth int
+	Offsets, Data, Valid   unsafe.Pointer
+	Off                    int64
+	Broadcast              bool
+}
+
+func (o CondSide) c() C.ah_cond_side {
+	var r C.ah_cond_side
+	r.offset_width, r.byte_width, r.offsets, r.data, r.valid, r.off = C.int(o.OffsetWidth), C.int(o.ByteWidth), o.Offsets, o.Data, (*C.uint8_t)(o.Valid), C.int64_t(o.Off)
+	if o.Broadcast {
+		r.broadcast = 1
+	}
+	return r
+}
+
+// IfElse writes row i = l[i] where the condition's bit condOff + i is set, else r[i]; the row is null where the condition or the
+// chosen side is (payload 0).  Fixed-width sides of one byte width.  outValid (from bit 0) may be nil only when condValid and both
+// sides' Valid are.  Enqueued; no synchronisation.
+func (x *Context) IfElse(condData, condValid unsafe.Pointer, condOff int64, l, r CondSide, n int64, outValues, outValid unsafe.Pointer) error {
+	lc, rc := l.c(), r.c()
+	return x.err(C.ah_if_else(x.c, (*C.uint8_t)(condData), (*C.uint8_t)(condValid), C.int64_t(condOff), &lc, &rc, C.int64_t(n), outValues, (*C.uint8_t)(outValid)))
+}
+
+// IfElseBoolean is IfElse for Boolean sides: outData and outValid are bitmaps from bit 0, a null row's data bit is 0.
+func (x *Context) IfElseBoolean(condData, condValid unsafe.Pointer, condOff int64, l, r CondSide, n int64, outData, outValid unsafe.Pointer) error {
+	lc, rc := l.c(), r.c()
+	return x.err(C.ah_if_else_boolean(x.c, (*C.uint8_t)(condData), (*C.uint8_t)(condValid), C.int64_t(condOff), &lc, &rc, C.int64_t(n), (*C.uint8_t)(outData), (*C.uint8_t)(outValid)))
+}
+
+// IfElseBinaryOffsets is the first call for var-length sides: outOffsets[0 … n] (outOffsetWidth bytes each, from 0), the validity, and
+// the number of value bytes to allocate for IfElseBinaryData.  Bytes that do not fit 4-byte offsets are arrow.ErrInvalid.
+func (x *Context) IfElseBinaryOffsets(condData, condValid unsafe.Pointer, condOff int64, l, r CondSide, n int64, outOffsetWidth int, outOffsets, outValid unsafe.Pointer) (totalBytes int64, err error) {
+	lc, rc := l.c(), r.c()
+	var tot C.int64_t
+	err = x.err(C.ah_if_else_binary_offsets(x.c, (*C.uint8_t)(condData), (*C.uint8_t)(condValid), C.int64_t(condOff), &lc, &rc, C.int64_t(n), C.int(outOffsetWidth), outOffsets, (*C.uint8_t)(outValid), &tot))
+	return int64(tot), err
+}
+
+// IfElseBinaryData copies the chosen rows' bytes behind the offsets IfElseBinaryOffsets wrote.
+func (x *Context) IfElseBinaryData(condData, condValid unsafe.Pointer, condOff int64, l, r CondSide, n int64, outOffsetWidth int, outOffsets, outData unsafe.Pointer) error {
+	lc, rc := l.c(), r.c()
+	return x.err(C.ah_if_else_binary_data(x.c, (*C.uint8_t)(condData), (*C.uint8_t)(condValid), C.int64_t(condOff), &lc, &rc, C.int64_t(n), C.int(outOffsetWidth), outOffsets, (*C.uint8_t)(outData)))
+}
+
+// FillDirection of the directed null fills: a null row takes the nearest valid row before (forward) or after (backward) it.
+type FillDirection int
+
+const (
+	FillForward  FillDirection = 0
+	FillBackward FillDirection = 1
+)
+
+// FillNullIndices writes per row the number of the row it takes its value from (uint32, 0 where there is none) and that slot's
+// validity bit: the (indices, validity) pair the Take calls read.  Returns the number of rows that stay null.
+func (x *Context) FillNullIndices(valid unsafe.Pointer, off, n int64, direction FillDirection, outIdx, outIdxValid unsafe.Pointer) (nulls int64, err error) {
+	var r C.int64_t
+	err = x.err(C.ah_fill_null_indices(x.c, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), C.int(direction), (*C.uint32_t)(outIdx), (*C.uint8_t)(outIdxValid), &r))
+	return int64(r), err
+}
+
+// FillNullDirected is the same walk with the gather fused in, for values of 1, 2, 4, 8, 16 or 32 bytes: outValues[i] =
+// values[off + source of row i], payload 0 where a row stays null.  Returns the number of rows that stay null.
+func (x *Context) FillNullDirected(byteWidth int, values, valid unsafe.Pointer, off, n int64, direction FillDirection, outValues, outValid unsafe.Pointer) (nulls int64, err error) {
+	var r C.int64_t
+	err = x.err(C.ah_fill_null_directed(x.c, C.int(byteWidth), values, (*C.uint8_t)(valid), C.int64_t(off), C.int64_t(n), C.int(direction), outValues, (*C.uint8_t)(outValid), &r))
+	return int64(r), err
+}
+
 // ---- ingest slots: the building blocks of Ingest for callers that run their own kernels on the chunks ------------------------
 
 func (i *Ingest) Depth() int      { return int(C.ah_ingest_depth(i.g)) }

@@ -1024,6 +1024,60 @@ int ah_take_binary_offsets(ah_ctx* ctx, int offset_width, const void* offsets, c
 int ah_take_binary_data(ah_ctx* ctx, int offset_width, const void* offsets, const uint8_t* data, int64_t voff, int idx_byte_width,
                         const void* idx, int64_t nidx, const void* out_offsets, uint8_t* out_data);
 
+/* ---- conditionals: if_else and the directed null fills (NEW — no reference analogue: arrow-go has neither; the semantics are
+ * Arrow C++'s) ----------------------------------------------------------------------------------------------------
+ * if_else(cond, l, r): row i is null where cond[i] is null; otherwise it is l[i] (cond true) or r[i] with that side's validity.
+ * The condition is a Boolean column: cond_data and cond_valid (nullable) are bitmaps read at bit cond_off + i.  coalesce(x, y) is
+ * if_else with cond_data = x's validity bitmap and cond_valid = NULL.  Where Arrow leaves bytes unspecified: the payload under a
+ * null slot of a fixed-width output is zero bytes, a null data bit is 0, a null var-length row has length 0.
+ *
+ * One side.  Fixed width: offset_width 0, row i is the byte_width bytes at data + (off + i) * byte_width.  Boolean
+ * (ah_if_else_boolean): `data` is a bitmap read at bit off + i.  Var-length: offset_width 4 or 8, `offsets` the offsets buffer,
+ * row i is data[offsets[off + i] ... offsets[off + i + 1]).  `valid` (nullable) is read at bit off + i.  broadcast != 0: a scalar
+ * as a one-row device column, every row reads element `off`.  Buffers are DEVICE memory; the descriptor itself is host memory. */
+typedef struct ah_cond_side {
+  int offset_width;
+  int byte_width;
+  const void* offsets;
+  const void* data;
+  const uint8_t* valid;
+  int64_t off;
+  int broadcast;
+} ah_cond_side;
+/* Fixed-width sides of the same byte_width (1 ... 4096; 1 / 2 / 4 / 8 / 16 / 32 move as vectors when the buffers are aligned to
+ * min(byte_width, 8), any other width or alignment row by row).  One streaming pass, no host synchronisation.  out_values: n
+ * slots; out_valid: a bitmap that starts at bit 0 — exactly ceil(n / 8) bytes are written, the unused bits of the last one 0.
+ * The three input offsets are independent.  out_valid may be NULL only when cond_valid, l->valid and r->valid all are. */
+int ah_if_else(ah_ctx* ctx, const uint8_t* cond_data, const uint8_t* cond_valid, int64_t cond_off, const ah_cond_side* l,
+               const ah_cond_side* r, int64_t n, void* out_values, uint8_t* out_valid);
+/* Boolean sides: (c & l) | (~c & r) word by word on data and validity.  out_data and out_valid start at bit 0, ceil(n / 8) bytes
+ * each.  No host synchronisation. */
+int ah_if_else_boolean(ah_ctx* ctx, const uint8_t* cond_data, const uint8_t* cond_valid, int64_t cond_off, const ah_cond_side* l,
+                       const ah_cond_side* r, int64_t n, uint8_t* out_data, uint8_t* out_valid);
+/* Var-length sides (either may have 4- or 8-byte offsets), two calls with the caller's allocation in between, like
+ * ah_take_binary_offsets / _data:
+ *   _offsets: out_offsets[0 ... n] (out_offset_width bytes each, starting at 0), out_valid (as above), the number of data bytes;
+ *             AH_EINVALID "binary output offset overflow" when they do not fit 4-byte offsets — synchronises;
+ *   _data:    the bytes, into a buffer of that many bytes; out_offsets is what _offsets wrote.  No host synchronisation. */
+int ah_if_else_binary_offsets(ah_ctx* ctx, const uint8_t* cond_data, const uint8_t* cond_valid, int64_t cond_off, const ah_cond_side* l,
+                              const ah_cond_side* r, int64_t n, int out_offset_width, void* out_offsets, uint8_t* out_valid,
+                              int64_t* out_total_bytes_host);
+int ah_if_else_binary_data(ah_ctx* ctx, const uint8_t* cond_data, const uint8_t* cond_valid, int64_t cond_off, const ah_cond_side* l,
+                           const ah_cond_side* r, int64_t n, int out_offset_width, const void* out_offsets, uint8_t* out_data);
+/* fill_null_forward (direction 0) / fill_null_backward (direction 1): a null row takes the nearest valid row at or before / at
+ * or after it and stays null when there is none.  `valid` (nullable) is read at bit off + i.  n <= 2^32 - 1 (AH_ENOTIMPL
+ * above).  The walk is over the bitmap's 64-bit words: a count-leading / -trailing-zeros inside a word, a reduce-then-scan
+ * running maximum across them (three launches, no workgroup waits for another).  Outputs start at bit 0 / row 0; a validity
+ * output is needed whenever `valid` is given.  out_null_count_host nullable: when given, the call synchronises.
+ *   _indices:  out_idx[i] (uint32) = the row number of row i's source, 0 where there is none, and out_idx_valid its bit: the
+ *              (idx, ivalid) pair of the Take family, for the columns _directed does not take (Boolean, var-length, odd widths);
+ *   _directed: the same walk with the gather fused in: out_values[i] = values[off + source] (payload 0 where there is none) for
+ *              byte_width 1 / 2 / 4 / 8 / 16 / 32 (AH_ENOTIMPL otherwise); `values` is the buffer's element 0. */
+int ah_fill_null_indices(ah_ctx* ctx, const uint8_t* valid, int64_t off, int64_t n, int direction, uint32_t* out_idx,
+                         uint8_t* out_idx_valid, int64_t* out_null_count_host);
+int ah_fill_null_directed(ah_ctx* ctx, int byte_width, const void* values, const uint8_t* valid, int64_t off, int64_t n, int direction,
+                          void* out_values, uint8_t* out_valid, int64_t* out_null_count_host);
+
 /* ---- fused scalar-expression evaluation (row §8(f)-1: the expression executor) ---------
  * What compute.Expression trees — NewCall / NewFieldRef / NewLiteral, arrow/compute/
  * expression.go:596-620 — evaluate to through executeScalarBatch (arrow/compute/exprs/

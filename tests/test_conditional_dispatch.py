@@ -1,0 +1,69 @@
+"""The conditionals in the function registry, resolved without a device: the five names, the promotion rule of the value arguments
+(the rule `add` uses; the condition stays Boolean), and the refusals with the reference's dispatch errors.  That the six new entry
+points of include/arrowhip.h are exported — header == nm -D — is tests/test_abi.py's."""
+import pyarrow as pa
+import pytest
+
+from arrow_go_amd import _native as N
+from arrow_go_amd import compute as ac
+
+B, I8, U8, I32, I64, U64, F32, F64 = pa.bool_(), pa.int8(), pa.uint8(), pa.int32(), pa.int64(), pa.uint64(), pa.float32(), pa.float64()
+NAMES = ("if_else", "coalesce", "fill_null", "fill_null_forward", "fill_null_backward")
+VALUE_TYPES = [pa.int8(), pa.uint8(), pa.int16(), pa.uint16(), pa.int32(), pa.uint32(), pa.int64(), pa.uint64(), pa.float32(), pa.float64(),
+               pa.bool_(), pa.string(), pa.binary(), pa.large_string(), pa.large_binary()]
+
+
+def test_the_five_functions_are_registered():
+    for name in NAMES:
+        assert ac.has_function(name), name
+        assert ac.function_num_kernels(name) == 18, name   # 10 numeric + bool + 4 binary-like + 3 fixed-width binary value types
+    for wrong in ("case_when", "choose", "ifelse", "fill_null_fwd"):
+        assert not ac.has_function(wrong)
+
+
+def test_the_six_entry_points_are_declared():
+    declared = set(N.declared_symbols())
+    assert {"ah_if_else", "ah_if_else_boolean", "ah_if_else_binary_offsets", "ah_if_else_binary_data", "ah_fill_null_indices",
+            "ah_fill_null_directed"} <= declared
+    assert len(declared) == 152
+
+
+def test_every_value_type_dispatches_exactly():
+    for t in VALUE_TYPES:
+        assert ac.dispatch_best("if_else", [B, t, t]) == [B, t, t]
+        assert ac.dispatch_best("coalesce", [t]) == [t]
+        assert ac.dispatch_best("coalesce", [t, t, t, t]) == [t, t, t, t]
+        assert ac.dispatch_best("fill_null", [t, t]) == [t, t]
+        assert ac.dispatch_best("fill_null_forward", [t]) == [t] and ac.dispatch_best("fill_null_backward", [t]) == [t]
+
+
+@pytest.mark.parametrize("given,want", [
+    ((I32, I64), I64), ((I64, I32), I64), ((I8, U8), pa.int16()), ((U8, U8), U8), ((I32, F32), F32), ((I64, F64), F64), ((U64, I8), I64),
+    ((pa.uint32(), pa.int32()), I64), ((F32, F64), F64),
+])
+def test_numeric_sides_are_promoted_like_add(given, want):
+    assert ac.dispatch_best("add", list(given)) == [want, want]   # the rule itself …
+    assert ac.dispatch_best("if_else", [B, *given]) == [B, want, want]   # … applied to the sides, the condition kept
+    assert ac.dispatch_best("fill_null", list(given)) == [want, want]
+    assert ac.dispatch_best("coalesce", [given[0], given[1], given[0]]) == [want, want, want]
+
+
+def test_refusals():
+    with pytest.raises(ac.ErrNotImplemented, match=r"function 'if_else' has no kernel matching input types \(int8, int32, int32\)"):
+        ac.dispatch_best("if_else", [I8, I32, I32])    # the condition is Boolean, and is not promoted to it
+    with pytest.raises(ac.ErrNotImplemented, match=r"function 'if_else' has no kernel matching input types \(bool, utf8, int32\)"):
+        ac.dispatch_best("if_else", [B, pa.string(), I32])
+    with pytest.raises(ac.ErrNotImplemented, match="no kernel matching"):
+        ac.dispatch_best("if_else", [B, pa.string(), pa.large_string()])   # no common binary type either: the pairing matches exactly or not at all
+    with pytest.raises(ac.ErrNotImplemented, match="no kernel matching"):
+        ac.dispatch_best("coalesce", [I32, pa.string()])
+    with pytest.raises(ac.ErrNotImplemented, match="no kernel matching"):
+        ac.dispatch_best("fill_null", [B, I32])    # Boolean is not a numeric type
+    with pytest.raises(ac.ErrInvalid, match="function 'if_else' accepts 3 arguments but 2 passed"):
+        ac.dispatch_best("if_else", [B, I32])
+    with pytest.raises(ac.ErrInvalid, match="varargs function 'coalesce' needs at least 1 arguments, but only 0 passed"):
+        ac.dispatch_best("coalesce", [])
+    with pytest.raises(ac.ErrInvalid, match="function 'fill_null' accepts 2 arguments but 3 passed"):
+        ac.dispatch_best("fill_null", [I32, I32, I32])
+    with pytest.raises(ac.ErrInvalid, match="function 'fill_null_forward' accepts 1 arguments but 2 passed"):
+        ac.dispatch_best("fill_null_forward", [I32, I32])
