@@ -273,6 +273,33 @@ lib.ah_ingest_slot_buffer.restype = _vp
 lib.ah_version.argtypes = []
 lib.ah_version.restype = C.c_char_p
 
+# the string predicates: libarrowhip_strings.so (include/arrowhip_strings.h), a library of its own on the same ah_ctx
+STRINGS_LIB_PATH = os.path.join(_HERE, "libarrowhip_strings.so")
+STRINGS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "arrowhip_strings.h")
+_STRINGS_SIGS = {
+    "ah_string_match": [_vp, _int, _vp, _i64, _vp, _i64, _vp, _i64],
+    "ah_string_find": [_vp, _vp, _i64, _vp, _i64, _int, _vp],
+    "ah_string_like": [_vp, _vp, _i64, _int, _vp, _i64, _vp, _i64],
+    "ah_string_length": [_vp, _vp, _i64, _int, _int, _vp],
+}
+
+
+def _load_strings() -> C.CDLL:
+    if not os.path.exists(STRINGS_LIB_PATH):
+        raise ImportError(f"{STRINGS_LIB_PATH} is missing — build() makes it beside libarrowhip.so. There is no CPU fallback.")
+    sl = C.CDLL(STRINGS_LIB_PATH, mode=C.RTLD_GLOBAL)
+    missing = [s for s in declared_symbols(STRINGS_HEADER_PATH) if not hasattr(sl, s)]
+    if missing:
+        raise ImportError(f"libarrowhip_strings.so does not export symbols declared in arrowhip_strings.h: {missing}")
+    for name, args in _STRINGS_SIGS.items():
+        fn = getattr(sl, name)
+        fn.argtypes = args
+        fn.restype = _int
+    return sl
+
+
+strings_lib = _load_strings()
+
 
 def check(ctx_handle, status: int) -> None:
     if status == AH_OK:

@@ -79,6 +79,10 @@ lib.ahc_ipc_writer_close.argtypes = [_vp]
 lib.ahc_ipc_writer_close.restype = None
 lib.ahc_substrait_inspect.argtypes = [_vp, C.c_int64, C.c_char_p, C.c_int64]
 lib.ahc_dispatch_best.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int64]
+lib.ahc_output_type.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int64]
+lib.ahc_validate_options.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]
+lib.ahc_like_compile.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64]
+lib.ahc_like_compile.restype = C.c_int64
 lib.ahc_expr_eval.argtypes = [_vp, C.c_char_p, C.c_int, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(C.c_int)]
 
 
@@ -275,6 +279,45 @@ def dispatch_best(function: str, types):
     import pyarrow as pa
     named = {"float": pa.float32(), "double": pa.float64(), "bool": pa.bool_()}
     return [named.get(back[i], None) or getattr(pa, back[i])() for i in tout]
+
+def output_type_id(function: str, type_ids) -> int:
+    """The arrow.Type id of what the kernel DispatchBest chooses for these argument type ids returns (ahc_output_type; 0 where the
+    call's options decide it), without a device; raises like dispatch_best."""
+    n = len(type_ids)
+    out = C.c_int()
+    err = C.create_string_buffer(1024)
+    rc = lib.ahc_output_type(function.encode(), n, (C.c_int * n)(*type_ids), C.byref(out), err, len(err))
+    if rc != 0:
+        raise _ERRS.get(rc, ArrowError)(err.value.decode(errors="replace"))
+    return out.value
+
+
+def validate_options(function: str, options: str) -> None:
+    """What `function` answers to an options string before anything runs, without a device (ahc_validate_options): the string
+    predicates check pattern_hex / ignore_case; raises the error class the call would raise."""
+    err = C.create_string_buffer(1024)
+    rc = lib.ahc_validate_options(function.encode(), options.encode(), err, len(err))
+    if rc != 0:
+        raise _ERRS.get(rc, ArrowError)(err.value.decode(errors="replace"))
+
+
+def like_compile(pattern) -> bytes:
+    """A SQL LIKE pattern (str or bytes; `%`, `_`, `\\` as in Arrow C++'s match_like) compiled on the host into the segment program
+    Context.string_like takes (ahc_like_compile, host/like_program.h)."""
+    pat = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+    out = C.create_string_buffer(3 + 4 * len(pat) + 8)
+    n = lib.ahc_like_compile(C.c_char_p(pat), len(pat), out, len(out))
+    if n < 0:
+        raise ErrInvalid("like_compile: the program does not fit its buffer")
+    return out.raw[:n]
+
+
+def pattern_options(pattern, ignore_case: bool = False) -> str:
+    """The options string of the string predicates: "pattern_hex=<the pattern's bytes in hex>" (a pattern may hold `;`, `=` or bytes
+    that are no UTF-8), and "ignore_case=true" where asked — which the functions refuse with ErrNotImplemented."""
+    pat = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+    return "pattern_hex=" + pat.hex() + (";ignore_case=true" if ignore_case else "")
+
 
 def inspect_substrait(buf) -> str:
     """What the Substrait reader understood of a serialized ExtendedExpression, without a device (ahc_substrait_inspect):
@@ -535,7 +578,8 @@ class Session:
         """ExecCtx fields of this session: 'chunk_bytes' (ExecCtx.ChunkSize's role for host-resident arguments), 'host_threshold_bytes';
         for the read_ipc calls that follow: 'ipc_device_lz4' (1: LZ4_FRAME bodies of independent blocks are inflated in HBM, 0: on the
         host like every other compressed body), 'ipc_device_lz4_min_bytes' (smaller compressed bodies stay on the host);
-        'select_k_route' (0: select_k chooses its route, 1: the radix route, 2: the sort with its final widening cut at k)."""
+        'select_k_route' (0: select_k chooses its route, 1: the radix route, 2: the sort with its final widening cut at k);
+        'string_tile_bytes' (the LDS tile of the string searches: 0 the default, else 64 … 32768 — no result depends on it)."""
         self._check(lib.ahc_session_set_option(self.h, name.encode(), int(value)))
 
     def import_host(self, arr) -> "DeviceArray":
@@ -775,6 +819,42 @@ class Session:
         """call_function("fill_null_backward", [values]): a null row takes the nearest valid row after it and stays null when there
         is none (trailing nulls); otherwise as fill_null_forward."""
         return self.call_function("fill_null_backward", [values], keep_on_device=keep_on_device)
+
+    # -- string predicates (Arrow C++'s semantics; values a String / Binary / LargeString / LargeBinary Array, ChunkedArray or DeviceArray,
+    # pattern str or bytes; the output's validity is the input's).  Session option 'string_tile_bytes' (0 = default) moves the tile
+    # borders of the searches; no result depends on it.
+    def match_substring(self, values, pattern, ignore_case: bool = False, keep_on_device: bool = False):
+        """call_function("match_substring", [values], "pattern_hex=…"): Boolean, the pattern's bytes occur in the row; the empty pattern
+        matches every row.  ignore_case=True is refused (ErrNotImplemented)."""
+        return self.call_function("match_substring", [values], pattern_options(pattern, ignore_case), keep_on_device=keep_on_device)
+
+    def starts_with(self, values, pattern, ignore_case: bool = False, keep_on_device: bool = False):
+        """call_function("starts_with", [values], "pattern_hex=…"): Boolean, the row begins with the pattern's bytes."""
+        return self.call_function("starts_with", [values], pattern_options(pattern, ignore_case), keep_on_device=keep_on_device)
+
+    def ends_with(self, values, pattern, ignore_case: bool = False, keep_on_device: bool = False):
+        """call_function("ends_with", [values], "pattern_hex=…"): Boolean, the row ends with the pattern's bytes."""
+        return self.call_function("ends_with", [values], pattern_options(pattern, ignore_case), keep_on_device=keep_on_device)
+
+    def find_substring(self, values, pattern, ignore_case: bool = False, keep_on_device: bool = False):
+        """call_function("find_substring", [values], "pattern_hex=…"): Int32 (Int64 for the Large types), the byte index of the pattern's
+        first occurrence in the row, -1 if there is none, 0 for the empty pattern."""
+        return self.call_function("find_substring", [values], pattern_options(pattern, ignore_case), keep_on_device=keep_on_device)
+
+    def match_like(self, values, pattern, ignore_case: bool = False, keep_on_device: bool = False):
+        """call_function("match_like", [values], "pattern_hex=…"): Boolean, SQL LIKE over the whole row: `%` any run of bytes, `_` one
+        character (a code point of a String / LargeString, a byte of a Binary / LargeBinary), `\\` makes the next pattern character
+        literal, a trailing lone `\\` matches nothing."""
+        return self.call_function("match_like", [values], pattern_options(pattern, ignore_case), keep_on_device=keep_on_device)
+
+    def binary_length(self, values, keep_on_device: bool = False):
+        """call_function("binary_length", [values]): Int32 (Int64 for the Large types), the bytes of the row; also FixedSizeBinary."""
+        return self.call_function("binary_length", [values], keep_on_device=keep_on_device)
+
+    def utf8_length(self, values, keep_on_device: bool = False):
+        """call_function("utf8_length", [values]): Int32 / Int64, the code points of a String / LargeString row = its bytes that are not
+        10xxxxxx continuation bytes (which is also what it counts on bytes that are no valid UTF-8)."""
+        return self.call_function("utf8_length", [values], keep_on_device=keep_on_device)
 
     def hash_join(self, left, right, keys, right_keys=None, join_type: str = "inner", keep_on_device: bool = False):
         """call_function("hash_join", [left, right], "left_keys=…;right_keys=…;type=…"): the two record batches joined on their key

@@ -100,6 +100,7 @@ struct ah_ctx {
   int opt_encode_table_batch;   // partition-first encode: the table pass probes its four records' first groups together (1) or one by one (0)
   int opt_encode_unperm_group;  // partition-first encode: tiles per workgroup in the final un-permute (1 or 4)
   int opt_take_vec_nt;     // nontemporal hints of the clustered take (7 all, 5 index + output, 4 output, 0 none)
+  int opt_string_tile_bytes;  // string searches (ah_string_match.hip): bytes of the data buffer per LDS tile, 0 = the default (16384); 64 … 32768
   // 2 × 8 words of coherent (fine-grained) pinned host memory kernels can store to: {value, sequence number} for ah_filter_count, {≤ 7 words, sequence number} for ah_mailbox_read.  A count the host
   // must see before it can go on (ah_filter_count) is polled here instead of paying a stream synchronisation's wake-up.
   unsigned long long* mailbox;

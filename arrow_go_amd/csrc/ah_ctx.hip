@@ -163,6 +163,10 @@ AH_EXPORT int ah_ctx_set_option(ah_ctx* c, const char* name, int64_t value) {
   else if (!strcmp(name, "groupby_reserve")) c->opt_groupby_reserve = (int)value;
   else if (!strcmp(name, "filter_cache")) { c->opt_filter_cache = value != 0; if (!value) c->fcache.valid = false; }
   else if (!strcmp(name, "scan_segment_log2")) c->opt_scan_segment_log2 = (int)value;
+  else if (!strcmp(name, "string_tile_bytes")) {
+    if (value != 0 && (value < 64 || value > 32768)) return ah_fail(c, AH_EINVALID, "set_option: string_tile_bytes is 0 (default) or 64 … 32768");
+    c->opt_string_tile_bytes = (int)value;
+  }
   else return ah_fail(c, AH_EINVALID, "set_option: unknown option '%s'", name);
   return AH_OK;
 }

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from ._native import lib, check
+from ._native import lib, strings_lib, check
 
 
 def _ptr(x) -> Optional[int]:
@@ -630,6 +630,34 @@ class Context:
         lo = _CmpOperand(left[0], left[1], _ptr(left[2]), _ptr(left[3]), left[4], left[5])
         ro = _CmpOperand(right[0], right[1], _ptr(right[2]), _ptr(right[3]), right[4], right[5])
         check(self.handle, lib.ah_compare_binary(self.handle, cmpop, C.byref(lo), C.byref(ro), n, _ptr(out_bits), out_bit_offset))
+
+    # ---- string predicates (libarrowhip_strings.so: csrc/strings/ah_string_match.hip, include/arrowhip_strings.h).  column: (offset_width, byte_width, offsets, data, off) — offset_width 4 / 8; 0 (fixed
+    # slots of byte_width bytes) only for string_length without utf8.  pattern / program: bytes on the host.
+    @staticmethod
+    def _column(column) -> _CmpOperand:
+        return _CmpOperand(column[0], column[1], _ptr(column[2]), _ptr(column[3]), column[4], 0)
+
+    def string_match(self, op: int, column, n: int, pattern: bytes, out_bits, out_bit_offset: int = 0) -> None:
+        """op 0 the pattern occurs in the row, 1 the row starts with it, 2 ends with it, 3 is it: bits [out_bit_offset, + n) of
+        out_bits, every other bit kept; every row computed, nulls included; no synchronisation (ah_string_match)"""
+        col = self._column(column)
+        check(self.handle, strings_lib.ah_string_match(self.handle, op, C.byref(col), n, C.c_char_p(bytes(pattern)), len(pattern), _ptr(out_bits), out_bit_offset))
+
+    def string_find(self, column, n: int, pattern: bytes, out_width: int, out) -> None:
+        """out[i] (Int32 / Int64 by out_width) = the byte index of the pattern's first occurrence in row i, -1 for none (ah_string_find)"""
+        col = self._column(column)
+        check(self.handle, strings_lib.ah_string_find(self.handle, C.byref(col), n, C.c_char_p(bytes(pattern)), len(pattern), out_width, _ptr(out)))
+
+    def string_like(self, column, n: int, utf8: bool, program: bytes, out_bits, out_bit_offset: int = 0) -> None:
+        """SQL LIKE with the pattern compiled by compute.like_compile; utf8: `_` is one code point, else one byte (ah_string_like)"""
+        col = self._column(column)
+        check(self.handle, strings_lib.ah_string_like(self.handle, C.byref(col), n, int(bool(utf8)), C.c_char_p(bytes(program)), len(program), _ptr(out_bits),
+                                              out_bit_offset))
+
+    def string_length(self, column, n: int, utf8: bool, out_width: int, out) -> None:
+        """out[i] = the bytes of row i, or (utf8) its bytes that are not 10xxxxxx continuation bytes (ah_string_length)"""
+        col = self._column(column)
+        check(self.handle, strings_lib.ah_string_length(self.handle, C.byref(col), n, int(bool(utf8)), out_width, _ptr(out)))
 
     def compare_decimal(self, cmpop: int, left, right, n: int, out_bits, out_bit_offset: int = 0) -> None:
         """left / right: (width 16 | 32, data, off, broadcast, scale-up exponent)"""

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/arrowhip.h"
+#include "../../include/arrowhip_strings.h"   // the string predicates: libarrowhip_strings.so, on the same ah_ctx
 
 namespace arrowhip {
 
@@ -357,6 +358,16 @@ struct RankOptions : FunctionOptions {
   std::string Tiebreaker;
   const char* TypeName() const override { return "RankOptions"; }
 };
+// match_substring, starts_with, ends_with, find_substring, match_like: Arrow C++'s MatchSubstringOptions.  The options string carries
+// the pattern as hex (pattern_hex=…: it may hold `;`, `=` or bytes that are no UTF-8); ignore_case=true is refused (Arrow folds
+// Unicode case through RE2; an ASCII fold would silently disagree).
+struct MatchSubstringOptions : FunctionOptions {
+  std::string Pattern;
+  bool PatternGiven = false, PatternBadHex = false, IgnoreCase = false;
+  const char* TypeName() const override { return "MatchSubstringOptions"; }
+};
+// what the pattern functions answer to their options before anything runs (also ahc_validate_options, without a device)
+Status ValidateStringMatchOptions(const std::string& function, const FunctionOptions* options);
 struct CompareFilterSumOptions : FunctionOptions { int cmpop = AH_CMP_GT; const char* TypeName() const override { return "CompareFilterSumOptions"; } };
 
 // compute.Datum (datum.go:35-40): array or scalar
@@ -477,6 +488,8 @@ class ScalarFunction : public Function {  // functions.go:239-290
   // the conditionals (if_else, coalesce, fill_null): when no kernel matches exactly, the arguments from this position on — the
   // values, not the condition — are promoted to commonNumeric by the rule `add` uses; −1: no such step
   int promote_from = -1;
+  // the string predicates: a scalar argument is refused instead of being computed as a one-row array
+  bool arrays_only = false;
   Status DispatchBest(std::vector<const DataType*>* types, const exec::ScalarKernel** out) const;
  private:
   std::vector<exec::ScalarKernel> kernels_;
@@ -558,6 +571,7 @@ void RegisterGroupBy(FunctionRegistry* reg);
 void RegisterHashJoin(FunctionRegistry* reg);
 void RegisterWindow(FunctionRegistry* reg);
 void RegisterConditional(FunctionRegistry* reg);
+void RegisterStringMatch(FunctionRegistry* reg);
 
 // ---- compute.Expression (arrow/compute/expression.go:59-78,596-620) and its executor
 // (arrow/compute/exprs/exec.go:440-700 ExecuteScalarExpression / executeScalarBatch) --------

@@ -14,6 +14,7 @@
 
 #include "arrowhip_compute.h"
 #include "capi_internal.h"
+#include "like_program.h"
 #include "ipc.h"
 
 // the public C header: the Arrow C Data / C Device Data structs and every ahc_* prototype — including it here makes the
@@ -97,6 +98,38 @@ AHC_EXPORT int ahc_dispatch_best(const char* function, int nargs, const int* typ
   }
   if (!st.ok()) return fail(st);
   for (int i = 0; i < nargs; i++) out_type_ids[i] = (int)types[i]->id;
+  return 0;
+}
+
+// The type id of what fn(types...) returns — the chosen kernel's output type — without executing; 0 where the options decide it.
+AHC_EXPORT int ahc_output_type(const char* function, int nargs, const int* type_ids, int* out_type_id, char* err, int64_t cap) {
+  auto fail = [&](const Status& st) { if (err && cap > 0) snprintf(err, (size_t)cap, "%s", st.ToString().c_str()); return (int)st.code; };
+  if (err && cap > 0) err[0] = 0;
+  auto* f = compute::GetFunctionRegistry()->GetFunction(function ? function : "");
+  if (!f) return fail(Status::Make(StatusCode::KeyError, std::string("function '") + (function ? function : "") + "' not found"));
+  Status ar = f->CheckArity((size_t)(nargs < 0 ? 0 : nargs));
+  if (!ar.ok()) return fail(ar);
+  std::vector<const DataType*> types;
+  for (int i = 0; i < nargs; i++) {
+    const DataType* t = GetDataType((Type)type_ids[i]);
+    if (!t) return fail(Status::Make(StatusCode::Invalid, "unknown type id " + std::to_string(type_ids[i])));
+    types.push_back(t);
+  }
+  const exec::KernelSignature* sig = nullptr;
+  Status st;
+  if (f->Kind() == compute::FuncKind::Scalar) {
+    const exec::ScalarKernel* k = nullptr;
+    st = static_cast<compute::ScalarFunction*>(f)->DispatchBest(&types, &k);
+    if (st.ok()) sig = &k->sig;
+  } else if (f->Kind() == compute::FuncKind::Vector) {
+    const exec::VectorKernel* k = nullptr;
+    st = static_cast<compute::VectorFunction*>(f)->DispatchExact(types, &k);
+    if (st.ok()) sig = &k->sig;
+  } else {
+    st = Status::Make(StatusCode::NotImplemented, "meta functions dispatch when they execute");
+  }
+  if (!st.ok()) return fail(st);
+  *out_type_id = sig->out_from_options ? 0 : sig->out_is_first_input ? (types.empty() ? 0 : (int)types[0]->id) : (int)sig->out_type;
   return 0;
 }
 
@@ -257,6 +290,11 @@ AHC_EXPORT int ahc_session_set_option(ahc_session* s, const char* name, int64_t 
     if (value > 2) return Fail(s, Status::Make(StatusCode::Invalid, "option 'select_k_route': 0 (auto), 1 (radix) or 2 (sort)"));
     s->ectx.SelectKRoute = (int)value;
   }
+  else if (n == "string_tile_bytes") {   // the string searches' LDS tile (ah_ctx_set_option): where a test puts the tile borders
+    Session* ss = s->session.get();
+    Status st = ss->FromStatus(ah_ctx_set_option(ss->ctx(), "string_tile_bytes", value));
+    if (!st.ok()) return Fail(s, st);
+  }
   else if (n == "ipc_device_lz4") s->ipc_device_lz4 = value != 0;
   else if (n == "ipc_device_lz4_min_bytes") s->ipc_device_lz4_min_bytes = value;
   else return Fail(s, Status::Make(StatusCode::KeyError, "unknown session option '" + n + "'"));
@@ -337,6 +375,7 @@ AHC_EXPORT int ahc_datum_info(ahc_datum* d, int* kind, int* type_id, int64_t* le
 //   partition_by=<name>,…   order_by=<name>[:asc|desc[:at_end|at_start]],…   functions=row_number|rank|dense_rank|cumulative_<sum|min|max|count>:<name>,…   (WindowOptions)
 //   tiebreaker=min|first|dense   beside sort_keys=… or order=…;null_placement=…                     (RankOptions)
 //   skip_nulls=0|1   start=<type>:<value>|null:<type>   (e.g. start=int64:10, start=double:1.5, start=null:int32)
+//   pattern_hex=<the pattern's bytes, two hex digits each>   ignore_case=false|true                 (MatchSubstringOptions)
 struct ParsedOptions {
   compute::FilterOptions filter;
   compute::TakeOptions take;
@@ -352,6 +391,7 @@ struct ParsedOptions {
   compute::HashJoinOptions hash_join;
   compute::WindowOptions window;
   compute::RankOptions rank;
+  compute::MatchSubstringOptions match;
   const compute::FunctionOptions* pick = nullptr;
 };
 static const struct { const char* name; Type id; } kTypeNames[] = {
@@ -509,6 +549,15 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
         p->pick = &p->window;
       }
       if (k == "tiebreaker") p->rank.Tiebreaker = v;
+      if (k == "pattern_hex") {   // hex: a pattern may hold ';', '=' or bytes that are no UTF-8
+        p->match.PatternGiven = true;
+        p->match.PatternBadHex = v.size() % 2 != 0 || v.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos;
+        p->match.Pattern.clear();
+        if (!p->match.PatternBadHex)
+          for (size_t q = 0; q < v.size(); q += 2) p->match.Pattern.push_back((char)strtoul(v.substr(q, 2).c_str(), nullptr, 16));
+        p->pick = &p->match;
+      }
+      if (k == "ignore_case") { p->match.IgnoreCase = v == "true" || v == "1"; p->pick = &p->match; }
       if (k == "order" || k == "null_placement") {
         if (p->sort.Keys.empty()) p->sort.Keys.push_back(compute::SortKey());
         if (k == "order") p->sort.Keys[0].Order = v == "descending" ? compute::SortOrderDescending : compute::SortOrderAscending;
@@ -536,6 +585,32 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
     }
     pos = end + 1;
   }
+}
+
+// What `function` answers to this options string before anything runs (needs no session and no GPU): the string predicates check
+// their pattern here; every other function accepts.
+static bool IsStringPatternFunction(const std::string& n) {
+  return n == "match_substring" || n == "starts_with" || n == "ends_with" || n == "find_substring" || n == "match_like";
+}
+AHC_EXPORT int ahc_validate_options(const char* function, const char* options, char* err, int64_t cap) {
+  if (err && cap > 0) err[0] = 0;
+  const std::string fname = function ? function : "";
+  Status st;
+  if (!compute::GetFunctionRegistry()->GetFunction(fname)) st = Status::Make(StatusCode::KeyError, "function '" + fname + "' not found");
+  else if (IsStringPatternFunction(fname)) {
+    ParsedOptions po;
+    ParseOptions(options, &po);
+    st = compute::ValidateStringMatchOptions(fname, po.pick);
+  }
+  if (!st.ok() && err && cap > 0) snprintf(err, (size_t)cap, "%s", st.ToString().c_str());
+  return (int)st.code;
+}
+// the LIKE pattern compiled into the program ah_string_like takes (host/like_program.h); → the program's length, -1 when cap is too small
+AHC_EXPORT int64_t ahc_like_compile(const uint8_t* pattern, int64_t pattern_len, uint8_t* out, int64_t cap) {
+  const std::vector<uint8_t> prog = like::Compile(pattern, pattern_len < 0 ? 0 : (size_t)pattern_len);
+  if ((int64_t)prog.size() > cap) return -1;
+  memcpy(out, prog.data(), prog.size());
+  return (int64_t)prog.size();
 }
 
 AHC_EXPORT int ahc_call(ahc_session* s, const char* name, const char* options, int nargs, ahc_datum** args, ahc_datum** out) {

@@ -452,6 +452,8 @@ Status ScalarFunction::Execute(ExecCtx* ctx, const FunctionOptions* opts, const 
     else if (length != a.array->length)
       return Status::Make(StatusCode::Invalid, "array arguments must all be the same length");
   }
+  if (all_scalar && arrays_only)
+    return Status::Make(StatusCode::NotImplemented, "function '" + name_ + "' takes an array or a chunked array, not a scalar");
   if (all_scalar) {
     for (auto& a : args) {
       ArrayDataPtr arr;
@@ -802,6 +804,7 @@ FunctionRegistry* GetFunctionRegistry() {
     RegisterHashJoin(r);
     RegisterWindow(r);
     RegisterConditional(r);
+    RegisterStringMatch(r);
     return r;
   }();
   return reg;

@@ -8,6 +8,9 @@
 //   scalar_bool.go:94-110, selection.go:42-114,618-650, vector_hash.go:61-100}.
 #include <cmath>
 #include "arrowhip_compute.h"
+#include "like_program.h"
+
+#include <dlfcn.h>
 
 #include <algorithm>
 #include <cstring>
@@ -2995,6 +2998,113 @@ void RegisterConditional(FunctionRegistry* reg) {
       k.can_execute_chunkwise = false;   // the carry crosses chunk borders
       fn->AddKernel(std::move(k));
     }
+    reg->AddFunction(fn, false);
+  }
+}
+
+// ---- string predicates: match_substring, starts_with, ends_with, find_substring, match_like, binary_length, utf8_length ----------------
+// No reference analogue (arrow-go has none of them): Arrow C++'s functions and semantics, DESIGN.md §3.17.  One argument, an array or
+// a chunked array (a chunk at a time, like every scalar function); the output's validity is the input's (NullIntersection).  The
+// kernels compute every row, null slots included.
+namespace {
+
+// The four entry points are libarrowhip_strings.so's (include/arrowhip_strings.h), a library beside libarrowhip.so.  It is opened on
+// first use, by name through this library's run path, so that whoever links the host layer needs libarrowhip.so alone; a library
+// that is missing or lacks an entry point is an error of the call — there is no other path.
+struct StringsLib {
+  decltype(&ah_string_match) match = nullptr;
+  decltype(&ah_string_find) find = nullptr;
+  decltype(&ah_string_like) like = nullptr;
+  decltype(&ah_string_length) length = nullptr;
+  std::string error;
+};
+const StringsLib& Strings() {
+  static const StringsLib lib = [] {
+    StringsLib l;
+    void* h = dlopen("libarrowhip_strings.so", RTLD_NOW | RTLD_GLOBAL);
+    if (!h) {
+      const char* e = dlerror();
+      l.error = std::string("libarrowhip_strings.so cannot be loaded: ") + (e ? e : "unknown error");
+      return l;
+    }
+    l.match = (decltype(l.match))dlsym(h, "ah_string_match");
+    l.find = (decltype(l.find))dlsym(h, "ah_string_find");
+    l.like = (decltype(l.like))dlsym(h, "ah_string_like");
+    l.length = (decltype(l.length))dlsym(h, "ah_string_length");
+    if (!l.match || !l.find || !l.like || !l.length) l.error = "libarrowhip_strings.so lacks an entry point of include/arrowhip_strings.h";
+    return l;
+  }();
+  return lib;
+}
+
+enum StringFn { kFnSubstring = AH_STR_SUBSTRING, kFnStartsWith = AH_STR_STARTS_WITH, kFnEndsWith = AH_STR_ENDS_WITH, kFnFind, kFnLike, kFnBinaryLength, kFnUtf8Length };
+
+Status ExecStringMatch(KernelCtx* k, const ExecSpan& b, ExecResult* out, const char* name, int fn) {
+  Session* s = k->session;
+  const bool needs_pattern = fn != kFnBinaryLength && fn != kFnUtf8Length;
+  const MatchSubstringOptions* opts = nullptr;
+  if (needs_pattern) {
+    const FunctionOptions* given = static_cast<const FunctionOptions*>(k->state);
+    AHC_RETURN_NOT_OK(ValidateStringMatchOptions(name, given));
+    opts = static_cast<const MatchSubstringOptions*>(given);
+  }
+  if (out->len == 0) return Status::OK();   // (a scalar argument never gets here: ScalarFunction::arrays_only)
+  const StringsLib& lib = Strings();
+  if (!lib.error.empty()) return Status::Make(StatusCode::Invalid, lib.error);
+  const ArraySpan& in = b.values[0].array;
+  const ByteLayout l = LayoutOf(in);
+  const ah_cmp_operand col{l.offset_width, l.byte_width, l.offsets, l.data, l.offset, 0};
+  const uint8_t* pattern = opts ? (const uint8_t*)opts->Pattern.data() : nullptr;
+  const int64_t m = opts ? (int64_t)opts->Pattern.size() : 0;
+  const int out_width = in.type->id == Type::LARGE_STRING || in.type->id == Type::LARGE_BINARY ? 8 : 4;
+  switch (fn) {
+    case kFnFind:
+      return s->FromStatus(lib.find(s->ctx(), &col, out->len, pattern, m, out_width, out->buffers[1].buf + out->offset * out_width));
+    case kFnLike: {
+      const std::vector<uint8_t> program = like::Compile(pattern, (size_t)m);
+      return s->FromStatus(lib.like(s->ctx(), &col, out->len, IsUtf8(in.type->id) ? 1 : 0, program.data(), (int64_t)program.size(), out->buffers[1].buf, out->offset));
+    }
+    case kFnBinaryLength:
+    case kFnUtf8Length:
+      return s->FromStatus(lib.length(s->ctx(), &col, out->len, fn == kFnUtf8Length ? 1 : 0, out_width, out->buffers[1].buf + out->offset * out_width));
+    default:
+      return s->FromStatus(lib.match(s->ctx(), fn, &col, out->len, pattern, m, out->buffers[1].buf, out->offset));
+  }
+}
+
+}  // namespace
+
+Status ValidateStringMatchOptions(const std::string& function, const FunctionOptions* options) {
+  const MatchSubstringOptions* o = dynamic_cast<const MatchSubstringOptions*>(options);
+  if (!o || !o->PatternGiven) return Status::Make(StatusCode::Invalid, "function '" + function + "' needs the option pattern_hex=<the pattern's bytes in hex>");
+  if (o->PatternBadHex) return Status::Make(StatusCode::Invalid, "function '" + function + "': pattern_hex is not a string of hex byte pairs");
+  if (o->IgnoreCase)
+    return Status::Make(StatusCode::NotImplemented, "function '" + function + "': ignore_case=true is not implemented (Arrow folds Unicode case; an ASCII-only fold would disagree with it)");
+  if (o->Pattern.size() > (size_t)AH_STR_MAX_PATTERN)
+    return Status::Make(StatusCode::NotImplemented, "function '" + function + "': a pattern of " + std::to_string(o->Pattern.size()) + " bytes (at most " +
+                                                        std::to_string(AH_STR_MAX_PATTERN) + ")");
+  return Status::OK();
+}
+
+void RegisterStringMatch(FunctionRegistry* reg) {
+  struct F { const char* name; int fn; };
+  for (F f : {F{"match_substring", kFnSubstring}, F{"starts_with", kFnStartsWith}, F{"ends_with", kFnEndsWith}, F{"find_substring", kFnFind},
+              F{"match_like", kFnLike}, F{"binary_length", kFnBinaryLength}, F{"utf8_length", kFnUtf8Length}}) {
+    auto fn = std::make_shared<ScalarFunction>(f.name, Arity{1, false});
+    std::vector<Type> types = {Type::STRING, Type::LARGE_STRING};
+    if (f.fn != kFnUtf8Length) { types.push_back(Type::BINARY); types.push_back(Type::LARGE_BINARY); }
+    if (f.fn == kFnBinaryLength) types.push_back(Type::FIXED_SIZE_BINARY);
+    for (Type t : types) {
+      exec::ScalarKernel k;
+      k.sig.in_types = {t};
+      k.sig.out_is_first_input = false;
+      const bool large = t == Type::LARGE_STRING || t == Type::LARGE_BINARY;
+      k.sig.out_type = f.fn == kFnFind || f.fn == kFnBinaryLength || f.fn == kFnUtf8Length ? (large ? Type::INT64 : Type::INT32) : Type::BOOL;
+      const F ff = f;
+      k.exec_fn = [ff](KernelCtx* kc, const ExecSpan& b, ExecResult* o) { return ExecStringMatch(kc, b, o, ff.name, ff.fn); };
+      fn->AddKernel(std::move(k));
+    }
+    fn->arrays_only = true;
     reg->AddFunction(fn, false);
   }
 }

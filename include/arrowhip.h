@@ -151,7 +151,9 @@ const char* ah_last_error(ah_ctx* ctx); /* never NULL; owned by ctx */
  * a separate bitmap copy + popcount, 3 one pass for unchecked columns without nulls only — 2 and 3 are measurement switches), "filter_cache" (1: ah_filter_count leaves its tile prefixes for the ah_filter_primitive that
  * follows, dropped by every entry point of THIS context that may write device memory — the default of ah_ctx_create; 0: the fill
  * always recounts — the default of ah_ctx_create_on_stream, where another producer on the shared stream may rewrite the mask
- * between the two calls; set it to 1 there only if nothing else writes the mask in between).  Defaults come from the ARROWHIP_*
+ * between the two calls; set it to 1 there only if nothing else writes the mask in between), "string_tile_bytes" (the string searches:
+ * bytes of the value buffer a workgroup stages per LDS tile, 0 = 16384, else 64 … 32768 — so that a test can put tile borders where
+ * it wants them).  Defaults come from the ARROWHIP_*
  * environment variables of the same names at context creation. */
 int ah_ctx_set_option(ah_ctx* ctx, const char* name, int64_t value);
 const char* ah_version(void);

@@ -113,6 +113,15 @@ int ahc_function_num_kernels(const char* name);
  * the argument types of the chosen kernel (type ids as in ahc_datum_type_id), i.e. the implicit casts the executor would insert.
  * Needs no session and no GPU.  Error text into err. */
 int ahc_dispatch_best(const char* function, int nargs, const int* type_ids, int* out_type_ids, char* err, int64_t cap);
+/* the type id of what the kernel chosen as above returns (0 where the call's options decide it); no session, no GPU */
+int ahc_output_type(const char* function, int nargs, const int* type_ids, int* out_type_id, char* err, int64_t cap);
+/* what `function` answers to an options string ("key=value;…") before anything runs: the string predicates (match_substring,
+ * starts_with, ends_with, find_substring, match_like) check pattern_hex / ignore_case here, every other function accepts.  Returns
+ * the status code (0 = fine), the text into err; no session, no GPU */
+int ahc_validate_options(const char* function, const char* options, char* err, int64_t cap);
+/* a SQL LIKE pattern compiled into the segment program ah_string_like takes (include/arrowhip.h; `%`, `_`, `\` as in Arrow C++'s
+ * match_like) → the program's length in bytes, -1 when it does not fit `cap`.  A plain host function */
+int64_t ahc_like_compile(const uint8_t* pattern, int64_t pattern_len, uint8_t* out, int64_t cap);
 /* AddAlias / AddFunction(allowOverwrite) on the session's child registry (registry.go:69-73, 97-135) */
 int ahc_registry_add_alias(ahc_session* s, const char* alias, const char* existing, int allow_overwrite);
 
