@@ -300,6 +300,33 @@ def _load_strings() -> C.CDLL:
 
 strings_lib = _load_strings()
 
+# the string transforms: libarrowhip_string_transform.so (include/arrowhip_string_transform.h), a third library on the same ah_ctx
+STRING_TRANSFORM_LIB_PATH = os.path.join(_HERE, "libarrowhip_string_transform.so")
+STRING_TRANSFORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "arrowhip_string_transform.h")
+STX_WHOLE, STX_SLICE_BYTES, STX_SLICE_CODEPOINTS, STX_TRIM_BYTES, STX_TRIM_CODEPOINTS = 0, 1, 2, 3, 4
+STX_LEFT, STX_RIGHT = 1, 2
+_STRING_TRANSFORM_SIGS = {
+    "ah_string_ranges": [_vp, _int, _i64, _i64, _int, _int, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _pi64],
+    "ah_string_gather": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+}
+
+
+def _load_string_transform() -> C.CDLL:
+    if not os.path.exists(STRING_TRANSFORM_LIB_PATH):
+        raise ImportError(f"{STRING_TRANSFORM_LIB_PATH} is missing — build() makes it beside libarrowhip.so. There is no CPU fallback.")
+    tl = C.CDLL(STRING_TRANSFORM_LIB_PATH, mode=C.RTLD_GLOBAL)
+    missing = [s for s in declared_symbols(STRING_TRANSFORM_HEADER_PATH) if not hasattr(tl, s)]
+    if missing:
+        raise ImportError(f"libarrowhip_string_transform.so does not export symbols declared in arrowhip_string_transform.h: {missing}")
+    for name, args in _STRING_TRANSFORM_SIGS.items():
+        fn = getattr(tl, name)
+        fn.argtypes = args
+        fn.restype = _int
+    return tl
+
+
+string_transform_lib = _load_string_transform()
+
 
 def check(ctx_handle, status: int) -> None:
     if status == AH_OK:

@@ -319,6 +319,19 @@ def pattern_options(pattern, ignore_case: bool = False) -> str:
     return "pattern_hex=" + pat.hex() + (";ignore_case=true" if ignore_case else "")
 
 
+def slice_options(start: int, stop=None, step: int = 1) -> str:
+    """The options string of utf8_slice_codeunits / binary_slice: "start=<int64>[;stop=<int64>][;step=<int64>]" — stop None: to the
+    end of the row; a step other than 1 is written as it is, and the functions refuse it with ErrNotImplemented."""
+    return "start=%d" % int(start) + ("" if stop is None else ";stop=%d" % int(stop)) + ("" if step == 1 else ";step=%d" % int(step))
+
+
+def trim_options(characters) -> str:
+    """The options string of ascii_trim / _ltrim / _rtrim and utf8_trim / _ltrim / _rtrim: "characters_hex=<the characters' bytes
+    in hex>" (str or bytes; may be empty)."""
+    chars = characters.encode() if isinstance(characters, str) else bytes(characters)
+    return "characters_hex=" + chars.hex()
+
+
 def inspect_substrait(buf) -> str:
     """What the Substrait reader understood of a serialized ExtendedExpression, without a device (ahc_substrait_inspect):
     "name:type,…|output_name=expression|…"; raises the reference's error class for a message the reader refuses as a whole."""
@@ -855,6 +868,64 @@ class Session:
         """call_function("utf8_length", [values]): Int32 / Int64, the code points of a String / LargeString row = its bytes that are not
         10xxxxxx continuation bytes (which is also what it counts on bytes that are no valid UTF-8)."""
         return self.call_function("utf8_length", [values], keep_on_device=keep_on_device)
+
+    # -- string transforms (Arrow C++'s semantics; values a String / LargeString — binary_slice: Binary / LargeBinary — Array, ChunkedArray
+    # or DeviceArray; the output has the input's type and validity, a null row has length 0).  Every result is one sub-range of the
+    # row's bytes: ah_string_ranges + ah_string_gather of libarrowhip_string_transform.so.
+    def ascii_upper(self, values, keep_on_device: bool = False):
+        """call_function("ascii_upper", [values]): the bytes a-z become A-Z, every other byte (≥ 0x80 included) stays."""
+        return self.call_function("ascii_upper", [values], keep_on_device=keep_on_device)
+
+    def ascii_lower(self, values, keep_on_device: bool = False):
+        """call_function("ascii_lower", [values]): the bytes A-Z become a-z, every other byte stays."""
+        return self.call_function("ascii_lower", [values], keep_on_device=keep_on_device)
+
+    def utf8_slice_codeunits(self, values, start: int, stop=None, step: int = 1, keep_on_device: bool = False):
+        """call_function("utf8_slice_codeunits", [values], "start=…;stop=…"): Python's row[start:stop] over the row's code points (a
+        byte that is not 10xxxxxx and the continuation bytes behind it; nothing is validated).  stop None: to the end of the row.
+        step other than 1 is refused (ErrNotImplemented)."""
+        return self.call_function("utf8_slice_codeunits", [values], slice_options(start, stop, step), keep_on_device=keep_on_device)
+
+    def binary_slice(self, values, start: int, stop=None, step: int = 1, keep_on_device: bool = False):
+        """call_function("binary_slice", [values], "start=…;stop=…"): Python's row[start:stop] over the bytes of a Binary / LargeBinary row."""
+        return self.call_function("binary_slice", [values], slice_options(start, stop, step), keep_on_device=keep_on_device)
+
+    def ascii_trim(self, values, characters, keep_on_device: bool = False):
+        """call_function("ascii_trim", [values], "characters_hex=…"): the bytes of `characters` (a set of bytes) removed from both ends."""
+        return self.call_function("ascii_trim", [values], trim_options(characters), keep_on_device=keep_on_device)
+
+    def ascii_ltrim(self, values, characters, keep_on_device: bool = False):
+        """… removed from the row's start."""
+        return self.call_function("ascii_ltrim", [values], trim_options(characters), keep_on_device=keep_on_device)
+
+    def ascii_rtrim(self, values, characters, keep_on_device: bool = False):
+        """… removed from the row's end."""
+        return self.call_function("ascii_rtrim", [values], trim_options(characters), keep_on_device=keep_on_device)
+
+    def ascii_trim_whitespace(self, values, keep_on_device: bool = False):
+        """call_function("ascii_trim_whitespace", [values]): the bytes 9-13 and 32 removed from both ends."""
+        return self.call_function("ascii_trim_whitespace", [values], keep_on_device=keep_on_device)
+
+    def ascii_ltrim_whitespace(self, values, keep_on_device: bool = False):
+        """… removed from the row's start."""
+        return self.call_function("ascii_ltrim_whitespace", [values], keep_on_device=keep_on_device)
+
+    def ascii_rtrim_whitespace(self, values, keep_on_device: bool = False):
+        """… removed from the row's end."""
+        return self.call_function("ascii_rtrim_whitespace", [values], keep_on_device=keep_on_device)
+
+    def utf8_trim(self, values, characters, keep_on_device: bool = False):
+        """call_function("utf8_trim", [values], "characters_hex=…"): the code points of `characters` (valid UTF-8; a set of code
+        points) removed from both ends."""
+        return self.call_function("utf8_trim", [values], trim_options(characters), keep_on_device=keep_on_device)
+
+    def utf8_ltrim(self, values, characters, keep_on_device: bool = False):
+        """… removed from the row's start."""
+        return self.call_function("utf8_ltrim", [values], trim_options(characters), keep_on_device=keep_on_device)
+
+    def utf8_rtrim(self, values, characters, keep_on_device: bool = False):
+        """… removed from the row's end."""
+        return self.call_function("utf8_rtrim", [values], trim_options(characters), keep_on_device=keep_on_device)
 
     def hash_join(self, left, right, keys, right_keys=None, join_type: str = "inner", keep_on_device: bool = False):
         """call_function("hash_join", [left, right], "left_keys=…;right_keys=…;type=…"): the two record batches joined on their key

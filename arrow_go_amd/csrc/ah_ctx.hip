@@ -6,6 +6,7 @@
 // ah_host_alloc_pinned gives Arrow buffers that hipMemcpyAsync can DMA directly.
 #include <chrono>
 #include "ah_common.h"
+#include "ah_arena.h"
 
 static const char* kVersion = "arrowhip 0.1 (gfx950)";
 
@@ -235,49 +236,14 @@ int ah_mailbox_read2(ah_ctx* c, const unsigned long long* dev_words, int nwords,
   return AH_OK;
 }
 
-int ah_scratch_reserve(ah_ctx* c, size_t nbytes, void** out) {
-  if (nbytes > c->scratch_bytes) {
-    // the old block may still be in use by enqueued kernels
-    AH_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->scratch) AH_HIP(c, hipFree(c->scratch));
-    c->scratch = nullptr;
-    c->scratch_bytes = 0;
-    size_t want = (nbytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    AH_HIP(c, hipMalloc(&c->scratch, want));
-    c->scratch_bytes = want;
-  }
-  *out = c->scratch;
-  return AH_OK;
-}
+// the three grow-only arenas: one growth policy (ah_arena.h), which the sibling libraries on this context use as well
+int ah_scratch_reserve(ah_ctx* c, size_t nbytes, void** out) { return ah_arena_reserve(c, &c->scratch, &c->scratch_bytes, nbytes, nullptr, out); }
 
 int ah_temp_reserve(ah_ctx* c, size_t nbytes, void** out, bool* out_of_memory) {
-  if (out_of_memory) *out_of_memory = false;
-  if (nbytes > c->temp_bytes) {
-    AH_HIP(c, hipStreamSynchronize(c->stream));  // the old block may still be in use by enqueued kernels
-    if (c->temp) AH_HIP(c, hipFree(c->temp));
-    c->temp = nullptr;
-    c->temp_bytes = 0;
-    size_t want = (nbytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    if (hipMalloc(&c->temp, want) != hipSuccess) { (void)hipGetLastError(); if (out_of_memory) *out_of_memory = true; return ah_fail(c, AH_EHIP, "out of device memory (%zu bytes of temporaries)", want); }
-    c->temp_bytes = want;
-  }
-  *out = c->temp;
-  return AH_OK;
+  return ah_arena_reserve(c, &c->temp, &c->temp_bytes, nbytes, "temporaries", out, out_of_memory);
 }
 
-int ah_pack_reserve(ah_ctx* c, size_t nbytes, void** out) {
-  if (nbytes > c->pack_bytes) {
-    AH_HIP(c, hipStreamSynchronize(c->stream));  // the old block may still be in use by enqueued kernels
-    if (c->pack) AH_HIP(c, hipFree(c->pack));
-    c->pack = nullptr;
-    c->pack_bytes = 0;
-    size_t want = (nbytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    if (hipMalloc(&c->pack, want) != hipSuccess) { (void)hipGetLastError(); return ah_fail(c, AH_EHIP, "out of device memory (%zu bytes of packed keys)", want); }
-    c->pack_bytes = want;
-  }
-  *out = c->pack;
-  return AH_OK;
-}
+int ah_pack_reserve(ah_ctx* c, size_t nbytes, void** out) { return ah_arena_reserve(c, &c->pack, &c->pack_bytes, nbytes, "packed keys", out); }
 
 AH_EXPORT int ah_buf_alloc(ah_ctx* c, size_t nbytes, void** dptr_host) {
   AH_ENTER_KEEP(c);

@@ -30,6 +30,7 @@
 // global memory.  Code-point stepping for `_` on UTF-8 columns is part of the segment walk (seg_fwd / seg_rev).
 #include "../ah_common.h"
 #include "../ah_bytes.h"
+#include "../ah_arena.h"
 #include "../../../include/arrowhip_strings.h"
 
 namespace {
@@ -519,20 +520,9 @@ int check_bits(ah_ctx* c, const char* fn, const uint8_t* out_bits, int64_t out_b
 }
 
 // The context's grow-only scratch arena, as ah_scratch_reserve (ah_ctx.hip) hands it out — that function is internal to
-// libarrowhip.so, and this file is a library of its own on the same ah_ctx.  Contents are undefined after the call.
-int scratch_reserve(ah_ctx* c, size_t nbytes, void** out) {
-  if (nbytes > c->scratch_bytes) {
-    AH_HIP(c, hipStreamSynchronize(c->stream));   // the old block may still be in use by enqueued kernels
-    if (c->scratch) AH_HIP(c, hipFree(c->scratch));
-    c->scratch = nullptr;
-    c->scratch_bytes = 0;
-    const size_t want = (nbytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    AH_HIP(c, hipMalloc(&c->scratch, want));
-    c->scratch_bytes = want;
-  }
-  *out = c->scratch;
-  return AH_OK;
-}
+// libarrowhip.so, and this file is a library of its own on the same ah_ctx; both grow the arena through ah_arena.h.  Contents are
+// undefined after the call.
+int scratch_reserve(ah_ctx* c, size_t nbytes, void** out) { return ah_arena_reserve(c, &c->scratch, &c->scratch_bytes, nbytes, nullptr, out); }
 
 // the pattern as zero-padded 8-byte words on the device, in front of `extra` more bytes of the scratch arena
 int upload_pattern(ah_ctx* c, const uint8_t* pattern, int m, size_t extra, unsigned long long** pat, uint8_t** rest) {

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from ._native import lib, strings_lib, check
+from ._native import lib, strings_lib, string_transform_lib, check
 
 
 def _ptr(x) -> Optional[int]:
@@ -658,6 +658,29 @@ class Context:
         """out[i] = the bytes of row i, or (utf8) its bytes that are not 10xxxxxx continuation bytes (ah_string_length)"""
         col = self._column(column)
         check(self.handle, strings_lib.ah_string_length(self.handle, C.byref(col), n, int(bool(utf8)), out_width, _ptr(out)))
+
+    # ---- string transforms (libarrowhip_string_transform.so: csrc/string_transform/ah_string_transform.hip, include/arrowhip_string_transform.h).
+    # column as above, offset_width 4 / 8; out_starts / out_offsets hold values of that width.
+    def string_ranges(self, op: int, column, n: int, out_starts, out_offsets, *, start: int = 0, stop=None, sides: int = 3, chars: bytes = b"",
+                      valid=None, valid_offset: int = 0) -> int:
+        """op 0 the whole row, 1 / 2 row[start:stop] over bytes / code points (stop None: to the row's end), 3 / 4 the bytes / code
+        points of `chars` trimmed from `sides` (1 left, 2 right): out_starts[i] = where row i's result starts in the column's data,
+        out_offsets[0 … n] the output offsets; a row whose validity bit (valid_offset + i of `valid`) is clear has length 0.
+        Returns the byte total — the call's one synchronisation (ah_string_ranges)"""
+        col = self._column(column)
+        total = C.c_int64(0)
+        check(self.handle, string_transform_lib.ah_string_ranges(self.handle, op, start, 0 if stop is None else stop, int(stop is not None), sides,
+                                                                 C.c_char_p(bytes(chars)), len(chars), C.byref(col), _ptr(valid), valid_offset, n,
+                                                                 _ptr(out_starts), _ptr(out_offsets), C.byref(total)))
+        return total.value
+
+    def string_gather(self, column, starts, out_offsets, n: int, out_data, map: Optional[bytes] = None) -> None:
+        """out_data[out_offsets[i] … out_offsets[i + 1]) = the column's data bytes from starts[i] on, through the 256-byte `map` where
+        one is given; no synchronisation (ah_string_gather)"""
+        col = self._column(column)
+        assert map is None or len(map) == 256
+        check(self.handle, string_transform_lib.ah_string_gather(self.handle, C.byref(col), _ptr(starts), _ptr(out_offsets), n,
+                                                                 None if map is None else C.c_char_p(bytes(map)), _ptr(out_data)))
 
     def compare_decimal(self, cmpop: int, left, right, n: int, out_bits, out_bit_offset: int = 0) -> None:
         """left / right: (width 16 | 32, data, off, broadcast, scale-up exponent)"""

@@ -33,6 +33,7 @@
 
 #include "../../include/arrowhip.h"
 #include "../../include/arrowhip_strings.h"   // the string predicates: libarrowhip_strings.so, on the same ah_ctx
+#include "../../include/arrowhip_string_transform.h"   // the string transforms: libarrowhip_string_transform.so, on the same ah_ctx
 
 namespace arrowhip {
 
@@ -368,6 +369,24 @@ struct MatchSubstringOptions : FunctionOptions {
 };
 // what the pattern functions answer to their options before anything runs (also ahc_validate_options, without a device)
 Status ValidateStringMatchOptions(const std::string& function, const FunctionOptions* options);
+// utf8_slice_codeunits, binary_slice: Arrow C++'s SliceOptions.  start=<int64> (required), stop=<int64> (absent: to the end of the
+// row), step=1 — any other step is refused: its result is not one sub-range of the row.  BadInteger names a key whose value is no int64.
+struct SliceOptions : FunctionOptions {
+  int64_t Start = 0, Stop = 0, Step = 1;
+  bool StartGiven = false, StopGiven = false;
+  std::string BadInteger;
+  const char* TypeName() const override { return "SliceOptions"; }
+};
+// ascii_trim / _ltrim / _rtrim (a set of bytes) and utf8_trim / _ltrim / _rtrim (a set of code points, valid UTF-8): Arrow C++'s
+// TrimOptions, the characters as hex (characters_hex=…) for the reason the patterns are
+struct TrimOptions : FunctionOptions {
+  std::string Characters;
+  bool Given = false, BadHex = false;
+  const char* TypeName() const override { return "TrimOptions"; }
+};
+// what the string transforms answer to their options before anything runs (also ahc_validate_options, without a device)
+bool IsStringTransformFunction(const std::string& function);
+Status ValidateStringTransformOptions(const std::string& function, const FunctionOptions* options);
 struct CompareFilterSumOptions : FunctionOptions { int cmpop = AH_CMP_GT; const char* TypeName() const override { return "CompareFilterSumOptions"; } };
 
 // compute.Datum (datum.go:35-40): array or scalar
@@ -572,6 +591,7 @@ void RegisterHashJoin(FunctionRegistry* reg);
 void RegisterWindow(FunctionRegistry* reg);
 void RegisterConditional(FunctionRegistry* reg);
 void RegisterStringMatch(FunctionRegistry* reg);
+void RegisterStringTransform(FunctionRegistry* reg);
 
 // ---- compute.Expression (arrow/compute/expression.go:59-78,596-620) and its executor
 // (arrow/compute/exprs/exec.go:440-700 ExecuteScalarExpression / executeScalarBatch) --------

@@ -376,6 +376,8 @@ AHC_EXPORT int ahc_datum_info(ahc_datum* d, int* kind, int* type_id, int64_t* le
 //   tiebreaker=min|first|dense   beside sort_keys=… or order=…;null_placement=…                     (RankOptions)
 //   skip_nulls=0|1   start=<type>:<value>|null:<type>   (e.g. start=int64:10, start=double:1.5, start=null:int32)
 //   pattern_hex=<the pattern's bytes, two hex digits each>   ignore_case=false|true                 (MatchSubstringOptions)
+//   start=<int64>   stop=<int64>   step=1                                                           (SliceOptions)
+//   characters_hex=<the characters' bytes, two hex digits each>                                     (TrimOptions)
 struct ParsedOptions {
   compute::FilterOptions filter;
   compute::TakeOptions take;
@@ -392,8 +394,20 @@ struct ParsedOptions {
   compute::WindowOptions window;
   compute::RankOptions rank;
   compute::MatchSubstringOptions match;
+  compute::SliceOptions slice;
+  compute::TrimOptions trim;
   const compute::FunctionOptions* pick = nullptr;
 };
+// an int64 in decimal with an optional sign, nothing else
+static bool ParseInt64Text(const std::string& v, int64_t* out) {
+  const size_t d0 = !v.empty() && (v[0] == '-' || v[0] == '+') ? 1 : 0;
+  if (v.size() <= d0 || v.size() > d0 + 19 || v.find_first_not_of("0123456789", d0) != std::string::npos) return false;
+  errno = 0;
+  const long long x = strtoll(v.c_str(), nullptr, 10);
+  if (errno == ERANGE) return false;
+  *out = (int64_t)x;
+  return true;
+}
 static const struct { const char* name; Type id; } kTypeNames[] = {
     {"uint8", Type::UINT8}, {"int8", Type::INT8}, {"uint16", Type::UINT16}, {"int16", Type::INT16}, {"uint32", Type::UINT32},
     {"int32", Type::INT32}, {"uint64", Type::UINT64}, {"int64", Type::INT64}, {"float", Type::FLOAT32}, {"double", Type::FLOAT64}};
@@ -558,6 +572,21 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
         p->pick = &p->match;
       }
       if (k == "ignore_case") { p->match.IgnoreCase = v == "true" || v == "1"; p->pick = &p->match; }
+      if (k == "start" || k == "stop" || k == "step") {   // the slices (start is also the cumulative functions' key: the function's name picks, below)
+        int64_t x = 0;
+        if (!ParseInt64Text(v, &x)) { if (p->slice.BadInteger.empty()) p->slice.BadInteger = k; }
+        else if (k == "start") { p->slice.Start = x; p->slice.StartGiven = true; }
+        else if (k == "stop") { p->slice.Stop = x; p->slice.StopGiven = true; }
+        else p->slice.Step = x;
+      }
+      if (k == "characters_hex") {   // hex, as pattern_hex
+        p->trim.Given = true;
+        p->trim.BadHex = v.size() % 2 != 0 || v.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos;
+        p->trim.Characters.clear();
+        if (!p->trim.BadHex)
+          for (size_t q = 0; q < v.size(); q += 2) p->trim.Characters.push_back((char)strtoul(v.substr(q, 2).c_str(), nullptr, 16));
+        p->pick = &p->trim;
+      }
       if (k == "order" || k == "null_placement") {
         if (p->sort.Keys.empty()) p->sort.Keys.push_back(compute::SortKey());
         if (k == "order") p->sort.Keys[0].Order = v == "descending" ? compute::SortOrderDescending : compute::SortOrderAscending;
@@ -589,6 +618,7 @@ static void ParseOptions(const char* text, ParsedOptions* p) {
 
 // What `function` answers to this options string before anything runs (needs no session and no GPU): the string predicates check
 // their pattern here; every other function accepts.
+static bool IsSliceFunction(const std::string& n) { return n == "utf8_slice_codeunits" || n == "binary_slice"; }
 static bool IsStringPatternFunction(const std::string& n) {
   return n == "match_substring" || n == "starts_with" || n == "ends_with" || n == "find_substring" || n == "match_like";
 }
@@ -601,6 +631,10 @@ AHC_EXPORT int ahc_validate_options(const char* function, const char* options, c
     ParsedOptions po;
     ParseOptions(options, &po);
     st = compute::ValidateStringMatchOptions(fname, po.pick);
+  } else if (compute::IsStringTransformFunction(fname)) {
+    ParsedOptions po;
+    ParseOptions(options, &po);
+    st = compute::ValidateStringTransformOptions(fname, IsSliceFunction(fname) ? &po.slice : po.pick);
   }
   if (!st.ok() && err && cap > 0) snprintf(err, (size_t)cap, "%s", st.ToString().c_str());
   return (int)st.code;
@@ -626,6 +660,7 @@ AHC_EXPORT int ahc_call(ahc_session* s, const char* name, const char* options, i
     po.pick = &po.select_k;
   }
   if (fname == "window") po.pick = &po.window;   // also without options: the refusal is window's
+  if (IsSliceFunction(fname)) po.pick = &po.slice;   // (start= is also the cumulative functions' key)
   if (fname == "rank") {   // tiebreaker beside either spelling of the sort keys
     po.rank.Keys = po.sort.Keys;
     if (po.rank.Keys.empty()) po.rank.Keys.push_back(compute::SortKey());

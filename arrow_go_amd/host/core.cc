@@ -805,6 +805,7 @@ FunctionRegistry* GetFunctionRegistry() {
     RegisterWindow(r);
     RegisterConditional(r);
     RegisterStringMatch(r);
+    RegisterStringTransform(r);
     return r;
   }();
   return reg;

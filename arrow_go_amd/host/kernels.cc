@@ -3109,5 +3109,170 @@ void RegisterStringMatch(FunctionRegistry* reg) {
   }
 }
 
+// ---- string transforms: ascii_upper / ascii_lower, utf8_slice_codeunits, binary_slice, the nine trims ------------------------------------
+// No reference analogue (arrow-go has none of them): Arrow C++'s functions and semantics, DESIGN.md §3.18.  The result of every row is
+// one contiguous sub-range of the row's bytes (the case mappings: the whole row through a byte map), so one pair of entry points
+// serves all thirteen: ah_string_ranges (source starts, output offsets, the byte total — the call's one synchronisation), the
+// allocation, ah_string_gather.  The output's validity is the input's (NullIntersection); a null row has length 0.
+namespace {
+
+// libarrowhip_string_transform.so (include/arrowhip_string_transform.h), opened on the first transform call as Strings() opens its
+// library: a library that is missing or lacks an entry point is an error of the call — there is no other path.
+struct StringTransformLib {
+  decltype(&ah_string_ranges) ranges = nullptr;
+  decltype(&ah_string_gather) gather = nullptr;
+  std::string error;
+};
+const StringTransformLib& StringTransform() {
+  static const StringTransformLib lib = [] {
+    StringTransformLib l;
+    void* h = dlopen("libarrowhip_string_transform.so", RTLD_NOW | RTLD_GLOBAL);
+    if (!h) {
+      const char* e = dlerror();
+      l.error = std::string("libarrowhip_string_transform.so cannot be loaded: ") + (e ? e : "unknown error");
+      return l;
+    }
+    l.ranges = (decltype(l.ranges))dlsym(h, "ah_string_ranges");
+    l.gather = (decltype(l.gather))dlsym(h, "ah_string_gather");
+    if (!l.ranges || !l.gather) l.error = "libarrowhip_string_transform.so lacks an entry point of include/arrowhip_string_transform.h";
+    return l;
+  }();
+  return lib;
+}
+
+enum TransformChars { kCharsNone, kCharsBytes, kCharsCodePoints, kCharsWhitespace };
+enum TransformMap { kMapNone, kMapUpper, kMapLower };
+struct TransformFn { const char* name; int op, sides, chars, map; bool strings; };   // strings: String / LargeString, else Binary / LargeBinary
+const TransformFn kTransformFns[] = {
+    {"ascii_upper", AH_STX_WHOLE, 0, kCharsNone, kMapUpper, true},
+    {"ascii_lower", AH_STX_WHOLE, 0, kCharsNone, kMapLower, true},
+    {"utf8_slice_codeunits", AH_STX_SLICE_CODEPOINTS, 0, kCharsNone, kMapNone, true},
+    {"binary_slice", AH_STX_SLICE_BYTES, 0, kCharsNone, kMapNone, false},
+    {"ascii_trim", AH_STX_TRIM_BYTES, AH_STX_LEFT | AH_STX_RIGHT, kCharsBytes, kMapNone, true},
+    {"ascii_ltrim", AH_STX_TRIM_BYTES, AH_STX_LEFT, kCharsBytes, kMapNone, true},
+    {"ascii_rtrim", AH_STX_TRIM_BYTES, AH_STX_RIGHT, kCharsBytes, kMapNone, true},
+    {"ascii_trim_whitespace", AH_STX_TRIM_BYTES, AH_STX_LEFT | AH_STX_RIGHT, kCharsWhitespace, kMapNone, true},
+    {"ascii_ltrim_whitespace", AH_STX_TRIM_BYTES, AH_STX_LEFT, kCharsWhitespace, kMapNone, true},
+    {"ascii_rtrim_whitespace", AH_STX_TRIM_BYTES, AH_STX_RIGHT, kCharsWhitespace, kMapNone, true},
+    {"utf8_trim", AH_STX_TRIM_CODEPOINTS, AH_STX_LEFT | AH_STX_RIGHT, kCharsCodePoints, kMapNone, true},
+    {"utf8_ltrim", AH_STX_TRIM_CODEPOINTS, AH_STX_LEFT, kCharsCodePoints, kMapNone, true},
+    {"utf8_rtrim", AH_STX_TRIM_CODEPOINTS, AH_STX_RIGHT, kCharsCodePoints, kMapNone, true},
+};
+const TransformFn* TransformByName(const std::string& name) {
+  for (const TransformFn& f : kTransformFns)
+    if (name == f.name) return &f;
+  return nullptr;
+}
+
+// RFC 3629: no overlong forms, no surrogates, nothing above U+10FFFF
+bool ValidUtf8(const std::string& s) {
+  for (size_t i = 0; i < s.size();) {
+    const unsigned char b = (unsigned char)s[i];
+    const int len = b < 0x80 ? 1 : (b & 0xE0) == 0xC0 ? 2 : (b & 0xF0) == 0xE0 ? 3 : (b & 0xF8) == 0xF0 ? 4 : 0;
+    if (!len || i + len > s.size()) return false;
+    unsigned cp = len == 1 ? b : b & (0xFF >> (len + 1));
+    for (int j = 1; j < len; j++) {
+      const unsigned char c = (unsigned char)s[i + j];
+      if ((c & 0xC0) != 0x80) return false;
+      cp = (cp << 6) | (c & 0x3F);
+    }
+    static const unsigned least[5] = {0, 0, 0x80, 0x800, 0x10000};
+    if (cp < least[len] || cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF)) return false;
+    i += len;
+  }
+  return true;
+}
+
+Status ExecStringTransform(KernelCtx* k, const ExecSpan& b, ExecResult* out, const TransformFn& f) {
+  Session* s = k->session;
+  const FunctionOptions* given = static_cast<const FunctionOptions*>(k->state);
+  AHC_RETURN_NOT_OK(ValidateStringTransformOptions(f.name, given));
+  const ArraySpan& in = b.values[0].array;
+  const int ow = out->type->bit_width / 8;
+  const int64_t n = out->len;
+  BufferPtr ob, db, sb;
+  AHC_RETURN_NOT_OK(k->Allocate((n + 1) * ow, &ob));   // (zeroed: the lone closing offset of an empty chunk)
+  out->buffers[1].WrapBuffer(ob);
+  if (n == 0) {   // (a scalar argument never gets here: ScalarFunction::arrays_only)
+    AHC_RETURN_NOT_OK(k->Allocate(0, &db));
+    out->buffers[2].WrapBuffer(db);
+    return Status::OK();
+  }
+  const StringTransformLib& lib = StringTransform();
+  if (!lib.error.empty()) return Status::Make(StatusCode::Invalid, lib.error);
+  int64_t start = 0, stop = 0;
+  int has_stop = 0;
+  std::string chars;
+  if (f.op == AH_STX_SLICE_BYTES || f.op == AH_STX_SLICE_CODEPOINTS) {
+    const SliceOptions* o = static_cast<const SliceOptions*>(given);
+    start = o->Start;
+    stop = o->Stop;
+    has_stop = o->StopGiven ? 1 : 0;
+  } else if (f.chars == kCharsWhitespace) {
+    chars = "\t\n\v\f\r ";
+  } else if (f.chars != kCharsNone) {
+    chars = static_cast<const TrimOptions*>(given)->Characters;
+  }
+  uint8_t map[256];
+  for (int c = 0; c < 256; c++)
+    map[c] = (uint8_t)(f.map == kMapUpper && c >= 'a' && c <= 'z' ? c - 32 : f.map == kMapLower && c >= 'A' && c <= 'Z' ? c + 32 : c);
+  const ByteLayout l = LayoutOf(in);
+  const ah_cmp_operand col{l.offset_width, l.byte_width, l.offsets, l.data, l.offset, 0};
+  const uint8_t* valid = in.MayHaveNulls() ? in.buffers[0].buf : nullptr;
+  AHC_RETURN_NOT_OK(k->Allocate(n * ow, &sb, /*zero_all=*/false));
+  int64_t total = 0;
+  AHC_RETURN_NOT_OK(s->FromStatus(lib.ranges(s->ctx(), f.op, start, stop, has_stop, f.sides, (const uint8_t*)chars.data(), (int64_t)chars.size(), &col, valid,
+                                             in.offset, n, sb->dptr, ob->dptr, &total)));
+  AHC_RETURN_NOT_OK(k->Allocate(total, &db, /*zero_all=*/false));
+  out->buffers[2].WrapBuffer(db);
+  if (total == 0) return Status::OK();
+  return s->FromStatus(lib.gather(s->ctx(), &col, sb->dptr, ob->dptr, n, f.map == kMapNone ? nullptr : map, (uint8_t*)db->dptr));
+}
+
+}  // namespace
+
+bool IsStringTransformFunction(const std::string& function) { return TransformByName(function) != nullptr; }
+
+Status ValidateStringTransformOptions(const std::string& function, const FunctionOptions* options) {
+  const TransformFn* f = TransformByName(function);
+  if (!f) return Status::Make(StatusCode::KeyError, "function '" + function + "' not found");
+  if (f->op == AH_STX_SLICE_BYTES || f->op == AH_STX_SLICE_CODEPOINTS) {
+    const SliceOptions* o = dynamic_cast<const SliceOptions*>(options);
+    if (o && !o->BadInteger.empty()) return Status::Make(StatusCode::Invalid, "function '" + function + "': " + o->BadInteger + " is not an int64");
+    if (!o || !o->StartGiven) return Status::Make(StatusCode::Invalid, "function '" + function + "' needs the option start=<int64>");
+    if (o->Step == 0) return Status::Make(StatusCode::Invalid, "function '" + function + "': slice step cannot be zero");
+    if (o->Step != 1)
+      return Status::Make(StatusCode::NotImplemented, "function '" + function + "': step=" + std::to_string(o->Step) + " is not implemented (the result must be one sub-range of the row: step=1)");
+    return Status::OK();
+  }
+  if (f->chars == kCharsBytes || f->chars == kCharsCodePoints) {
+    const TrimOptions* o = dynamic_cast<const TrimOptions*>(options);
+    if (!o || !o->Given) return Status::Make(StatusCode::Invalid, "function '" + function + "' needs the option characters_hex=<the characters' bytes in hex>");
+    if (o->BadHex) return Status::Make(StatusCode::Invalid, "function '" + function + "': characters_hex is not a string of hex byte pairs");
+    if (o->Characters.size() > (size_t)AH_STX_MAX_CHARS)
+      return Status::Make(StatusCode::NotImplemented, "function '" + function + "': characters of " + std::to_string(o->Characters.size()) + " bytes (at most " +
+                                                          std::to_string(AH_STX_MAX_CHARS) + ")");
+    if (f->chars == kCharsCodePoints && !ValidUtf8(o->Characters)) return Status::Make(StatusCode::Invalid, "function '" + function + "': the characters are not valid UTF-8");
+  }
+  return Status::OK();
+}
+
+void RegisterStringTransform(FunctionRegistry* reg) {
+  for (const TransformFn& f : kTransformFns) {
+    auto fn = std::make_shared<ScalarFunction>(f.name, Arity{1, false});
+    const std::vector<Type> types = f.strings ? std::vector<Type>{Type::STRING, Type::LARGE_STRING} : std::vector<Type>{Type::BINARY, Type::LARGE_BINARY};
+    for (Type t : types) {
+      exec::ScalarKernel k;
+      k.sig.in_types = {t};   // (the output type is the input's: out_is_first_input)
+      k.mem_alloc = exec::MemAlloc::MemNoPrealloc;
+      const TransformFn* ff = &f;
+      k.exec_fn = [ff](KernelCtx* kc, const ExecSpan& b, ExecResult* o) { return ExecStringTransform(kc, b, o, *ff); };
+      fn->AddKernel(std::move(k));
+    }
+    fn->arrays_only = true;
+    reg->AddFunction(fn, false);
+  }
+}
+
 }  // namespace compute
 }  // namespace arrowhip

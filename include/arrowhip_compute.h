@@ -116,7 +116,8 @@ int ahc_dispatch_best(const char* function, int nargs, const int* type_ids, int*
 /* the type id of what the kernel chosen as above returns (0 where the call's options decide it); no session, no GPU */
 int ahc_output_type(const char* function, int nargs, const int* type_ids, int* out_type_id, char* err, int64_t cap);
 /* what `function` answers to an options string ("key=value;…") before anything runs: the string predicates (match_substring,
- * starts_with, ends_with, find_substring, match_like) check pattern_hex / ignore_case here, every other function accepts.  Returns
+ * starts_with, ends_with, find_substring, match_like) check pattern_hex / ignore_case here, the string transforms start / stop / step (the slices) and
+ * characters_hex (the trims that take characters), every other function accepts.  Returns
  * the status code (0 = fine), the text into err; no session, no GPU */
 int ahc_validate_options(const char* function, const char* options, char* err, int64_t cap);
 /* a SQL LIKE pattern compiled into the segment program ah_string_like takes (include/arrowhip.h; `%`, `_`, `\` as in Arrow C++'s
