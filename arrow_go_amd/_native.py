@@ -1,4 +1,4 @@
-"""ctypes binding of libarrowhip.so (the C ABI in include/arrowhip.h).
+"""ctypes binding of libarrowhip.so (the C ABI in include/arrowhip.h and include/arrowhip_strings.h).
 
 This is plumbing: it declares the C signatures and turns status codes into Python
 exceptions named after the arrow-go error values a Go shim would wrap
@@ -15,6 +15,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ARROWHIP_LIB") or os.path.join(_HERE, "libarrowhip.so")  # env: kernel-variant experiments only
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "arrowhip.h")
+STRINGS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "arrowhip_strings.h")   # the string entry points of the same library
 
 AH_OK, AH_EINVALID, AH_EINDEX, AH_EOVERFLOW, AH_EHIP, AH_ENOTIMPL = 0, 1, 2, 3, 4, 5
 
@@ -34,6 +35,8 @@ X_NEGATE, X_ABS, X_SIGN = 20, 21, 22
 X_EQ, X_NE, X_GT, X_GE, X_LT, X_LE = 30, 31, 32, 33, 34, 35
 X_AND, X_OR, X_XOR, X_AND_NOT, X_INVERT = 40, 41, 42, 43, 44
 X_CAST = 50
+STX_WHOLE, STX_SLICE_BYTES, STX_SLICE_CODEPOINTS, STX_TRIM_BYTES, STX_TRIM_CODEPOINTS = 0, 1, 2, 3, 4   # AH_STX_* (include/arrowhip_strings.h)
+STX_LEFT, STX_RIGHT = 1, 2
 OP_DIV, OP_SQRT, OP_DIV_CHECKED, OP_ABS_CHECKED, OP_NEGATE_CHECKED, OP_SQRT_CHECKED = 3, 6, 24, 25, 26, 27
 OP_POWER, OP_POWER_CHECKED = 7, 28
 OP_SHIFT_LEFT, OP_SHIFT_LEFT_CHECKED, OP_SHIFT_RIGHT, OP_SHIFT_RIGHT_CHECKED, OP_BIT_AND, OP_BIT_OR, OP_BIT_XOR, OP_BIT_NOT = 64, 65, 66, 67, 68, 69, 70, 71
@@ -70,10 +73,12 @@ _ERRS = {AH_EINVALID: ErrInvalid, AH_EINDEX: ErrIndex, AH_EOVERFLOW: ErrOverflow
          AH_ENOTIMPL: ErrNotImplemented}
 
 
-def declared_symbols(header_path: str = HEADER_PATH) -> list[str]:
-    """Every function name include/arrowhip.h declares."""
-    with open(header_path) as f:
-        text = f.read()
+def declared_symbols(header_path: str | None = None) -> list[str]:
+    """Every function name the library's headers declare (include/arrowhip.h and include/arrowhip_strings.h), or one header's."""
+    text = ""
+    for path in ((header_path,) if header_path else (HEADER_PATH, STRINGS_HEADER_PATH)):
+        with open(path) as f:
+            text += f.read()
     return sorted(set(re.findall(r"\b(ah_[a-z0-9_]+)\s*\(", text)))
 
 
@@ -85,7 +90,7 @@ def _load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [s for s in declared_symbols() if not hasattr(lib, s)]
     if missing:
-        raise ImportError(f"libarrowhip.so does not export symbols declared in arrowhip.h: {missing}")
+        raise ImportError(f"libarrowhip.so does not export symbols declared in its headers: {missing}")
     return lib
 
 
@@ -208,6 +213,12 @@ _SIGS = {
     "ah_cmp_filter_sum_f64": [_vp, _int, _vp, _vp, _i64, _i64, C.c_double, _pd, _pi64],
     "ah_cmp_filter_sum_i64_dev": [_vp, _int, _vp, _vp, _i64, _i64, _i64, _vp],
     "ah_cmp_filter_sum_f64_dev": [_vp, _int, _vp, _vp, _i64, _i64, C.c_double, _vp, _vp],
+    "ah_string_match": [_vp, _int, _vp, _i64, _vp, _i64, _vp, _i64],
+    "ah_string_find": [_vp, _vp, _i64, _vp, _i64, _int, _vp],
+    "ah_string_like": [_vp, _vp, _i64, _int, _vp, _i64, _vp, _i64],
+    "ah_string_length": [_vp, _vp, _i64, _int, _int, _vp],
+    "ah_string_ranges": [_vp, _int, _i64, _i64, _int, _int, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _pi64],
+    "ah_string_gather": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
 }
 _SIGS.update({
     "ah_comm_unique_id": [_vp],
@@ -272,60 +283,6 @@ lib.ah_ingest_slot_buffer.argtypes = [_vp, _int, _int]
 lib.ah_ingest_slot_buffer.restype = _vp
 lib.ah_version.argtypes = []
 lib.ah_version.restype = C.c_char_p
-
-# the string predicates: libarrowhip_strings.so (include/arrowhip_strings.h), a library of its own on the same ah_ctx
-STRINGS_LIB_PATH = os.path.join(_HERE, "libarrowhip_strings.so")
-STRINGS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "arrowhip_strings.h")
-_STRINGS_SIGS = {
-    "ah_string_match": [_vp, _int, _vp, _i64, _vp, _i64, _vp, _i64],
-    "ah_string_find": [_vp, _vp, _i64, _vp, _i64, _int, _vp],
-    "ah_string_like": [_vp, _vp, _i64, _int, _vp, _i64, _vp, _i64],
-    "ah_string_length": [_vp, _vp, _i64, _int, _int, _vp],
-}
-
-
-def _load_strings() -> C.CDLL:
-    if not os.path.exists(STRINGS_LIB_PATH):
-        raise ImportError(f"{STRINGS_LIB_PATH} is missing — build() makes it beside libarrowhip.so. There is no CPU fallback.")
-    sl = C.CDLL(STRINGS_LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [s for s in declared_symbols(STRINGS_HEADER_PATH) if not hasattr(sl, s)]
-    if missing:
-        raise ImportError(f"libarrowhip_strings.so does not export symbols declared in arrowhip_strings.h: {missing}")
-    for name, args in _STRINGS_SIGS.items():
-        fn = getattr(sl, name)
-        fn.argtypes = args
-        fn.restype = _int
-    return sl
-
-
-strings_lib = _load_strings()
-
-# the string transforms: libarrowhip_string_transform.so (include/arrowhip_string_transform.h), a third library on the same ah_ctx
-STRING_TRANSFORM_LIB_PATH = os.path.join(_HERE, "libarrowhip_string_transform.so")
-STRING_TRANSFORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "arrowhip_string_transform.h")
-STX_WHOLE, STX_SLICE_BYTES, STX_SLICE_CODEPOINTS, STX_TRIM_BYTES, STX_TRIM_CODEPOINTS = 0, 1, 2, 3, 4
-STX_LEFT, STX_RIGHT = 1, 2
-_STRING_TRANSFORM_SIGS = {
-    "ah_string_ranges": [_vp, _int, _i64, _i64, _int, _int, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _pi64],
-    "ah_string_gather": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
-}
-
-
-def _load_string_transform() -> C.CDLL:
-    if not os.path.exists(STRING_TRANSFORM_LIB_PATH):
-        raise ImportError(f"{STRING_TRANSFORM_LIB_PATH} is missing — build() makes it beside libarrowhip.so. There is no CPU fallback.")
-    tl = C.CDLL(STRING_TRANSFORM_LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [s for s in declared_symbols(STRING_TRANSFORM_HEADER_PATH) if not hasattr(tl, s)]
-    if missing:
-        raise ImportError(f"libarrowhip_string_transform.so does not export symbols declared in arrowhip_string_transform.h: {missing}")
-    for name, args in _STRING_TRANSFORM_SIGS.items():
-        fn = getattr(tl, name)
-        fn.argtypes = args
-        fn.restype = _int
-    return tl
-
-
-string_transform_lib = _load_string_transform()
 
 
 def check(ctx_handle, status: int) -> None:

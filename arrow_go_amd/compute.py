@@ -871,7 +871,7 @@ class Session:
 
     # -- string transforms (Arrow C++'s semantics; values a String / LargeString — binary_slice: Binary / LargeBinary — Array, ChunkedArray
     # or DeviceArray; the output has the input's type and validity, a null row has length 0).  Every result is one sub-range of the
-    # row's bytes: ah_string_ranges + ah_string_gather of libarrowhip_string_transform.so.
+    # row's bytes: ah_string_ranges + ah_string_gather.
     def ascii_upper(self, values, keep_on_device: bool = False):
         """call_function("ascii_upper", [values]): the bytes a-z become A-Z, every other byte (≥ 0x80 included) stays."""
         return self.call_function("ascii_upper", [values], keep_on_device=keep_on_device)

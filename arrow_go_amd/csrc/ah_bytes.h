@@ -99,6 +99,17 @@ __device__ __forceinline__ unsigned long long word_at(const uint8_t* p, int64_t 
   return len - j >= 8 ? load8(p + j) : load_tail(p + j, (int)(len - j));
 }
 
+// The wave takes the lanes in `need` (wave-uniform; called with all 64 lanes active), one after another: body(l) with the number of
+// the lane whose turn it is — every lane runs it, for lane l's row, whose values it fetches with __shfl(x, l).
+template <typename Body>
+__device__ __forceinline__ void for_pending_lanes(unsigned long long need, Body body) {
+  while (need) {
+    const int l = __ffsll((long long)need) - 1;
+    need &= need - 1;
+    body(l);
+  }
+}
+
 // The whole wave compares the long values of the lanes in `need` (wave-uniform; called with all 64 lanes active), one
 // pending lane after another, 512 bytes per step (64 lanes × 8 bytes): bytes [from, len) of a and b, `from` a multiple of 8.
 // Each pending lane then calls done(r) with the result for its own a, b, len:
@@ -108,9 +119,7 @@ __device__ __forceinline__ unsigned long long word_at(const uint8_t* p, int64_t 
 template <bool ORDER, typename Done>
 __device__ __forceinline__ void wave_compare(unsigned long long need, const uint8_t* a, const uint8_t* b, int64_t len, int64_t from, Done done) {
   const int lane = ah_lane();
-  while (need) {
-    const int l = __ffsll((long long)need) - 1;
-    need &= need - 1;
+  for_pending_lanes(need, [&](int l) {
     const uint8_t* wa = (const uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)a, l);
     const uint8_t* wb = (const uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)b, l);
     const int64_t m = __shfl((long long)len, l);
@@ -131,7 +140,7 @@ __device__ __forceinline__ void wave_compare(unsigned long long need, const uint
       r = __ballot(diff) != 0ull;
     }
     if (lane == l) done(r);
-  }
+  });
 }
 
 // The row copy of the var-length outputs (the Take of ah_varlen.hip, the if_else of ah_conditional.hip): a wave owns 64 output rows,
@@ -159,19 +168,6 @@ __device__ __forceinline__ void wave_copy_rows(CopyRow* s_rows, const uint8_t* s
   }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the next chunk overwrites s_rows
   __builtin_amdgcn_wave_barrier();
-}
-
-// The offsets buffer of a var-length output from the inclusive scan of its rows' lengths (the Take of ah_varlen.hip, the formatted
-// casts of ah_cast_string.hip): out_offsets[0] = 0, out_offsets[i + 1] = incl[i]; int32 offsets: flag an overflow
-template <typename OffT, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void offsets_kernel(const long long* __restrict__ incl, int64_t n, OffT* __restrict__ out_offsets,
-                                                         unsigned* __restrict__ overflow) {
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i <= n; i += stride) {
-    const long long v = i == 0 ? 0 : incl[i - 1];
-    if (sizeof(OffT) == 4 && v > 2147483647ll) atomicOr(overflow, 1u);
-    out_offsets[i] = (OffT)v;
-  }
 }
 
 }  // namespace

@@ -17,6 +17,7 @@
 //              taken by the whole wave one after the other, 16 bytes per lane and step (sc_utf8_valid_range).
 #include "ah_bytes.h"
 #include "ah_strconv.h"
+#include "ah_varout.h"
 
 namespace {
 
@@ -321,37 +322,26 @@ AH_EXPORT int ah_format_int_offsets(ah_ctx* c, int in_type, const void* values, 
     AH_HIP(c, hipMemsetAsync(out_offsets, 0, (size_t)offset_width, c->stream));
     return AH_OK;
   }
-  // temporaries in the temp arena (the scan called below uses the scratch arena)
-  const size_t col = ah_pad((size_t)n * 8);
-  void* arena;
-  int rc = ah_temp_reserve(c, 2 * col, &arena);
+  VarOut v;
+  int rc = varout_begin(c, n, 0, /*can_overflow=*/true, &v);
   if (rc != AH_OK) return rc;
-  long long* lens = (long long*)arena;
-  long long* incl = (long long*)((uint8_t*)arena + col);
-  unsigned* overflow = (unsigned*)&c->dscalars[3];
-  AH_HIP(c, hipMemsetAsync(overflow, 0, sizeof(uint64_t), c->stream));
   const unsigned grid = chunk_grid(c, n);
   const uint8_t* in = (const uint8_t*)values;
   switch (bytes) {
-    case 0: format_lens_kernel<0><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, lens); break;
-    case 1: format_lens_kernel<1><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, lens); break;
-    case 2: format_lens_kernel<2><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, lens); break;
-    case 4: format_lens_kernel<4><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, lens); break;
-    default: format_lens_kernel<8><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, lens); break;
+    case 0: format_lens_kernel<0><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, v.lens); break;
+    case 1: format_lens_kernel<1><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, v.lens); break;
+    case 2: format_lens_kernel<2><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, v.lens); break;
+    case 4: format_lens_kernel<4><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, v.lens); break;
+    default: format_lens_kernel<8><<<grid, kBlock, 0, c->stream>>>(in, valid, off, n, is_signed, v.lens); break;
   }
   AH_LAUNCH_CHECK(c);
-  rc = ah_cumulative_sum(c, AH_INT64, lens, nullptr, 0, n, nullptr, 0, 0, incl, nullptr, nullptr);
+  rc = varout_enqueue(c, v, n, offset_width, out_offsets, /*caller_words=*/false);
   if (rc != AH_OK) return rc;
-  const unsigned ogrid = ah_stream_grid(c, ah_ceil_div(n + 1, kBlock), 8);
-  if (offset_width == 4) offsets_kernel<int32_t, kBlock><<<ogrid, kBlock, 0, c->stream>>>(incl, n, (int32_t*)out_offsets, overflow);
-  else offsets_kernel<long long, kBlock><<<ogrid, kBlock, 0, c->stream>>>(incl, n, (long long*)out_offsets, overflow);
-  AH_LAUNCH_CHECK(c);
-  AH_HIP(c, hipMemcpyAsync(c->pinned, overflow, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  AH_HIP(c, hipMemcpyAsync(&c->pinned[1], incl + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  AH_HIP(c, hipStreamSynchronize(c->stream));
-  const unsigned over = *(volatile unsigned*)&c->pinned[0];
-  const int64_t total = *(volatile int64_t*)&c->pinned[1];
-  if (over & 1u) return ah_fail(c, AH_EINVALID, "formatted cast: %lld bytes exceed the 32-bit offsets of the output", (long long)total);
+  int64_t total = 0;
+  bool over = false;
+  rc = varout_finish(c, v, &total, &over);
+  if (rc != AH_OK) return rc;
+  if (over) return ah_fail(c, AH_EINVALID, "formatted cast: %lld bytes exceed the 32-bit offsets of the output", (long long)total);
   if (out_total_bytes_host) *out_total_bytes_host = total;
   return AH_OK;
 }

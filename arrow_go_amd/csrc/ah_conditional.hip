@@ -33,6 +33,7 @@
 // No workgroup waits for another one.  A column of one workgroup's rows is launch 3 alone.
 #include "ah_bytes.h"
 #include "ah_index.h"
+#include "ah_varout.h"
 
 namespace {
 
@@ -647,29 +648,20 @@ AH_EXPORT int ah_if_else_binary_offsets(ah_ctx* c, const uint8_t* cond_data, con
     AH_HIP(c, hipMemsetAsync(out_offsets, 0, (size_t)out_offset_width, c->stream));
     return AH_OK;
   }
-  // temporaries in the context's temp arena (the scan called below uses the scratch arena)
-  const size_t col = ah_pad((size_t)n * 8);
-  void* arena;
-  rc = ah_temp_reserve(c, 2 * col, &arena);
+  VarOut v;
+  rc = varout_begin(c, n, 0, /*can_overflow=*/true, &v);
   if (rc != AH_OK) return rc;
-  long long* lens = (long long*)arena;
-  long long* incl = (long long*)((uint8_t*)arena + col);
-  unsigned* overflow = (unsigned*)&c->dscalars[3];
-  AH_HIP(c, hipMemsetAsync(overflow, 0, sizeof(uint64_t), c->stream));
   if_else_lens_kernel<<<ah_stream_grid(c, ah_ceil_div(ah_ceil_div(n, 64), kBlock / 64), 8), kBlock, 0, c->stream>>>(Cond{cond_data, cond_valid, cond_off}, side_of(*l),
-                                                                                                                    side_of(*r), n, lens, out_valid);
+                                                                                                                    side_of(*r), n, v.lens, out_valid);
   AH_LAUNCH_CHECK(c);
-  rc = ah_cumulative_sum(c, AH_INT64, lens, nullptr, 0, n, nullptr, 0, 0, incl, nullptr, nullptr);
+  rc = varout_enqueue(c, v, n, out_offset_width, out_offsets, /*caller_words=*/false);
   if (rc != AH_OK) return rc;
-  const unsigned grid = ah_stream_grid(c, ah_ceil_div(n + 1, kBlock), 8);
-  if (out_offset_width == 4) offsets_kernel<int32_t, kBlock><<<grid, kBlock, 0, c->stream>>>(incl, n, (int32_t*)out_offsets, overflow);
-  else offsets_kernel<int64_t, kBlock><<<grid, kBlock, 0, c->stream>>>(incl, n, (int64_t*)out_offsets, overflow);
-  AH_LAUNCH_CHECK(c);
-  AH_HIP(c, hipMemcpyAsync(&c->pinned[0], overflow, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  AH_HIP(c, hipMemcpyAsync(&c->pinned[1], incl + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  AH_HIP(c, hipStreamSynchronize(c->stream));
-  if (*(volatile unsigned*)&c->pinned[0] & 1u) return ah_fail(c, AH_EINVALID, "binary output offset overflow");   // the Take pair's words
-  if (out_total_bytes_host) *out_total_bytes_host = *(volatile int64_t*)&c->pinned[1];
+  int64_t total = 0;
+  bool overflow = false;
+  rc = varout_finish(c, v, &total, &overflow);
+  if (rc != AH_OK) return rc;
+  if (overflow) return ah_fail(c, AH_EINVALID, "binary output offset overflow");
+  if (out_total_bytes_host) *out_total_bytes_host = total;
   return AH_OK;
 }
 

@@ -6,7 +6,6 @@
 // ah_host_alloc_pinned gives Arrow buffers that hipMemcpyAsync can DMA directly.
 #include <chrono>
 #include "ah_common.h"
-#include "ah_arena.h"
 
 static const char* kVersion = "arrowhip 0.1 (gfx950)";
 
@@ -236,7 +235,34 @@ int ah_mailbox_read2(ah_ctx* c, const unsigned long long* dev_words, int nwords,
   return AH_OK;
 }
 
-// the three grow-only arenas: one growth policy (ah_arena.h), which the sibling libraries on this context use as well
+// The three grow-only arenas (scratch, temp, pack) and their one growth policy: make *block hold at least nbytes (its size in
+// *bytes, rounded up to 1 MiB); contents are undefined after the call.  The old block may still be in use by enqueued kernels, so
+// growing synchronises the stream first.  `what` names the arena in the out-of-memory error ("out of device memory (N bytes of
+// <what>)"; nullptr: the plain hipMalloc error); *out_of_memory (nullable) tells a failed hipMalloc from a failed synchronisation
+// or hipFree.
+static int ah_arena_reserve(ah_ctx* c, void** block, size_t* bytes, size_t nbytes, const char* what, void** out, bool* out_of_memory = nullptr) {
+  if (out_of_memory) *out_of_memory = false;
+  if (nbytes > *bytes) {
+    AH_HIP(c, hipStreamSynchronize(c->stream));
+    if (*block) AH_HIP(c, hipFree(*block));
+    *block = nullptr;
+    *bytes = 0;
+    const size_t want = (nbytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+    if (what) {
+      if (hipMalloc(block, want) != hipSuccess) {
+        (void)hipGetLastError();
+        if (out_of_memory) *out_of_memory = true;
+        return ah_fail(c, AH_EHIP, "out of device memory (%zu bytes of %s)", want, what);
+      }
+    } else {
+      AH_HIP(c, hipMalloc(block, want));
+    }
+    *bytes = want;
+  }
+  *out = *block;
+  return AH_OK;
+}
+
 int ah_scratch_reserve(ah_ctx* c, size_t nbytes, void** out) { return ah_arena_reserve(c, &c->scratch, &c->scratch_bytes, nbytes, nullptr, out); }
 
 int ah_temp_reserve(ah_ctx* c, size_t nbytes, void** out, bool* out_of_memory) {

@@ -1,4 +1,4 @@
-// ah_string_match.hip (libarrowhip_strings.so, include/arrowhip_strings.h) — what is inside a string: match_substring, starts_with, ends_with, find_substring, match_like, binary_length,
+// ah_string_match.hip (include/arrowhip_strings.h) — what is inside a string: match_substring, starts_with, ends_with, find_substring, match_like, binary_length,
 // utf8_length over String / Binary / LargeString / LargeBinary columns (no reference analogue; Arrow C++'s semantics).
 //
 // The searches work over the value BYTES of the column, which are contiguous across rows, not over its rows.  The data buffer of the
@@ -28,20 +28,15 @@
 // matched from LDS segment by segment — leftmost-greedy, a row per lane up to kLaneLike bytes, longer rows by the whole wave, 64
 // candidate positions of a segment per step.  The one row per tile that ends behind the staged bytes is matched by the wave from
 // global memory.  Code-point stepping for `_` on UTF-8 columns is part of the segment walk (seg_fwd / seg_rev).
-#include "../ah_common.h"
-#include "../ah_bytes.h"
-#include "../ah_arena.h"
-#include "../../../include/arrowhip_strings.h"
+#include "ah_bytes.h"
+#include "ah_strings.h"
+#include "../../include/arrowhip_strings.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kDefaultTile = 16384;  // bytes of the data buffer per tile: 16 KiB + bit array + pattern ≈ 19 KiB of LDS, eight workgroups per CU
-constexpr int kMinTile = 64, kMaxTile = 32768;
 constexpr int kLaneSpan = 512;       // positions (16 words of the bit array) a lane scans alone
 constexpr int kLaneLike = 256;       // bytes of a row a lane matches alone (LIKE)
 constexpr int kLaneCmp = 64;         // bytes of the pattern a lane compares alone (starts_with / ends_with / equals)
-constexpr int kWgPerCu = 8;
 constexpr int kMaxLikeElems = 2048, kMaxLikeSegs = 512;
 constexpr int kMaxProgram = 3 + 2 * kMaxLikeSegs + 2 * kMaxLikeElems;
 
@@ -62,26 +57,13 @@ __host__ __device__ inline int pattern_words(int m) { return (m + 7) / 8 + 1; }
 
 // the run of tiles of this workgroup and its first row: the first row that starts at or behind the run's first byte
 template <int OW>
-__device__ __forceinline__ bool tile_run(const void* offsets, int64_t n, int T, int64_t* base, int64_t* end, int64_t* ntiles, int64_t* t0, int64_t* t1,
-                                         long long* s_cur) {
-  *base = off_at<OW>(offsets, 0);
+__device__ __forceinline__ bool column_run(const void* offsets, int64_t n, int T, int64_t* base, int64_t* end, int64_t* ntiles, int64_t* t0, int64_t* t1,
+                                           long long* s_cur) {
+  const int64_t b = *base = off_at<OW>(offsets, 0);
   *end = off_at<OW>(offsets, n);
-  const int64_t total = *end - *base;
+  const int64_t total = *end - b;
   *ntiles = total > 0 ? (total + T - 1) / T : 1;   // (a column without bytes still has rows to answer: one empty tile)
-  const int64_t per = (*ntiles + gridDim.x - 1) / gridDim.x;
-  *t0 = (int64_t)blockIdx.x * per;
-  *t1 = *t0 + per < *ntiles ? *t0 + per : *ntiles;
-  if (*t0 >= *t1) return false;
-  if (threadIdx.x == 0) {
-    const int64_t x = *base + *t0 * T;
-    int64_t lo = 0, hi = n;   // first i in [0, n] with offsets[i] >= x (offsets[n] = end >= x)
-    while (lo < hi) {
-      const int64_t mid = lo + ((hi - lo) >> 1);
-      if (off_at<OW>(offsets, mid) < x) lo = mid + 1;
-      else hi = mid;
-    }
-    *s_cur = lo;
-  }
+  if (!tile_run(*ntiles, T, n, [&](int64_t i, int64_t x) { return off_at<OW>(offsets, i) < b + x; }, t0, t1, s_cur)) return false;   // (offsets[n] = end is not in front of x)
   __syncthreads();
   return true;
 }
@@ -174,9 +156,7 @@ __device__ __forceinline__ int scan_lane(const unsigned* h, int a, int b) {
 template <int MODE>
 __device__ __forceinline__ void scan_wave(unsigned long long need, const unsigned* h, int a, int b, int* res) {
   const int lane = ah_lane();
-  while (need) {
-    const int l = __ffsll((long long)need) - 1;
-    need &= need - 1;
+  for_pending_lanes(need, [&](int l) {
     const int ra = __shfl(a, l), rb = __shfl(b, l);
     const int k1 = (rb - 1) >> 5;
     int r = MODE == kFind ? -1 : 0;
@@ -198,7 +178,7 @@ __device__ __forceinline__ void scan_wave(unsigned long long need, const unsigne
       for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o);
     }
     if (lane == l) *res = r;
-  }
+  });
 }
 
 // The search over the tiles.  MODE kFind: out[i] = the byte index of the pattern's first occurrence in row i, all ones for none;
@@ -213,7 +193,7 @@ __global__ __launch_bounds__(kBlock) void search_kernel(const void* __restrict__
   unsigned* s_hit = (unsigned*)(lds + sbytes);
   unsigned long long* s_pat = (unsigned long long*)(lds + sbytes + round_up(nwords * 4, 8));
   int64_t base, end, ntiles, t0, t1;
-  if (!tile_run<OW>(offsets, n, T, &base, &end, &ntiles, &t0, &t1, &s_cur)) return;
+  if (!column_run<OW>(offsets, n, T, &base, &end, &ntiles, &t0, &t1, &s_cur)) return;
   if (MODE == kFind)
     for (int j = threadIdx.x; j < pattern_words(m); j += kBlock) s_pat[j] = pat[j];
   int64_t cur = s_cur;
@@ -333,7 +313,6 @@ __global__ __launch_bounds__(kBlock) void length_kernel(ByteRows rows, int64_t n
 // ---- LIKE ------------------------------------------------------------------------------------------------------------------------------
 // One segment of the program: a 2-byte element count, then {kind, byte} pairs (kind 0: the literal byte, 1: one character).
 // `_` on a UTF-8 column is one byte that is not 10xxxxxx and ALL the continuation bytes behind it, read forwards or backwards.
-__device__ __forceinline__ bool is_cont(uint8_t b) { return (b & 0xC0) == 0x80; }
 
 // the segment matched at position x of the row's first `len` bytes → the position behind it, or −1
 __device__ __forceinline__ long long seg_fwd(const uint8_t* seg, const uint8_t* p, long long x, long long len, int utf8) {
@@ -426,7 +405,7 @@ __global__ __launch_bounds__(kBlock) void like_kernel(const void* __restrict__ o
   const int sbytes = round_up(T + overlap, 16);
   uint8_t* s_data = lds;
   int64_t base, end, ntiles, t0, t1;
-  if (!tile_run<OW>(offsets, n, T, &base, &end, &ntiles, &t0, &t1, &s_cur)) return;
+  if (!column_run<OW>(offsets, n, T, &base, &end, &ntiles, &t0, &t1, &s_cur)) return;
   for (int j = threadIdx.x; j < program_len; j += kBlock) s_prog[j] = program[j];
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -463,15 +442,12 @@ __global__ __launch_bounds__(kBlock) void like_kernel(const void* __restrict__ o
           else pend = true;
         }
       }
-      unsigned long long need = __ballot(pend);
-      while (need) {   // the long rows: the whole wave, one after another
-        const int l = __ffsll((long long)need) - 1;
-        need &= need - 1;
+      for_pending_lanes(__ballot(pend), [&](int l) {   // the long rows: the whole wave, one after another
         const uint8_t* wp = (const uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)p, l);
         const long long wl = __shfl(len, l);
         const bool r = like_row<true>(s_prog, s_seg, wp, wl, utf8);
         if (ah_lane() == l) hit = r;
-      }
+      });
       if (in) part[i] = hit ? 1 : 0;
       const int cnt = __syncthreads_count(in);
       seen += cnt;
@@ -482,26 +458,8 @@ __global__ __launch_bounds__(kBlock) void like_kernel(const void* __restrict__ o
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-int tile_bytes(const ah_ctx* c) {   // (ah_ctx_set_option refuses values outside kMinTile … kMaxTile)
-  const int t = c->opt_string_tile_bytes ? c->opt_string_tile_bytes : kDefaultTile;
-  return t < kMinTile ? kMinTile : t > kMaxTile ? kMaxTile : t;
-}
-unsigned tile_grid(const ah_ctx* c) { return (unsigned)(c->num_cu > 0 ? c->num_cu : 1) * kWgPerCu; }
-unsigned chunk_grid(ah_ctx* c, int64_t n) { return ah_stream_grid(c, ah_ceil_div(ah_ceil_div(n, 64), kBlock / 64), 8); }
 int out_aligned(const uint8_t* out, int64_t out_off) { return (out_off & 63) == 0 && ((uintptr_t)out & 7) == 0; }
 
-int check_column(ah_ctx* c, const char* fn, const ah_cmp_operand* o, int64_t n, bool fixed_ok) {
-  if (n < 0) return ah_fail(c, AH_EINVALID, "%s: negative length", fn);
-  if (!o) return ah_fail(c, AH_EINVALID, "%s: null operand descriptor", fn);
-  if (o->offset_width == 0 && !fixed_ok) return ah_fail(c, AH_EINVALID, "%s: the column needs 4- or 8-byte offsets, not fixed slots", fn);
-  if (o->offset_width != 0 && o->offset_width != 4 && o->offset_width != 8)
-    return ah_fail(c, AH_EINVALID, "%s: offset width must be 0, 4 or 8 (got %d)", fn, o->offset_width);
-  if (o->offset_width == 0 && o->byte_width < 0) return ah_fail(c, AH_EINVALID, "%s: negative byte width", fn);
-  if (o->off < 0) return ah_fail(c, AH_EINVALID, "%s: negative element offset", fn);
-  if (o->broadcast) return ah_fail(c, AH_EINVALID, "%s: the column cannot be a broadcast scalar", fn);
-  if (n > 0 && o->offset_width != 0 && !o->offsets) return ah_fail(c, AH_EINVALID, "%s: null offsets", fn);
-  return AH_OK;
-}
 int check_pattern(ah_ctx* c, const char* fn, const uint8_t* pattern, int64_t m) {
   if (m < 0 || m > AH_STR_MAX_PATTERN) return ah_fail(c, AH_EINVALID, "%s: pattern length %lld outside 0 … %d", fn, (long long)m, AH_STR_MAX_PATTERN);
   if (m > 0 && !pattern) return ah_fail(c, AH_EINVALID, "%s: null pattern", fn);
@@ -519,16 +477,11 @@ int check_bits(ah_ctx* c, const char* fn, const uint8_t* out_bits, int64_t out_b
   return AH_OK;
 }
 
-// The context's grow-only scratch arena, as ah_scratch_reserve (ah_ctx.hip) hands it out — that function is internal to
-// libarrowhip.so, and this file is a library of its own on the same ah_ctx; both grow the arena through ah_arena.h.  Contents are
-// undefined after the call.
-int scratch_reserve(ah_ctx* c, size_t nbytes, void** out) { return ah_arena_reserve(c, &c->scratch, &c->scratch_bytes, nbytes, nullptr, out); }
-
 // the pattern as zero-padded 8-byte words on the device, in front of `extra` more bytes of the scratch arena
 int upload_pattern(ah_ctx* c, const uint8_t* pattern, int m, size_t extra, unsigned long long** pat, uint8_t** rest) {
   const size_t pbytes = (size_t)pattern_words(m) * 8;
   void* tmp = nullptr;
-  if (int rc = scratch_reserve(c, ah_pad(pbytes) + extra, &tmp)) return rc;
+  if (int rc = ah_scratch_reserve(c, ah_pad(pbytes) + extra, &tmp)) return rc;
   *pat = (unsigned long long*)tmp;
   *rest = (uint8_t*)tmp + ah_pad(pbytes);
   AH_HIP(c, hipMemsetAsync(tmp, 0, pbytes, c->stream));
@@ -663,7 +616,7 @@ AH_EXPORT int ah_string_like(ah_ctx* c, const ah_cmp_operand* operand, int64_t n
   }
   const int T = tile_bytes(c), overlap = T / 4 < 64 ? 64 : T / 4;
   void* tmp = nullptr;
-  if (int rc = scratch_reserve(c, ah_pad((size_t)program_len) + (size_t)n, &tmp)) return rc;
+  if (int rc = ah_scratch_reserve(c, ah_pad((size_t)program_len) + (size_t)n, &tmp)) return rc;
   uint8_t* part = (uint8_t*)tmp + ah_pad((size_t)program_len);
   AH_HIP(c, hipMemcpyAsync(tmp, program, (size_t)program_len, hipMemcpyHostToDevice, c->stream));
   const ByteRows rows = byte_rows(operand->offset_width, operand->offsets, operand->data, 0, operand->off);

@@ -1,4 +1,4 @@
-// ah_string_transform.hip (libarrowhip_string_transform.so, include/arrowhip_string_transform.h) — the string transforms whose result
+// ah_string_transform.hip (include/arrowhip_strings.h) — the string transforms whose result
 // is one contiguous sub-range of the row's bytes: utf8_slice_codeunits, binary_slice, ascii_trim*, utf8_trim*, and — the whole row
 // through a byte map — ascii_upper / ascii_lower (no reference analogue; Arrow C++'s semantics).
 //
@@ -17,16 +17,13 @@
 //                     its lane alone (≤ kLaneCopy bytes), by the wave (≤ kWaveCopy, 256 bytes per step) or by the whole workgroup
 //                     (4 KiB per step, 16 bytes per thread) — so a row that covers many runs is copied by all of them, and every
 //                     output byte has exactly one writer.  The optional byte map sits in LDS.
-#include "../ah_common.h"
-#include "../ah_bytes.h"
-#include "../ah_arena.h"
-#include "../../../include/arrowhip_string_transform.h"
+#include "ah_bytes.h"
+#include "ah_strings.h"
+#include "ah_varout.h"
+#include "../../include/arrowhip_strings.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kDefaultTile = 16384, kMinTile = 64, kMaxTile = 32768;   // (string_tile_bytes, as ah_string_match.hip reads it)
-constexpr int kWgPerCu = 8;
 constexpr int kLaneWalk = 64;      // bytes of a row a lane looks at alone (ranges)
 constexpr int kLaneCopy = 64;      // bytes of a clipped row a lane copies alone (gather)
 constexpr int kWaveCopy = 4096;    // … the wave copies; longer: the workgroup
@@ -36,8 +33,6 @@ struct RangeOp {
   int op, has_stop, sides, nkeys;
   long long start, stop;
 };
-
-__device__ __forceinline__ bool is_cont(uint8_t b) { return (b & 0xC0) == 0x80; }
 
 // WAVE: all 64 lanes hold the same row and look at 64 consecutive bytes per step; else one lane walks alone, a byte per step, and
 // gives up (→ −1 / false) when its budget of kLaneWalk bytes is spent.
@@ -247,10 +242,7 @@ __global__ __launch_bounds__(kBlock) void ranges_kernel(const OffT* __restrict__
         pend = !row_range<OP, false>(o, p, len, s_set, &a, &b);
       }
     }
-    unsigned long long need = __ballot(pend);
-    while (need) {   // the rows a lane could not finish alone: the whole wave, one after another
-      const int l = __ffsll((long long)need) - 1;
-      need &= need - 1;
+    for_pending_lanes(__ballot(pend), [&](int l) {   // the rows a lane could not finish alone: the whole wave, one after another
       const uint8_t* wp = (const uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)p, l);
       const long long wl = __shfl(len, l);
       long long wa = 0, wb = 0;
@@ -259,7 +251,7 @@ __global__ __launch_bounds__(kBlock) void ranges_kernel(const OffT* __restrict__
         a = wa;
         b = wb;
       }
-    }
+    });
     if (i < n) {
       starts[i] = (OffT)(rs + a);
       lens[i] = b - a;
@@ -288,21 +280,10 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const uint8_t* __restric
   __shared__ uint8_t s_map[256];
   __shared__ BigRow s_big[kBlock];
   const int64_t total = (int64_t)oo[n];
-  const int64_t ntiles = (total + T - 1) / T;
-  const int64_t per = (ntiles + gridDim.x - 1) / gridDim.x;
-  const int64_t t0 = (int64_t)blockIdx.x * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
-  if (t0 >= t1) return;
+  int64_t t0, t1;   // the first row of the run: the first that ends behind its first byte (that byte is in front of total = oo[n]: row n − 1 is one)
+  if (!tile_run((total + T - 1) / T, T, n - 1, [&](int64_t i, int64_t x) { return (int64_t)oo[i + 1] <= x; }, &t0, &t1, &s_first)) return;
   const int64_t lo = t0 * T, hi = t1 * T < total ? t1 * T : total;   // this workgroup's output bytes
-  if (threadIdx.x == 0) {
-    int64_t l = 0, h = n - 1;   // the first row i with oo[i + 1] > lo (lo < total = oo[n]: row n − 1 is one)
-    while (l < h) {
-      const int64_t mid = l + ((h - l) >> 1);
-      if ((int64_t)oo[mid + 1] > lo) h = mid;
-      else l = mid + 1;
-    }
-    s_first = l;
-    s_nbig = 0;
-  }
+  if (threadIdx.x == 0) s_nbig = 0;
   if (MAP) s_map[threadIdx.x] = map.b[threadIdx.x];   // (kBlock = 256; the map travels as a kernel argument: nothing to upload)
   __syncthreads();
   const int lane = ah_lane();
@@ -332,17 +313,14 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const uint8_t* __restric
       for (; b + 4 <= len; b += 4) ((U32u*)(dst + b))->v = map4<MAP>(((const U32u*)(src + b))->v, s_map);
       for (; b < len; b++) dst[b] = map1<MAP>(src[b], s_map);
     }
-    unsigned long long need = __ballot(len > kLaneCopy && len <= kWaveCopy);
-    while (need) {   // the wave's rows, one after another: 4 bytes per lane and step
-      const int l = __ffsll((long long)need) - 1;
-      need &= need - 1;
+    for_pending_lanes(__ballot(len > kLaneCopy && len <= kWaveCopy), [&](int l) {   // the wave's rows, one after another: 4 bytes per lane and step
       const uint8_t* ws = (const uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)src, l);
       uint8_t* wd = (uint8_t*)(uintptr_t)__shfl((long long)(uintptr_t)dst, l);
       const long long wl = __shfl(len, l);
       for (long long b = (long long)lane * 4; b + 4 <= wl; b += 256) ((U32u*)(wd + b))->v = map4<MAP>(((const U32u*)(ws + b))->v, s_map);
       const long long tail = wl & ~3ll;
       if (lane < (int)(wl - tail)) wd[tail + lane] = map1<MAP>(ws[tail + lane], s_map);
-    }
+    });
     const int cnt = __syncthreads_count(in);
     // How many rows were queued comes from a reduction over the threads' own `len`, never from a read of s_nbig: a wave that is
     // already in the next iteration may be adding to that counter.  s_nbig only hands out the slots; it is reset inside the
@@ -372,26 +350,7 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const uint8_t* __restric
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-int tile_bytes(const ah_ctx* c) {   // (ah_ctx_set_option refuses values outside kMinTile … kMaxTile)
-  const int t = c->opt_string_tile_bytes ? c->opt_string_tile_bytes : kDefaultTile;
-  return t < kMinTile ? kMinTile : t > kMaxTile ? kMaxTile : t;
-}
-
-int check_column(ah_ctx* c, const char* fn, const ah_cmp_operand* o, int64_t n) {
-  if (n < 0) return ah_fail(c, AH_EINVALID, "%s: negative length", fn);
-  if (!o) return ah_fail(c, AH_EINVALID, "%s: null operand descriptor", fn);
-  if (o->offset_width != 4 && o->offset_width != 8) return ah_fail(c, AH_EINVALID, "%s: the column needs 4- or 8-byte offsets (got width %d)", fn, o->offset_width);
-  if (o->off < 0) return ah_fail(c, AH_EINVALID, "%s: negative element offset", fn);
-  if (o->broadcast) return ah_fail(c, AH_EINVALID, "%s: the column cannot be a broadcast scalar", fn);
-  if (n > 0 && !o->offsets) return ah_fail(c, AH_EINVALID, "%s: null offsets", fn);
-  return AH_OK;
-}
 bool bad_buffer(const void* p, int width) { return !p || ((uintptr_t)p & (uintptr_t)(width - 1)); }
-
-// The context's second grow-only arena, as ah_temp_reserve (ah_ctx.hip) hands it out — that function is internal to libarrowhip.so,
-// and this file is a library of its own on the same ah_ctx.  (The scan called below takes the scratch arena.)
-// Both grow the arena through ah_arena.h.
-int temp_reserve(ah_ctx* c, size_t nbytes, void** out) { return ah_arena_reserve(c, &c->temp, &c->temp_bytes, nbytes, "temporaries", out); }
 
 // `chars` as the sorted keys of its code points (their bytes, first byte lowest); false: not valid UTF-8
 bool code_point_keys(const uint8_t* s, int64_t m, unsigned* keys, int* nkeys) {
@@ -432,7 +391,7 @@ AH_EXPORT int ah_string_ranges(ah_ctx* c, int op, int64_t start, int64_t stop, i
   AH_ENTER(c);
   if (out_total_bytes_host) *out_total_bytes_host = 0;
   if (op < AH_STX_WHOLE || op > AH_STX_TRIM_CODEPOINTS) return ah_fail(c, AH_EINVALID, "string_ranges: bad op %d", op);
-  if (int rc = check_column(c, "string_ranges", operand, n)) return rc;
+  if (int rc = check_column(c, "string_ranges", operand, n, false)) return rc;
   if (valid_offset < 0) return ah_fail(c, AH_EINVALID, "string_ranges: negative validity offset");
   const bool trim = op == AH_STX_TRIM_BYTES || op == AH_STX_TRIM_CODEPOINTS;
   unsigned set_words[kMaxKeys];
@@ -454,21 +413,18 @@ AH_EXPORT int ah_string_ranges(ah_ctx* c, int op, int64_t start, int64_t stop, i
   const int ow = operand->offset_width;
   if (n > 0 && (bad_buffer(out_starts, ow) || bad_buffer(out_offsets, ow))) return ah_fail(c, AH_EINVALID, "string_ranges: null or misaligned output");
   if (n == 0) return AH_OK;
-  // temporaries in the temp arena (the scan takes the scratch arena): the set, the rows' lengths, their inclusive scan
-  const size_t col = ah_pad((size_t)n * 8), setb = ah_pad(sizeof(set_words));
-  void* arena = nullptr;
-  if (int rc = temp_reserve(c, setb + 2 * col, &arena)) return rc;
-  unsigned* set_dev = (unsigned*)arena;
-  long long* lens = (long long*)((uint8_t*)arena + setb);
-  long long* incl = (long long*)((uint8_t*)arena + setb + col);
+  // the rows' lengths and their scan, the set in front of them; a row's result is never longer than the row: no overflow to look for
+  VarOut v;
+  if (int rc = varout_begin(c, n, sizeof(set_words), /*can_overflow=*/false, &v)) return rc;
+  unsigned* set_dev = (unsigned*)v.extra;
   // (set_words is this function's stack: the copy is read by the time the call returns — it ends in a synchronisation, also where it fails)
   if (nset > 0) AH_HIP(c, hipMemcpyAsync(set_dev, set_words, (size_t)nset * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
   const ByteRows rows = byte_rows(ow, operand->offsets, operand->data, 0, operand->off);
-  const unsigned grid = ah_stream_grid(c, ah_ceil_div(ah_ceil_div(n, 64), kBlock / 64), 8);
+  const unsigned grid = chunk_grid(c, n);
   auto launch = [&](auto tag) {
     constexpr int OP = decltype(tag)::value;
-    if (ow == 4) ranges_kernel<int32_t, OP><<<grid, kBlock, 0, c->stream>>>((const int32_t*)rows.offsets, rows.data, valid, valid_offset, n, o, set_dev, nset, (int32_t*)out_starts, lens);
-    else ranges_kernel<long long, OP><<<grid, kBlock, 0, c->stream>>>((const long long*)rows.offsets, rows.data, valid, valid_offset, n, o, set_dev, nset, (long long*)out_starts, lens);
+    if (ow == 4) ranges_kernel<int32_t, OP><<<grid, kBlock, 0, c->stream>>>((const int32_t*)rows.offsets, rows.data, valid, valid_offset, n, o, set_dev, nset, (int32_t*)out_starts, v.lens);
+    else ranges_kernel<long long, OP><<<grid, kBlock, 0, c->stream>>>((const long long*)rows.offsets, rows.data, valid, valid_offset, n, o, set_dev, nset, (long long*)out_starts, v.lens);
   };
   switch (op) {
     case AH_STX_SLICE_BYTES: launch(std::integral_constant<int, AH_STX_SLICE_BYTES>{}); break;
@@ -481,25 +437,22 @@ AH_EXPORT int ah_string_ranges(ah_ctx* c, int op, int64_t start, int64_t stop, i
     (void)hipStreamSynchronize(c->stream);
     return ah_fail(c, AH_EHIP, "string_ranges: the launch failed");
   }
-  if (int rc = ah_cumulative_sum(c, AH_INT64, lens, nullptr, 0, n, nullptr, 0, 0, incl, nullptr, nullptr)) {
-    (void)hipStreamSynchronize(c->stream);   // (ah_cumulative_sum left its own message)
+  int rc = varout_enqueue(c, v, n, ow, out_offsets, /*caller_words=*/false);
+  int64_t total = 0;
+  bool overflow = false;
+  if (rc == AH_OK) rc = varout_finish(c, v, &total, &overflow);
+  if (rc != AH_OK) {
+    (void)hipStreamSynchronize(c->stream);   // (the failed step left its own message)
     return rc;
   }
-  const unsigned ogrid = ah_stream_grid(c, ah_ceil_div(n + 1, kBlock), 8);
-  unsigned* never = (unsigned*)&c->dscalars[3];   // (the overflow word of offsets_kernel: a row's result is never longer than the row)
-  if (ow == 4) offsets_kernel<int32_t, kBlock><<<ogrid, kBlock, 0, c->stream>>>(incl, n, (int32_t*)out_offsets, never);
-  else offsets_kernel<long long, kBlock><<<ogrid, kBlock, 0, c->stream>>>(incl, n, (long long*)out_offsets, never);
-  AH_LAUNCH_CHECK(c);
-  AH_HIP(c, hipMemcpyAsync(c->pinned, incl + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  AH_HIP(c, hipStreamSynchronize(c->stream));
-  if (out_total_bytes_host) *out_total_bytes_host = *(volatile int64_t*)&c->pinned[0];
+  if (out_total_bytes_host) *out_total_bytes_host = total;
   return AH_OK;
 }
 
 AH_EXPORT int ah_string_gather(ah_ctx* c, const ah_cmp_operand* operand, const void* starts, const void* out_offsets, int64_t n,
                                const uint8_t* map, uint8_t* out_data) {
   AH_ENTER(c);
-  if (int rc = check_column(c, "string_gather", operand, n)) return rc;
+  if (int rc = check_column(c, "string_gather", operand, n, false)) return rc;
   if (n == 0) return AH_OK;
   const int ow = operand->offset_width;
   if (bad_buffer(starts, ow) || bad_buffer(out_offsets, ow)) return ah_fail(c, AH_EINVALID, "string_gather: null or misaligned starts / offsets");
@@ -508,7 +461,7 @@ AH_EXPORT int ah_string_gather(ah_ctx* c, const ah_cmp_operand* operand, const v
   if (map) memcpy(map_dev.b, map, 256);
   else memset(map_dev.b, 0, 256);
   const int T = tile_bytes(c);
-  const unsigned grid = (unsigned)(c->num_cu > 0 ? c->num_cu : 1) * kWgPerCu;
+  const unsigned grid = tile_grid(c);
   if (ow == 4) {
     if (map) gather_kernel<int32_t, true><<<grid, kBlock, 0, c->stream>>>(operand->data, (const int32_t*)starts, (const int32_t*)out_offsets, n, map_dev, T, out_data);
     else gather_kernel<int32_t, false><<<grid, kBlock, 0, c->stream>>>(operand->data, (const int32_t*)starts, (const int32_t*)out_offsets, n, map_dev, T, out_data);

@@ -23,6 +23,7 @@
 // 24 B/row), the value bytes once in and once out in the second.
 #include "ah_bytes.h"
 #include "ah_index.h"
+#include "ah_varout.h"
 
 namespace {
 
@@ -67,16 +68,11 @@ __global__ __launch_bounds__(kBlock) void copy_kernel(const OffT* __restrict__ o
 
 
 template <typename OffT, typename IdxT>
-int run_offsets(ah_ctx* c, const void* offsets, const uint8_t* vvalid, int64_t voff, int64_t nvalues, const void* idx, const uint8_t* ivalid,
-                int64_t ioff, int64_t n, void* out_offsets, uint8_t* out_valid, long long* lens, long long* incl) {
+int run_lens(ah_ctx* c, const void* offsets, const uint8_t* vvalid, int64_t voff, int64_t nvalues, const void* idx, const uint8_t* ivalid,
+             int64_t ioff, int64_t n, uint8_t* out_valid, long long* lens) {
   const unsigned grid = ah_stream_grid(c, ah_ceil_div(ah_ceil_div(n, 64), kBlock / 64), 8);
   lens_kernel<OffT, IdxT><<<grid, kBlock, 0, c->stream>>>((const OffT*)offsets, vvalid, voff, (unsigned long long)nvalues, (const IdxT*)idx, ivalid,
-                                                         ioff, n, lens, out_valid, (unsigned long long*)&c->dscalars[1]);
-  AH_LAUNCH_CHECK(c);
-  int rc = ah_cumulative_sum(c, AH_INT64, lens, nullptr, 0, n, nullptr, 0, 0, incl, nullptr, nullptr);
-  if (rc != AH_OK) return rc;
-  offsets_kernel<OffT, kBlock><<<ah_stream_grid(c, ah_ceil_div(n + 1, kBlock), 8), kBlock, 0, c->stream>>>(incl, n, (OffT*)out_offsets,
-                                                                                                          (unsigned*)&c->dscalars[3]);
+                                                         ioff, n, lens, out_valid, (unsigned long long*)&c->dscalars[kDsVarFirst]);
   AH_LAUNCH_CHECK(c);
   return AH_OK;
 }
@@ -110,35 +106,31 @@ AH_EXPORT int ah_take_binary_offsets(ah_ctx* c, int offset_width, const void* of
     AH_HIP(c, hipMemsetAsync(out_offsets, 0, (size_t)offset_width, c->stream));
     return AH_OK;
   }
-  // temporaries in the context's temp arena (the scan called below uses the scratch arena)
-  const size_t col = (((size_t)nidx * 8) + 255) & ~(size_t)255;
-  void* arena;
-  rc = ah_temp_reserve(c, 2 * col, &arena);
+  VarOut v;
+  rc = varout_begin(c, nidx, 0, /*can_overflow=*/true, &v);   // (zeroes the valid count and the overflow flag)
   if (rc != AH_OK) return rc;
-  long long* lens = (long long*)arena;
-  long long* incl = (long long*)((uint8_t*)arena + col);
-  AH_HIP(c, hipMemsetAsync(&c->dscalars[1], 0xFF, sizeof(uint64_t), c->stream));  // first bad position
-  AH_HIP(c, hipMemsetAsync(&c->dscalars[2], 0, 2 * sizeof(uint64_t), c->stream)); // valid count, overflow flag
+  AH_HIP(c, hipMemsetAsync(&c->dscalars[kDsVarFirst], 0xFF, sizeof(uint64_t), c->stream));  // first bad position
   const bool known = with_index_type(idx_byte_width, idx_signed, [&](auto it) {
     using IdxT = typename decltype(it)::type;
-    rc = offset_width == 4 ? run_offsets<int32_t, IdxT>(c, offsets, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_offsets, out_valid, lens, incl)
-                           : run_offsets<int64_t, IdxT>(c, offsets, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_offsets, out_valid, lens, incl);
+    rc = offset_width == 4 ? run_lens<int32_t, IdxT>(c, offsets, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_valid, v.lens)
+                           : run_lens<int64_t, IdxT>(c, offsets, vvalid, voff, nvalues, idx, ivalid, ioff, nidx, out_valid, v.lens);
   });
   if (!known) return ah_fail(c, AH_EINDEX, "invalid indices byte width");
   if (rc != AH_OK) return rc;
   if (out_valid && out_null_count_host) {
-    rc = ah_popcount_async(c, out_valid, 0, nidx, (unsigned long long*)&c->dscalars[2]);
+    rc = ah_popcount_async(c, out_valid, 0, nidx, (unsigned long long*)&c->dscalars[kDsVarCount]);
     if (rc != AH_OK) return rc;
   }
-  AH_HIP(c, hipMemcpyAsync(c->pinned, &c->dscalars[1], 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  AH_HIP(c, hipMemcpyAsync(&c->pinned[3], incl + nidx - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  AH_HIP(c, hipStreamSynchronize(c->stream));
-  const uint64_t bad_pos = *(volatile uint64_t*)&c->pinned[0];
-  const uint64_t nvalid = *(volatile uint64_t*)&c->pinned[1];
-  const unsigned overflow = *(volatile unsigned*)&c->pinned[2];
-  const int64_t total = *(volatile int64_t*)&c->pinned[3];
+  rc = varout_enqueue(c, v, nidx, offset_width, out_offsets, /*caller_words=*/true);
+  if (rc != AH_OK) return rc;
+  int64_t total = 0;
+  bool overflow = false;
+  rc = varout_finish(c, v, &total, &overflow);
+  if (rc != AH_OK) return rc;
+  const uint64_t bad_pos = *(volatile uint64_t*)&c->pinned[kVarPinFirst];
+  const uint64_t nvalid = *(volatile uint64_t*)&c->pinned[kVarPinCount];
   if (bad_pos != ~0ull) return take_fail_bad_index(c, idx, idx_byte_width, idx_signed, bad_pos, bad_index_host);
-  if (overflow & 1u) return ah_fail(c, AH_EINVALID, "binary output offset overflow");  // :1245
+  if (overflow) return ah_fail(c, AH_EINVALID, "binary output offset overflow");  // :1245
   if (out_null_count_host) *out_null_count_host = out_valid ? nidx - (int64_t)nvalid : 0;
   if (out_total_bytes_host) *out_total_bytes_host = total;
   return AH_OK;

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from ._native import lib, strings_lib, string_transform_lib, check
+from ._native import lib, check
 
 
 def _ptr(x) -> Optional[int]:
@@ -631,7 +631,7 @@ class Context:
         ro = _CmpOperand(right[0], right[1], _ptr(right[2]), _ptr(right[3]), right[4], right[5])
         check(self.handle, lib.ah_compare_binary(self.handle, cmpop, C.byref(lo), C.byref(ro), n, _ptr(out_bits), out_bit_offset))
 
-    # ---- string predicates (libarrowhip_strings.so: csrc/strings/ah_string_match.hip, include/arrowhip_strings.h).  column: (offset_width, byte_width, offsets, data, off) — offset_width 4 / 8; 0 (fixed
+    # ---- string predicates (csrc/ah_string_match.hip, include/arrowhip_strings.h).  column: (offset_width, byte_width, offsets, data, off) — offset_width 4 / 8; 0 (fixed
     # slots of byte_width bytes) only for string_length without utf8.  pattern / program: bytes on the host.
     @staticmethod
     def _column(column) -> _CmpOperand:
@@ -641,25 +641,25 @@ class Context:
         """op 0 the pattern occurs in the row, 1 the row starts with it, 2 ends with it, 3 is it: bits [out_bit_offset, + n) of
         out_bits, every other bit kept; every row computed, nulls included; no synchronisation (ah_string_match)"""
         col = self._column(column)
-        check(self.handle, strings_lib.ah_string_match(self.handle, op, C.byref(col), n, C.c_char_p(bytes(pattern)), len(pattern), _ptr(out_bits), out_bit_offset))
+        check(self.handle, lib.ah_string_match(self.handle, op, C.byref(col), n, C.c_char_p(bytes(pattern)), len(pattern), _ptr(out_bits), out_bit_offset))
 
     def string_find(self, column, n: int, pattern: bytes, out_width: int, out) -> None:
         """out[i] (Int32 / Int64 by out_width) = the byte index of the pattern's first occurrence in row i, -1 for none (ah_string_find)"""
         col = self._column(column)
-        check(self.handle, strings_lib.ah_string_find(self.handle, C.byref(col), n, C.c_char_p(bytes(pattern)), len(pattern), out_width, _ptr(out)))
+        check(self.handle, lib.ah_string_find(self.handle, C.byref(col), n, C.c_char_p(bytes(pattern)), len(pattern), out_width, _ptr(out)))
 
     def string_like(self, column, n: int, utf8: bool, program: bytes, out_bits, out_bit_offset: int = 0) -> None:
         """SQL LIKE with the pattern compiled by compute.like_compile; utf8: `_` is one code point, else one byte (ah_string_like)"""
         col = self._column(column)
-        check(self.handle, strings_lib.ah_string_like(self.handle, C.byref(col), n, int(bool(utf8)), C.c_char_p(bytes(program)), len(program), _ptr(out_bits),
+        check(self.handle, lib.ah_string_like(self.handle, C.byref(col), n, int(bool(utf8)), C.c_char_p(bytes(program)), len(program), _ptr(out_bits),
                                               out_bit_offset))
 
     def string_length(self, column, n: int, utf8: bool, out_width: int, out) -> None:
         """out[i] = the bytes of row i, or (utf8) its bytes that are not 10xxxxxx continuation bytes (ah_string_length)"""
         col = self._column(column)
-        check(self.handle, strings_lib.ah_string_length(self.handle, C.byref(col), n, int(bool(utf8)), out_width, _ptr(out)))
+        check(self.handle, lib.ah_string_length(self.handle, C.byref(col), n, int(bool(utf8)), out_width, _ptr(out)))
 
-    # ---- string transforms (libarrowhip_string_transform.so: csrc/string_transform/ah_string_transform.hip, include/arrowhip_string_transform.h).
+    # ---- string transforms (csrc/ah_string_transform.hip, include/arrowhip_strings.h).
     # column as above, offset_width 4 / 8; out_starts / out_offsets hold values of that width.
     def string_ranges(self, op: int, column, n: int, out_starts, out_offsets, *, start: int = 0, stop=None, sides: int = 3, chars: bytes = b"",
                       valid=None, valid_offset: int = 0) -> int:
@@ -669,7 +669,7 @@ class Context:
         Returns the byte total — the call's one synchronisation (ah_string_ranges)"""
         col = self._column(column)
         total = C.c_int64(0)
-        check(self.handle, string_transform_lib.ah_string_ranges(self.handle, op, start, 0 if stop is None else stop, int(stop is not None), sides,
+        check(self.handle, lib.ah_string_ranges(self.handle, op, start, 0 if stop is None else stop, int(stop is not None), sides,
                                                                  C.c_char_p(bytes(chars)), len(chars), C.byref(col), _ptr(valid), valid_offset, n,
                                                                  _ptr(out_starts), _ptr(out_offsets), C.byref(total)))
         return total.value
@@ -679,7 +679,7 @@ class Context:
         one is given; no synchronisation (ah_string_gather)"""
         col = self._column(column)
         assert map is None or len(map) == 256
-        check(self.handle, string_transform_lib.ah_string_gather(self.handle, C.byref(col), _ptr(starts), _ptr(out_offsets), n,
+        check(self.handle, lib.ah_string_gather(self.handle, C.byref(col), _ptr(starts), _ptr(out_offsets), n,
                                                                  None if map is None else C.c_char_p(bytes(map)), _ptr(out_data)))
 
     def compare_decimal(self, cmpop: int, left, right, n: int, out_bits, out_bit_offset: int = 0) -> None:

@@ -32,8 +32,7 @@
 #include <vector>
 
 #include "../../include/arrowhip.h"
-#include "../../include/arrowhip_strings.h"   // the string predicates: libarrowhip_strings.so, on the same ah_ctx
-#include "../../include/arrowhip_string_transform.h"   // the string transforms: libarrowhip_string_transform.so, on the same ah_ctx
+#include "../../include/arrowhip_strings.h"   // the string predicates and transforms of libarrowhip.so
 
 namespace arrowhip {
 

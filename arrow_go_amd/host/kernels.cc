@@ -10,7 +10,6 @@
 #include "arrowhip_compute.h"
 #include "like_program.h"
 
-#include <dlfcn.h>
 
 #include <algorithm>
 #include <cstring>
@@ -3008,35 +3007,6 @@ void RegisterConditional(FunctionRegistry* reg) {
 // kernels compute every row, null slots included.
 namespace {
 
-// The four entry points are libarrowhip_strings.so's (include/arrowhip_strings.h), a library beside libarrowhip.so.  It is opened on
-// first use, by name through this library's run path, so that whoever links the host layer needs libarrowhip.so alone; a library
-// that is missing or lacks an entry point is an error of the call — there is no other path.
-struct StringsLib {
-  decltype(&ah_string_match) match = nullptr;
-  decltype(&ah_string_find) find = nullptr;
-  decltype(&ah_string_like) like = nullptr;
-  decltype(&ah_string_length) length = nullptr;
-  std::string error;
-};
-const StringsLib& Strings() {
-  static const StringsLib lib = [] {
-    StringsLib l;
-    void* h = dlopen("libarrowhip_strings.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) {
-      const char* e = dlerror();
-      l.error = std::string("libarrowhip_strings.so cannot be loaded: ") + (e ? e : "unknown error");
-      return l;
-    }
-    l.match = (decltype(l.match))dlsym(h, "ah_string_match");
-    l.find = (decltype(l.find))dlsym(h, "ah_string_find");
-    l.like = (decltype(l.like))dlsym(h, "ah_string_like");
-    l.length = (decltype(l.length))dlsym(h, "ah_string_length");
-    if (!l.match || !l.find || !l.like || !l.length) l.error = "libarrowhip_strings.so lacks an entry point of include/arrowhip_strings.h";
-    return l;
-  }();
-  return lib;
-}
-
 enum StringFn { kFnSubstring = AH_STR_SUBSTRING, kFnStartsWith = AH_STR_STARTS_WITH, kFnEndsWith = AH_STR_ENDS_WITH, kFnFind, kFnLike, kFnBinaryLength, kFnUtf8Length };
 
 Status ExecStringMatch(KernelCtx* k, const ExecSpan& b, ExecResult* out, const char* name, int fn) {
@@ -3049,8 +3019,6 @@ Status ExecStringMatch(KernelCtx* k, const ExecSpan& b, ExecResult* out, const c
     opts = static_cast<const MatchSubstringOptions*>(given);
   }
   if (out->len == 0) return Status::OK();   // (a scalar argument never gets here: ScalarFunction::arrays_only)
-  const StringsLib& lib = Strings();
-  if (!lib.error.empty()) return Status::Make(StatusCode::Invalid, lib.error);
   const ArraySpan& in = b.values[0].array;
   const ByteLayout l = LayoutOf(in);
   const ah_cmp_operand col{l.offset_width, l.byte_width, l.offsets, l.data, l.offset, 0};
@@ -3059,16 +3027,16 @@ Status ExecStringMatch(KernelCtx* k, const ExecSpan& b, ExecResult* out, const c
   const int out_width = in.type->id == Type::LARGE_STRING || in.type->id == Type::LARGE_BINARY ? 8 : 4;
   switch (fn) {
     case kFnFind:
-      return s->FromStatus(lib.find(s->ctx(), &col, out->len, pattern, m, out_width, out->buffers[1].buf + out->offset * out_width));
+      return s->FromStatus(ah_string_find(s->ctx(), &col, out->len, pattern, m, out_width, out->buffers[1].buf + out->offset * out_width));
     case kFnLike: {
       const std::vector<uint8_t> program = like::Compile(pattern, (size_t)m);
-      return s->FromStatus(lib.like(s->ctx(), &col, out->len, IsUtf8(in.type->id) ? 1 : 0, program.data(), (int64_t)program.size(), out->buffers[1].buf, out->offset));
+      return s->FromStatus(ah_string_like(s->ctx(), &col, out->len, IsUtf8(in.type->id) ? 1 : 0, program.data(), (int64_t)program.size(), out->buffers[1].buf, out->offset));
     }
     case kFnBinaryLength:
     case kFnUtf8Length:
-      return s->FromStatus(lib.length(s->ctx(), &col, out->len, fn == kFnUtf8Length ? 1 : 0, out_width, out->buffers[1].buf + out->offset * out_width));
+      return s->FromStatus(ah_string_length(s->ctx(), &col, out->len, fn == kFnUtf8Length ? 1 : 0, out_width, out->buffers[1].buf + out->offset * out_width));
     default:
-      return s->FromStatus(lib.match(s->ctx(), fn, &col, out->len, pattern, m, out->buffers[1].buf, out->offset));
+      return s->FromStatus(ah_string_match(s->ctx(), fn, &col, out->len, pattern, m, out->buffers[1].buf, out->offset));
   }
 }
 
@@ -3115,30 +3083,6 @@ void RegisterStringMatch(FunctionRegistry* reg) {
 // serves all thirteen: ah_string_ranges (source starts, output offsets, the byte total — the call's one synchronisation), the
 // allocation, ah_string_gather.  The output's validity is the input's (NullIntersection); a null row has length 0.
 namespace {
-
-// libarrowhip_string_transform.so (include/arrowhip_string_transform.h), opened on the first transform call as Strings() opens its
-// library: a library that is missing or lacks an entry point is an error of the call — there is no other path.
-struct StringTransformLib {
-  decltype(&ah_string_ranges) ranges = nullptr;
-  decltype(&ah_string_gather) gather = nullptr;
-  std::string error;
-};
-const StringTransformLib& StringTransform() {
-  static const StringTransformLib lib = [] {
-    StringTransformLib l;
-    void* h = dlopen("libarrowhip_string_transform.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) {
-      const char* e = dlerror();
-      l.error = std::string("libarrowhip_string_transform.so cannot be loaded: ") + (e ? e : "unknown error");
-      return l;
-    }
-    l.ranges = (decltype(l.ranges))dlsym(h, "ah_string_ranges");
-    l.gather = (decltype(l.gather))dlsym(h, "ah_string_gather");
-    if (!l.ranges || !l.gather) l.error = "libarrowhip_string_transform.so lacks an entry point of include/arrowhip_string_transform.h";
-    return l;
-  }();
-  return lib;
-}
 
 enum TransformChars { kCharsNone, kCharsBytes, kCharsCodePoints, kCharsWhitespace };
 enum TransformMap { kMapNone, kMapUpper, kMapLower };
@@ -3198,8 +3142,6 @@ Status ExecStringTransform(KernelCtx* k, const ExecSpan& b, ExecResult* out, con
     out->buffers[2].WrapBuffer(db);
     return Status::OK();
   }
-  const StringTransformLib& lib = StringTransform();
-  if (!lib.error.empty()) return Status::Make(StatusCode::Invalid, lib.error);
   int64_t start = 0, stop = 0;
   int has_stop = 0;
   std::string chars;
@@ -3221,12 +3163,12 @@ Status ExecStringTransform(KernelCtx* k, const ExecSpan& b, ExecResult* out, con
   const uint8_t* valid = in.MayHaveNulls() ? in.buffers[0].buf : nullptr;
   AHC_RETURN_NOT_OK(k->Allocate(n * ow, &sb, /*zero_all=*/false));
   int64_t total = 0;
-  AHC_RETURN_NOT_OK(s->FromStatus(lib.ranges(s->ctx(), f.op, start, stop, has_stop, f.sides, (const uint8_t*)chars.data(), (int64_t)chars.size(), &col, valid,
+  AHC_RETURN_NOT_OK(s->FromStatus(ah_string_ranges(s->ctx(), f.op, start, stop, has_stop, f.sides, (const uint8_t*)chars.data(), (int64_t)chars.size(), &col, valid,
                                              in.offset, n, sb->dptr, ob->dptr, &total)));
   AHC_RETURN_NOT_OK(k->Allocate(total, &db, /*zero_all=*/false));
   out->buffers[2].WrapBuffer(db);
   if (total == 0) return Status::OK();
-  return s->FromStatus(lib.gather(s->ctx(), &col, sb->dptr, ob->dptr, n, f.map == kMapNone ? nullptr : map, (uint8_t*)db->dptr));
+  return s->FromStatus(ah_string_gather(s->ctx(), &col, sb->dptr, ob->dptr, n, f.map == kMapNone ? nullptr : map, (uint8_t*)db->dptr));
 }
 
 }  // namespace

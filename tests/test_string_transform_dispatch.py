@@ -1,13 +1,8 @@
 """The string transforms in the function registry, resolved without a device: the thirteen names and their kernel counts, the types
 each accepts and refuses (with the registry's usual dispatch error), the output type = the input type, and what the functions answer
-to their options string.  The two C entry points live in a third library, libarrowhip_string_transform.so: header == nm -D is
-checked here, and that its names collide with neither of the other two headers."""
-import os
-import subprocess
-
+to their options string.  (The two C entry points are libarrowhip.so's: tests/test_string_match_dispatch.py holds the header check.)"""
 import pytest
 
-from arrow_go_amd import _native as N
 from arrow_go_amd import compute as ac
 from tests.test_string_match_dispatch import dispatch_ids
 
@@ -98,17 +93,3 @@ def test_trim_options():
     for name in ("ascii_upper", "ascii_lower", "ascii_trim_whitespace", "ascii_ltrim_whitespace", "ascii_rtrim_whitespace"):
         ac.validate_options(name, "")
     assert ac.trim_options("a;=") == "characters_hex=613b3d" and ac.trim_options(b"\xff\x00") == "characters_hex=ff00" and ac.trim_options("") == "characters_hex="
-
-
-def test_the_library_exports_exactly_its_header():
-    declared = N.declared_symbols(N.STRING_TRANSFORM_HEADER_PATH)
-    assert declared == ["ah_string_gather", "ah_string_ranges"]
-    out = subprocess.check_output(["nm", "-D", "--defined-only", N.STRING_TRANSFORM_LIB_PATH], text=True)
-    assert sorted(l.split()[-1] for l in out.splitlines() if " T " in l) == declared
-    assert not set(declared) & set(N.declared_symbols())
-    assert not set(declared) & set(N.declared_symbols(N.STRINGS_HEADER_PATH))
-    src = '#include "arrowhip_string_transform.h"\nint main(void) { return 0; }\n'   # plain C11, like the other boundary headers
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-pedantic", "-fsyntax-only", "-I", os.path.dirname(N.STRING_TRANSFORM_HEADER_PATH), "-x", "c", "-"],
-                   input=src, text=True, check=True)
-    needed = subprocess.check_output(["readelf", "-d", N.STRING_TRANSFORM_LIB_PATH], text=True)
-    assert "libarrowhip.so" in needed and "$ORIGIN" in needed
